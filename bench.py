@@ -13,10 +13,13 @@ no data-path collective; only the timing is reduced (MAX).
 /root/reference/code/train_rgb.py:196-202, ``ddp_setup`` :53-57); under a launcher it checks that the
 process group really has N ranks.  ``n_gpus`` on the line is what the process group reports.
 
-Secondary legs on the same JSON line (none of them is ``value``): other conv precisions, batch sweep,
-the fitting step of BASELINE configs 3 (RGB-driven, Encoder in the step) and 4 (3DMM-driven) with the
-all-reduce of the shared gradients, a 500-frame synthetic fit (config 3 as written), the batched
-audio-driven reenactment of config 5, the CPU oracle baseline.
+A plain run measures the headline only: set-up, settle + W warm-up steps, K timed steps, the
+outputs of the last timed step if ``--dump-outputs DIR`` is given, the line.  ``--full`` adds the
+secondary legs (none of them is ``value``): the per-kernel roofline pass of the headline, other conv
+precisions, batch sweep, the fitting step of BASELINE configs 3 (RGB-driven, Encoder in the step) and
+4 (3DMM-driven) with the all-reduce of the shared gradients, a 500-frame synthetic fit (config 3 as
+written), the batched audio-driven reenactment of config 5, the CPU oracle baseline; and it writes
+bench_detail.json.
 
 Prints ONE JSON line on rank 0 (see the contract in the task description).
 """
@@ -45,6 +48,8 @@ MFMA_F16_PEAK_TFLOPS = 2500.0   # v_mfma_f32_32x32x16_f16 dense peak (same rate 
 
 
 LINE_BYTE_BUDGET = 6000      # the driver parses the ONE stdout line out of a bounded tail (round 5's 21.6 KB line came back unparsed)
+DUMP_BYTE_BUDGET = 60 << 20  # --dump-outputs writes at most 64 MB in all (this + the .npy headers)
+RENDER_SEED = 1234           # device RNG seed set before every timed region: the renderer's uniforms are drawn inside the step
 
 
 def _sig(v, digits=5):
@@ -67,7 +72,7 @@ def _rows_stats() -> dict:
     return ops.ROWS_STATS
 
 
-def compact_line(full: dict) -> dict:
+def compact_line(full: dict, detail: bool = True) -> dict:
     """The ONE line rank 0 prints: the contract's keys, the dominant kernel's `roofline`, `cpu_baseline`, and a few dozen scalars
     (fitting steps, family roofline fractions, the other legs' headline numbers).  Everything else `main` measured — per-layer
     and per-kernel tables, percentiles, phases, prose — goes to bench_detail.json (and stderr).  tests/test_bench_line.py holds the
@@ -151,7 +156,10 @@ def compact_line(full: dict) -> dict:
     if fam:
         line["roofline_train_frac_ms"] = fam
     line["leg_seconds"] = full.get("leg_seconds")
-    line["detail"] = "bench_detail.json (every table of this run; also on stderr)"
+    if not roof:                 # a plain run: no roofline pass
+        line.pop("roofline")
+    if detail:
+        line["detail"] = "bench_detail.json (every table of this run; also on stderr)"
     line = _sig(line)
     # never lose the line to its own length: drop the least important groups until it fits
     for victim in ("leg_seconds", "roofline_train_frac_ms", "per_rank_frames_per_s"):
@@ -176,6 +184,29 @@ def write_detail(full: dict, where=None) -> list:
     sys.stderr.write("[bench detail] " + json.dumps(full) + "\n")
     sys.stderr.flush()
     return paths
+
+
+def dump_outputs(outputs: dict, where: str, seed: int = 0) -> dict:
+    """--dump-outputs: each array of `outputs` (name -> tensor) as `where`/<name>.npy in float32, smallest first.  An array larger
+    than its share of what is left of DUMP_BYTE_BUDGET is written as a fixed, seeded sample of its elements instead: 1-D, flat
+    indices in increasing order, the same indices for the same shape in every run.  Returns {name: {shape, sampled}}."""
+    import numpy as np
+    import torch
+    os.makedirs(where, exist_ok=True)
+    todo = sorted(outputs.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left, info = DUMP_BYTE_BUDGET, {}
+    for i, (name, t) in enumerate(todo):
+        a = t.detach().float().cpu()
+        share = left // (len(todo) - i)
+        sampled = 4 * a.numel() > share
+        if sampled:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(seed))[:share // 4].sort().values
+            a = a.reshape(-1)[idx]
+        arr = a.numpy()
+        np.save(os.path.join(where, name + ".npy"), arr)
+        left -= arr.nbytes
+        info[name] = {"shape": list(t.shape), "sampled": sampled}
+    return info
 
 
 def parse():
@@ -217,10 +248,21 @@ def parse():
                          "path on a 1-GPU box, numbers not comparable)")
     ap.add_argument("--share-device", action="store_true", help="developer: every rank uses cuda:0")
     ap.add_argument("--detail", default=None,
-                    help="file for the full result object (default: bench_detail.json next to this script and under gpurun_out/)")
+                    help="file for the full result object (a plain run writes it only when this is given; --full defaults to "
+                         "bench_detail.json next to this script)")
     ap.add_argument("--no-f16-leg", action="store_true",
                     help="skip the legs with the super-resolution / all convs on the single-pass fp16 MFMA path")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg (roofline pass, other precisions, batch sweep, fitting steps and fits, audio "
+                         "reenactment, CPU baseline) and write bench_detail.json; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (image, image_raw, image_depth of rank 0) "
+                         "as DIR/<name>.npy in float32; an array beyond its share of 60 MiB is written as a fixed, seeded sample "
+                         "of its elements (1-D)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port() -> int:
@@ -827,7 +869,7 @@ def main():
     # the generator the parity tests run the oracle against at this batch (tests/test_gpu_round3.py::benched): EG3D init
     # + non-zero biases and noise strengths, so that the timed state is the tested state
     gen = perturb_state(TriPlaneGenerator(cfg, seed=0)).requires_grad_(False)
-    state = state_cpu(gen) if (rank == 0 and world == 1 and not args.no_cpu_baseline) else None
+    state = state_cpu(gen) if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline) else None
     gen = gen.to(dev)
     B = args.batch
     # each rank renders its own frames (frame-parallel): different seed per rank
@@ -837,11 +879,12 @@ def main():
     def step():
         # the renderer's stratified / importance uniforms are DRAWN INSIDE the timed call, as EG3D's ImportanceRenderer does on every
         # synthesis (torch.rand on the device: 50 M floats at B = 32); the parity legs hand over fixed ones
-        return gen.synthesis(ws, c, noise_mode="const")["image"]
+        return gen.synthesis(ws, c, noise_mode="const")
 
-    def render_leg(precision, sr_precision=None, events=True, sr_storage="f32"):
+    def render_leg(precision, sr_precision=None, events=True, sr_storage="f32", outputs=None):
         """W warm-up + K timed steps with the conv GEMMs in ``precision`` (super-resolution blocks: ``sr_precision``
-        when given); (seconds max over ranks, this rank's seconds, event table)."""
+        when given); (seconds max over ranks, this rank's seconds, event table).  ``outputs`` (a dict) receives what the
+        last timed step returned."""
         gen.conv_precision = precision
         gen.sr_conv_precision = sr_precision
         gen.sr_storage = sr_storage
@@ -851,6 +894,7 @@ def main():
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
+        torch.cuda.manual_seed(RENDER_SEED + rank)    # (the timed steps' uniforms do not depend on how many steps `settle` took)
         gen.timing = {} if events else None
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
         # (as `timeit` does: no cyclic-GC pass inside the timed region — a generation-2 collection over the heap this process
@@ -861,7 +905,7 @@ def main():
         t0 = time.perf_counter()
         marks[0].record()
         for i in range(args.steps):
-            img = step()
+            res = step()
             marks[i + 1].record()
         torch.cuda.synchronize()
         own = time.perf_counter() - t0
@@ -876,7 +920,9 @@ def main():
             t = torch.tensor([dt], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
-        assert torch.isfinite(img).all()
+        assert torch.isfinite(res["image"]).all()
+        if outputs is not None:
+            outputs.update(res)
         return dt, own, timing
 
     def sweep_leg(b, precision, steps=20, warmup=3):
@@ -936,15 +982,22 @@ def main():
             n_settled += 1
     timed_leg("settle", settle)
     # the headline leg first, exactly as the contract words it (W warm-up steps, then K timed steps), WITHOUT the
-    # per-kernel timing events (they cost host time per launch); a second pass of the same leg collects the events
-    # the roofline objects are computed from
-    dt, own_dt, timing_head = timed_leg("render", render_leg, prec, None, False)
-    _, _, timing = timed_leg("render", render_leg, prec)
-    timing["step"] = timing_head["step"]
+    # per-kernel timing events (they cost host time per launch); with --full a second pass of the same leg collects the
+    # events the roofline objects are computed from
+    last = {} if args.dump_outputs else None
+    dt, own_dt, timing_head = timed_leg("render", render_leg, prec, None, False, "f32", last)
+    if last is not None:
+        if rank == 0:
+            timed_leg("dump_outputs", dump_outputs, last, args.dump_outputs)
+        del last
+    timing = timing_head
+    if args.full:
+        _, _, timing = timed_leg("render", render_leg, prec)
+        timing["step"] = timing_head["step"]
     dt32 = timing32 = dtb3 = None
     # single-GPU diagnostics (other precisions, batch sweeps, the LPIPS-cost leg, the CPU baseline) are skipped at N > 1: a
     # multi-GPU run measures the headline, the fitting legs with their collectives and the sharded fits — nothing else
-    diag = n_ranks == 1
+    diag = n_ranks == 1 and args.full
     if prec != "fp32" and not args.no_fp32_leg and diag:
         dt32, _, timing32 = timed_leg("render_other_precisions", render_leg, "fp32")
         if prec != "bf16x3":
@@ -975,7 +1028,7 @@ def main():
                 torch.cuda.empty_cache()
                 sweep[str(b)] = {"skipped": "out of memory"}
     gen.conv_precision, gen.sr_conv_precision = prec, None
-    overflow = gen.f16_range_report()
+    overflow = gen.f16_range_report() if args.full else None
 
     def agg(key, table=None):
         evs = (timing if table is None else table).get(key, [])
@@ -992,7 +1045,7 @@ def main():
 
     del ws, c, us, ui
     train = train_B = fit = fit3 = audio = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         torch.cuda.empty_cache()
         train, train_B = timed_leg("train_steps", train_legs, args, args.preset, dev, rank, world, dist)
         if args.fit_frames > 0:
@@ -1000,7 +1053,7 @@ def main():
             torch.cuda.empty_cache()
         if args.fit3dmm_frames_per_rank > 0:
             fit3 = timed_leg("fit_3dmm_sharded", fit3dmm_leg, args, args.preset, dev, rank, world, dist)
-    if args.audio_frames > 0:
+    if args.full and args.audio_frames > 0:
         torch.cuda.empty_cache()
         audio = timed_leg("audio_reenactment", audio_leg, args, args.preset, dev, rank, world, dist)
 
@@ -1017,7 +1070,32 @@ def main():
             pass
         return None
 
-    if rank == 0:
+    def headline():
+        """The contract's keys and what the headline leg itself measured: all that a plain run reports."""
+        res = {
+            "metric": "rendered 512^2 frames/sec (96 depth samples), whole job",
+            "value": n_ranks * B * args.steps / dt, "unit": "frames/s", "n_gpus": n_ranks, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32" if prec == "fp32" else f"f32 tensors and accumulation; conv GEMM products as {prec} "
+                                                  f"(operands split into {SPLIT_ELEM[prec]} parts, {SPLIT_MFMAS[prec]} "
+                                                  f"MFMAs per product" + (": 22 mantissa bits, fp32-class results)"
+                                                                          if prec == "f16x3" else ")"),
+            "data": "synthetic",
+            "renderer_uniforms": "drawn inside the timed call (torch.rand on the device per synthesis, as EG3D's ImportanceRenderer does)",
+            "config": {"workload": f"{cfg.name}: synthesis(ws[B,14,512], c[B,25]) forward, 512x512 out, 128^2 rays x "
+                                   f"(48+48) samples, random-init weights, random latents+cameras",
+                       "frames_per_step_per_gpu": B, "parallelism": f"frame-parallel x{n_ranks}", "conv_precision": prec},
+            "per_rank_frames_per_s": per_rank,
+            # (max - min) / median over the ranks: frame-parallel rendering has no collective in the timed region, so a spread
+            # beyond a few per cent means one GPU (clock, thermal state, a noisy neighbour on its NUMA node) holds the job back
+            "per_rank_spread": ((max(per_rank) - min(per_rank)) / sorted(per_rank)[len(per_rank) // 2]) if per_rank else 0.0,
+        }
+        res["step_ms"] = _pct(timing_head["step"])       # per-step HIP event pairs of the timed region (this rank)
+        res["step_ms"]["argmax"] = max(range(args.steps), key=lambda i: timing_head["step"][i])      # (which step a stall hit)
+        return res
+
+    if rank == 0 and args.full:
         frames = n_ranks * B * args.steps
         rm_ms, rm_bytes, rm_n = agg("raymarch")
         rm_gbs = rm_bytes / (rm_ms * 1e-3) / 1e9
@@ -1095,24 +1173,8 @@ def main():
         floor_ms = (gather_bytes / (L2_PEAK_GBS * 1e9) + dec_flops / (dec_peak * 1e12)) * 1e3
         rm_traffic = profiled_traffic("raymarch_kernel")
         compulsory = frames_per_launch * (3 * cfg.plane_resolution ** 2 * 32 * 4 + r * (34 + s_tot) * 4)
-        out = {
-            "metric": "rendered 512^2 frames/sec (96 depth samples), whole job",
-            "value": frames / dt, "unit": "frames/s", "n_gpus": n_ranks, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32" if prec == "fp32" else f"f32 tensors and accumulation; conv GEMM products as {prec} "
-                                                  f"(operands split into {SPLIT_ELEM[prec]} parts, {SPLIT_MFMAS[prec]} "
-                                                  f"MFMAs per product" + (": 22 mantissa bits, fp32-class results)"
-                                                                          if prec == "f16x3" else ")"),
-            "data": "synthetic",
-            "renderer_uniforms": "drawn inside the timed call (torch.rand on the device per synthesis, as EG3D's ImportanceRenderer does)",
-            "config": {"workload": f"{cfg.name}: synthesis(ws[B,14,512], c[B,25]) forward, 512x512 out, 128^2 rays x "
-                                   f"(48+48) samples, random-init weights, random latents+cameras",
-                       "frames_per_step_per_gpu": B, "parallelism": f"frame-parallel x{n_ranks}"},
-            "per_rank_frames_per_s": per_rank,
-            # (max - min) / median over the ranks: frame-parallel rendering has no collective in the timed region, so a spread
-            # beyond a few per cent means one GPU (clock, thermal state, a noisy neighbour on its NUMA node) holds the job back
-            "per_rank_spread": ((max(per_rank) - min(per_rank)) / sorted(per_rank)[len(per_rank) // 2]) if per_rank else 0.0,
+        out = headline()
+        out.update({
             # dominant kernel by time: the modulated-conv implicit GEMM
             "roofline": roof,
             # the kernel north_star names: see the comment above
@@ -1132,8 +1194,7 @@ def main():
                                   "hbm_counter_frac_of_peak": (rm_traffic / (rm_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
                                                                if rm_traffic else None),
                                   "traffic_over_compulsory": rm_traffic / compulsory if rm_traffic else None},
-        }
-        out["config"]["conv_precision"] = prec
+        })
         if overflow is not None:
             # fp16 range tracking: largest |activation| any unclamped layer produced in the last frame batch; the fp16-part
             # GEMMs normalise by it (exact power of two), no layer fell back to another precision
@@ -1170,8 +1231,6 @@ def main():
         if dt32 is not None:
             out["value_fp32_exact"] = frames / dt32
             out["roofline_fp32_exact"] = f32_roofline(timing32)
-        out["step_ms"] = _pct(timing["step"])       # per-step HIP event pairs of the timed region (this rank)
-        out["step_ms"]["argmax"] = max(range(len(timing["step"])), key=lambda i: timing["step"][i])      # (which step a stall hit)
         if sweep is not None:
             out["batch_sweep"] = sweep
         if train is not None:
@@ -1317,9 +1376,14 @@ def main():
                     return gen.synthesis(ws_.to(dev), c_.to(dev), noise_mode="const", u_strat=us_.to(dev), u_imp=ui_.to(dev))["image"].cpu()
             out["cpu_baseline"] = cpu_baseline(cfg, state, args.cpu_runs, args.cpu_warmup, args.cpu_n1, check=hip_image)
             leg_s["cpu_baseline"] = round(time.perf_counter() - t_cpu, 2)
+    if rank == 0:
+        if not args.full:
+            out = headline()
         out["leg_seconds"] = leg_s
-        write_detail(out, args.detail)
-        line = json.dumps(compact_line(out))
+        detail = args.full or args.detail is not None
+        if detail:
+            write_detail(out, args.detail)
+        line = json.dumps(compact_line(out, detail))
         assert len(line) <= LINE_BYTE_BUDGET, len(line)
         sys.stdout.flush()
         sys.stderr.flush()

@@ -6,7 +6,7 @@ R="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 tag="${1:-fwd}"; shift || true
 out="$R/gpurun_out/prof_$tag"; mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o bench -- python "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-train --no-fp32-leg "$@" > "$out/trace.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o bench -- python "$R/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-train --no-fp32-leg "$@" > "$out/trace.log" 2>&1
 python - "$out" <<'PY'
 import csv, glob, os, sys
 out = sys.argv[1]

@@ -93,3 +93,51 @@ def test_the_printed_line_stays_parseable_and_short():
     huge = dict(full, leg_seconds={f"leg{i}": 1.0 for i in range(600)})
     small = bench.compact_line(huge)
     assert len(json.dumps(small)) <= 6000 and "leg_seconds" not in small and "roofline" in small
+
+
+def test_plain_run_is_the_default_and_steps_are_checked(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline only: `--full` (every secondary leg) is off unless asked
+    for, `--dump-outputs` is off, and a step count that would time nothing is refused before any set-up."""
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "d"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        import pytest
+        with pytest.raises(SystemExit):
+            bench.parse()
+
+
+def test_dump_outputs_stay_within_64_mb_and_sample_the_same_elements(tmp_path):
+    """--dump-outputs at the headline's batch (32 frames: a 100 MB image): the small arrays go out whole, the image as a fixed,
+    seeded sample of its elements; all float32, at most 64 MB in all, and the same files for the same arrays in every run."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    outs = {"image": torch.randn(32, 3, 512, 512, generator=g), "image_raw": torch.randn(32, 3, 128, 128, generator=g),
+            "image_depth": torch.rand(32, 1, 128, 128, generator=g, dtype=torch.float64)}
+    info = bench.dump_outputs(outs, str(tmp_path / "a"))
+    bench.dump_outputs(outs, str(tmp_path / "b"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["image.npy", "image_depth.npy", "image_raw.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 * 10 ** 6
+    assert info["image"] == {"shape": [32, 3, 512, 512], "sampled": True} and not info["image_raw"]["sampled"]
+    for name, t in outs.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        flat = t.float().reshape(-1).numpy()
+        if info[name]["sampled"]:
+            # distinct elements at increasing flat positions: the first k of a seeded permutation, sorted
+            assert a.ndim == 1 and a.size > flat.size // 2
+            idx = torch.randperm(flat.size, generator=torch.Generator().manual_seed(0))[:a.size].sort().values.numpy()
+            assert np.array_equal(a, flat[idx])
+        else:
+            assert a.shape == tuple(t.shape) and np.array_equal(a.reshape(-1), flat)
+    # a small output (what `--batch 2` computes) goes out whole
+    small = {"image": outs["image"][:2].clone()}
+    assert not bench.dump_outputs(small, str(tmp_path / "c"))["image"]["sampled"]
+    assert np.array_equal(np.load(tmp_path / "c" / "image.npy"), small["image"].numpy())

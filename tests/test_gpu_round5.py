@@ -159,7 +159,7 @@ def test_bench_with_a_forced_one_rank_rccl_group_reports_its_algorithm_field(tmp
     env = dict(os.environ, HFAGP_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("NCCL_DEBUG", "NCCL_DEBUG_SUBSYS", "NCCL_DEBUG_FILE", "RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "2", "--no-cpu-baseline",
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "2", "--no-cpu-baseline",
                           "--no-sweep", "--audio-frames", "0", "--fit-frames", "0", "--fit3dmm-frames-per-rank", "0", "--no-lpips",
                           "--no-fp32-leg", "--no-f16-leg", "--train-steps", "2", "--detail", str(tmp_path / "detail.json")],
                          capture_output=True, text=True, timeout=900, env=env)

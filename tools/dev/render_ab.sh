@@ -6,6 +6,6 @@ for i in 1 2 3; do
   for old in 1 0; do
     if [ $old = 1 ]; then export HFAGP_DEV_UP_LEGACY_TILES=1 HFAGP_DEV_UP_WAVES=8; else unset HFAGP_DEV_UP_LEGACY_TILES HFAGP_DEV_UP_WAVES; fi
     echo -n "old_up_tiling=$old "
-    python bench.py $args 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('up_layers_ms_per_step'))"
+    python bench.py --full $args 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('up_layers_ms_per_step'))"
   done
 done
