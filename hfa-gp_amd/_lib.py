@@ -14,7 +14,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (HFAGP_LIB_PATH: developer override, used by the ablation builds of tools/dev/ — the product loads the in-tree library)
 LIB_PATH = os.environ.get("HFAGP_LIB_PATH") or os.path.join(_HERE, "libhfagp_hip.so")
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 c_float_p = C.c_void_p  # device pointers travel as integers
 
@@ -31,6 +31,14 @@ class RaymarchArgs(C.Structure):
         ("box_warp", C.c_float), ("decoder_lr_mul", C.c_float),
         ("planes_absmax", C.c_void_p), ("state", C.c_void_p),
     ]
+
+
+class PlanesQueryArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("planes", "coords", "dec_w0", "dec_b0", "dec_w1", "dec_b1", "planes_absmax",
+                                          "sigma", "rgb")] + \
+        [("M", C.c_int64), ("out_stride", C.c_int64)] + \
+        [(n, C.c_int32) for n in ("B", "H", "W", "Bc", "N", "x_begin", "x_count", "plane_axes")] + \
+        [("decoder_lr_mul", C.c_float), ("box_warp", C.c_double), ("cube_length", C.c_double)]
 
 
 class StyleArgs(C.Structure):
@@ -156,6 +164,7 @@ SYMBOLS = {
     "hfagp_abi_version": (C.c_int, []),
     "hfagp_last_error": (C.c_char_p, []),
     "hfagp_raymarch_fwd": (C.c_int, [C.POINTER(RaymarchArgs), C.c_void_p]),
+    "hfagp_planes_query": (C.c_int, [C.POINTER(PlanesQueryArgs), C.c_void_p]),
     "hfagp_depth_clamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hfagp_style_fwd": (C.c_int, [C.POINTER(StyleArgs), C.c_void_p]),
     "hfagp_fc_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_float, C.c_float, C.c_void_p]),

@@ -801,6 +801,94 @@ class TriPlaneGenerator(nn.Module):
             ws = mp.w_avg.lerp(ws, truncation_psi)
         return ws
 
+    # ------------------------------------------------------------------ point queries (EG3D TriPlaneGenerator.sample*)
+    def _query_guard(self, who: str, ws: torch.Tensor, *tensors) -> None:
+        if not ws.is_cuda:
+            raise RuntimeError(f"TriPlaneGenerator.{who}: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
+        if ws.device.index != torch.cuda.current_device():
+            raise RuntimeError(f"TriPlaneGenerator.{who}: tensors live on {ws.device} but the current device is "
+                               f"cuda:{torch.cuda.current_device()}; wrap the call in `with torch.cuda.device(ws.device):`")
+        if ws.dim() != 3 or ws.shape[1:] != (self.cfg.num_ws, self.cfg.w_dim):
+            raise ValueError(f"expected ws [B,{self.cfg.num_ws},{self.cfg.w_dim}], got {tuple(ws.shape)}")
+        self._no_backward(who, ws, *tensors)
+
+    def _no_backward(self, who: str, *tensors) -> None:
+        if torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors) or
+                                        any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError(f"TriPlaneGenerator.{who}: wrap in `torch.no_grad()`; the query has no backward "
+                               f"(an input or a generator parameter requires grad)")
+
+    def _query_planes(self, ws: torch.Tensor):
+        """One backbone pass → (planes [B,3,R,R,32], the |planes| bound `synthesis` hands the renderer)."""
+        planes = self.backbone_planes(ws.detach().float().contiguous())
+        return planes, getattr(self, "_planes_absmax", None)
+
+    def _query_kwargs(self) -> dict:
+        cfg = self.cfg
+        net = self.decoder.net
+        return dict(dec_w0=net["0"].weight, dec_b0=net["0"].bias, dec_w1=net["2"].weight, dec_b1=net["2"].bias,
+                    box_warp=cfg.box_warp, plane_axes=0 if cfg.plane_axes == "eg3d_original" else 1,
+                    decoder_lr_mul=cfg.decoder_lr_mul, decoder_precision=cfg.decoder_precision)
+
+    def sample_mixed(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], ws: torch.Tensor,
+                     truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:
+        """EG3D TriPlaneGenerator.sample_mixed: the raw decoder outputs at `coordinates` [B or 1, M, 3] (world units) of the
+        tri-planes of `ws` → {'rgb': [B,M,32], 'sigma': [B,M,1]} (sigma before the renderer's softplus).  `directions` is
+        shape-checked and ignored (OSGDecoder does not read it); the truncation arguments are EG3D's and unused here, as
+        there.  One backbone pass, one launch (ops.planes_query), the decoder precision the renderer runs.  Forward only."""
+        noise_mode = synthesis_kwargs.get("noise_mode", "const")
+        if noise_mode != "const":
+            raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
+        if coordinates.dim() != 3 or coordinates.shape[-1] != 3 or coordinates.shape[0] not in (1, ws.shape[0]):
+            raise ValueError(f"expected coordinates [B or 1, M, 3] for ws of batch {ws.shape[0]}, got {tuple(coordinates.shape)}")
+        if directions is not None and directions.shape != coordinates.shape:
+            raise ValueError(f"directions {tuple(directions.shape)} must match coordinates {tuple(coordinates.shape)}")
+        self._query_guard("sample_mixed", ws, coordinates)
+        b, m = ws.shape[0], coordinates.shape[1]
+        if b == 0 or m == 0:
+            return {"rgb": torch.zeros(b, m, 32, device=ws.device), "sigma": torch.zeros(b, m, 1, device=ws.device)}
+        with torch.no_grad():
+            planes, pam = self._query_planes(ws)
+            sigma, rgb = ops.planes_query(planes, coordinates.detach().float().contiguous(), planes_absmax=pam,
+                                          **self._query_kwargs())
+        return {"rgb": rgb, "sigma": sigma}
+
+    def sample(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], z: torch.Tensor, c: torch.Tensor,
+               truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:
+        """EG3D TriPlaneGenerator.sample: `mapping(z, c, truncation_psi)` then `sample_mixed`.  Only truncation_cutoff=None
+        (truncate every w row) is supported."""
+        if truncation_cutoff is not None:
+            raise NotImplementedError("TriPlaneGenerator.sample: only truncation_cutoff=None is supported")
+        self._no_backward("sample", z, coordinates)
+        ws = self.mapping(z, c, truncation_psi=truncation_psi)
+        return self.sample_mixed(coordinates, directions, ws, update_emas=update_emas, **synthesis_kwargs)
+
+    def density_grid(self, ws: torch.Tensor, resolution: int = 512, cube_length: Optional[float] = None,
+                     max_points: Optional[int] = None) -> torch.Tensor:
+        """Raw density on EG3D's shape-export lattice (gen_samples.py --shapes, create_samples): [B, N, N, N] indexed (ix, iy, iz),
+        iz fastest, N = `resolution` points per axis over a cube of side `cube_length` (default box_warp) centred at the
+        origin — before EG3D's flip / border trim (render.shape_volume_eg3d).  The lattice is the exact integer one
+        (DESIGN.md §4.4).  One backbone pass, then the grid-mode kernel in x slabs of at most `max_points` points (at
+        least one x plane per launch); no coordinate tensor is built.  Forward only."""
+        n = int(resolution)
+        if n < 2:
+            raise ValueError(f"density_grid: resolution must be >= 2, got {resolution}")
+        self._query_guard("density_grid", ws)
+        b = ws.shape[0]
+        vol = torch.empty(b, n, n, n, device=ws.device, dtype=torch.float32)
+        if b == 0:
+            return vol
+        cube = float(self.cfg.box_warp if cube_length is None else cube_length)
+        step = n if max_points is None else max(1, min(n, int(max_points) // (b * n * n)))
+        with torch.no_grad():
+            planes, pam = self._query_planes(ws)
+            kw = self._query_kwargs()
+            for x0 in range(0, n, step):
+                xc = min(step, n - x0)
+                ops.planes_query(planes, grid=(n, cube, x0, xc), planes_absmax=pam, want_rgb=False,
+                                 out=vol[:, x0:x0 + xc], **kw)
+        return vol
+
     def forward(self, *args, **kwargs):
         raise NotImplementedError("HFA-GP only calls generator.synthesis (headnerf.py:112); mapping is in mapping()")
 

@@ -175,6 +175,11 @@ class _LatentBasis(nn.Module):
         flip_label_(label)                               # in place, on the caller's tensor
         return self._synthesis(latent, label, renderer_uniforms)
 
+    def get_shape(self, latent: torch.Tensor, resolution: int = 512, **kw) -> torch.Tensor:
+        """Density volume [B, N, N, N] of a fitted latent (`generator.density_grid`): the geometry next to `get_image`.
+        `render.shape_volume_eg3d` / `render.save_mrc` turn it into EG3D's .mrc export.  Forward only."""
+        return self.generator.density_grid(latent, resolution=resolution, **kw)
+
     def _synthesis(self, latent, label, renderer_uniforms) -> torch.Tensor:
         """`generator.synthesis(latent, c=label, noise_mode='const')['image']` (headnerf.py:112).  `renderer_uniforms`
         (keyword-only `u_strat` [B,R,Sc], `u_imp` [B*R,Sf]) is a TEST HOOK: EG3D's renderer draws its stratified-jitter and

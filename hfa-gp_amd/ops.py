@@ -641,6 +641,74 @@ def raymarch(planes: torch.Tensor, cam2world: torch.Tensor, intrinsics: torch.Te
     return feat, depth, wsum, tmm
 
 
+def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *, grid=None, dec_w0: torch.Tensor,
+                 dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, box_warp: float, plane_axes,
+                 decoder_lr_mul: float, decoder_precision: str, planes_absmax: Optional[torch.Tensor] = None,
+                 want_rgb: bool = True, out: Optional[torch.Tensor] = None):
+    """The decoder at points (hfagp_planes_query): raw density and the 32 decoder features, as
+    ``oracle.osg_decoder(P, oracle.sample_from_planes(axes, planes, coords, box_warp), lr_mul)``.  Returns ``(sigma, rgb)``,
+    rgb None when ``want_rgb`` is False (the sigma-only kernel skips the colour rows of the decoder's last layer).
+
+    planes [B,3,H,W,32] channels-last.  Points, one of:
+      * ``coords`` [Bc,M,3] (Bc = 1 or B; 1 queries the same points for every identity) → sigma [B,M,1], rgb [B,M,32];
+      * ``grid=(N, cube_length, x_begin, x_count)`` (or just N: the whole lattice, cube_length = box_warp): EG3D's
+        create_samples lattice on the exact integer grid, generated in the kernel → sigma [B,x_count,N,N] indexed
+        (ix - x_begin, iy, iz), rgb [B,x_count,N,N,32].  ``out`` (grid, sigma only): a [B,x_count,N,N] tensor to write into,
+        contiguous inside each identity (a slab view of a whole [B,N,N,N] volume).
+    Decoder arithmetic as `raymarch`: 'f16x3' (bound on |planes| from ``planes_absmax`` or one reduction here) or 'fp32'."""
+    _chk(planes, "planes")
+    if planes.dim() != 5 or planes.shape[1] != 3 or planes.shape[4] != 32:
+        raise RuntimeError("planes_query: planes must be [B, 3, H, W, 32]")
+    b, _, h, w, _ = planes.shape
+    dev = planes.device
+    if isinstance(plane_axes, str):
+        plane_axes = 0 if plane_axes == "eg3d_original" else 1
+    a = L.PlanesQueryArgs()
+    if coords is not None:
+        if grid is not None:
+            raise ValueError("planes_query: pass coords or grid, not both")
+        _chk(coords, "coords")
+        if coords.dim() != 3 or coords.shape[2] != 3 or coords.shape[0] not in (1, b):
+            raise RuntimeError(f"planes_query: coords must be [1 or B={b}, M, 3], got {tuple(coords.shape)}")
+        if out is not None:
+            raise ValueError("planes_query: out= is for grid mode")
+        m = coords.shape[1]
+        sigma = torch.empty(b, m, 1, device=dev, dtype=torch.float32)
+        rgb = torch.empty(b, m, 32, device=dev, dtype=torch.float32) if want_rgb else None
+        if b == 0 or m == 0:
+            return sigma, rgb
+        a.coords, a.Bc, a.M = _ptr(coords), coords.shape[0], m
+    else:
+        if grid is None:
+            raise ValueError("planes_query: pass coords or grid")
+        n, cube, x0, xc = (grid, None, 0, None) if isinstance(grid, int) else tuple(grid)
+        cube = float(box_warp) if cube is None else float(cube)
+        xc = n - x0 if xc is None else xc
+        if out is not None:
+            if want_rgb:
+                raise ValueError("planes_query: out= takes the sigma of a sigma-only query (want_rgb=False)")
+            if out.shape != (b, xc, n, n) or out.dtype != torch.float32 or not out.is_cuda or \
+                    (b > 0 and out[0].numel() > 0 and not out[0].is_contiguous()):
+                raise RuntimeError(f"planes_query: out must be a float32 [B, {xc}, {n}, {n}] tensor contiguous per identity")
+            sigma = out
+        else:
+            sigma = torch.empty(b, xc, n, n, device=dev, dtype=torch.float32)
+        rgb = torch.empty(b, xc, n, n, 32, device=dev, dtype=torch.float32) if want_rgb else None
+        if b == 0 or xc == 0:
+            return sigma, rgb
+        a.N, a.x_begin, a.x_count, a.cube_length = n, x0, xc, cube
+        a.out_stride = sigma.stride(0)
+    a.planes = _ptr(planes)
+    a.dec_w0, a.dec_b0 = _ptr(_chk(dec_w0, "dec_w0")), _ptr(_chk(dec_b0, "dec_b0"))
+    a.dec_w1, a.dec_b1 = _ptr(_chk(dec_w1, "dec_w1")), _ptr(_chk(dec_b1, "dec_b1"))
+    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
+    a.sigma, a.rgb = _ptr(sigma), _ptr(rgb)
+    a.B, a.H, a.W, a.plane_axes = b, h, w, plane_axes
+    a.box_warp, a.decoder_lr_mul = box_warp, decoder_lr_mul
+    L.check(L.lib().hfagp_planes_query(C.byref(a), _stream()), "planes_query")
+    return sigma, rgb
+
+
 def depth_clamp_(depth: torch.Tensor, tminmax: torch.Tensor) -> torch.Tensor:
     """In place: depth.clamp_(tminmax[..., 0].min(), tminmax[..., 1].max()) — MipRayMarcher2's batch-global depth clamp — as ONE
     launch (hfagp_depth_clamp)."""

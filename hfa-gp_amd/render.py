@@ -7,6 +7,7 @@ from __future__ import annotations
 
 from typing import Iterable, Iterator, Optional, Tuple
 
+import numpy as np
 import torch
 
 
@@ -60,3 +61,48 @@ def render_frames(gen, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], per
     if pending is not None:
         pending[1].synchronize()
         yield pending[0]
+
+
+# ----------------------------------------------------------------------------- shape export (EG3D gen_samples.py --shapes)
+def shape_volume_eg3d(sigma_grid) -> np.ndarray:
+    """EG3D's post-processing of a density grid [N, N, N] (TriPlaneGenerator.density_grid of one identity, indexed (ix, iy, iz)):
+    flip along axis 0, then every voxel within pad = int(30 N / 256) of a face set to -1000.  Returns a float32 numpy array."""
+    v = sigma_grid.detach().float().cpu().numpy() if isinstance(sigma_grid, torch.Tensor) else np.asarray(sigma_grid, np.float32)
+    if v.ndim != 3 or len(set(v.shape)) != 1:
+        raise ValueError(f"shape_volume_eg3d: expected an [N, N, N] grid, got {v.shape}")
+    v = np.ascontiguousarray(np.flip(v, 0), dtype=np.float32)
+    pad = int(30 * v.shape[0] / 256)
+    if pad > 0:
+        v[:pad] = -1000; v[-pad:] = -1000
+        v[:, :pad] = -1000; v[:, -pad:] = -1000
+        v[:, :, :pad] = -1000; v[:, :, -pad:] = -1000
+    return v
+
+
+def save_mrc(path, volume, voxel_size: float = 1.0) -> None:
+    """Write a float32 volume [NZ, NY, NX] (C order: NX = last axis) as an MRC2014 map (MODE 2), the format EG3D's shape export
+    writes through the `mrcfile` package: 1024-byte header, then the data.  Cell = N * voxel_size per axis, angles 90."""
+    v = np.ascontiguousarray(np.asarray(volume, dtype=np.float32))
+    if v.ndim != 3:
+        raise ValueError(f"save_mrc: expected a 3-D volume, got {v.shape}")
+    nz, ny, nx = v.shape
+    words = np.zeros(256, dtype="<i4")
+    floats = words.view("<f4")
+    words[0:3] = (nx, ny, nz)                 # NX NY NZ
+    words[3] = 2                              # MODE 2: float32
+    words[7:10] = (nx, ny, nz)                # MX MY MZ
+    floats[10:13] = (nx * voxel_size, ny * voxel_size, nz * voxel_size)    # CELLA
+    floats[13:16] = 90.0                      # CELLB
+    words[16:19] = (1, 2, 3)                  # MAPC MAPR MAPS
+    vd = v.astype(np.float64)
+    floats[19], floats[20], floats[21] = (v.min(), v.max(), vd.mean()) if v.size else (0.0, 0.0, 0.0)    # DMIN DMAX DMEAN
+    words[22] = 1                             # ISPG
+    words[27] = 20140                         # NVERSION
+    header = bytearray(words.tobytes())
+    header[208:212] = b"MAP "                 # MAP (word 53)
+    header[212:216] = bytes((0x44, 0x44, 0, 0))   # MACHST: little-endian
+    floats_rms = np.float32(np.sqrt(((vd - vd.mean()) ** 2).mean())) if v.size else np.float32(0)
+    header[216:220] = np.array([floats_rms], dtype="<f4").tobytes()           # RMS (word 55)
+    with open(path, "wb") as f:
+        f.write(bytes(header))
+        f.write(v.astype("<f4", copy=False).tobytes())

@@ -24,6 +24,8 @@
  *   hfagp_fc_fwd            <- FullyConnectedLayer (MappingNetwork; EqualLinear twin: code/networks/encoder3d.py:112-139)
  *   hfagp_weight_prep[_split|_prec] <- (no reference counterpart: MFMA operand images of a conv weight, per weight version)
  *   hfagp_qr_gram_fwd / hfagp_qr_refine_fwd <- torch.qr(bases.T) of get_latent (code/networks/headnerf.py:91,187,246)
+ *   hfagp_planes_query      <- TriPlaneGenerator.sample / sample_mixed (sample_from_planes + OSGDecoder at given points) and the
+ *                              density volume of gen_samples.py --shapes (create_samples lattice), one launch (ABI 13)
  *   hfagp_depth_clamp       <- MipRayMarcher2's torch.clamp(depth, min sample depth, max sample depth) over the batch, one launch (ABI 10)
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
@@ -61,7 +63,7 @@
 extern "C" {
 #endif
 
-#define HFAGP_ABI_VERSION 12
+#define HFAGP_ABI_VERSION 13
 
 enum { HFAGP_OK = 0, HFAGP_EBADARG = -1, HFAGP_EUNSUPPORTED = -2, HFAGP_ELAUNCH = -3 };
 
@@ -109,6 +111,43 @@ typedef struct {
 } HfagpRaymarchArgs;
 
 int hfagp_raymarch_fwd(const HfagpRaymarchArgs* a, void* stream);
+
+/* ------------------------------------------------------------------ point queries (ABI 13)
+ * The decoder at arbitrary points, no compositing: per point the same tri-plane gather and OSGDecoder the ray marcher runs,
+ *   sigma = raw decoder output 0 (NO softplus: EG3D's sample() returns x[..., 0:1])
+ *   rgb   = sigmoid(x[..., 1:]) * 1.002 - 0.001 (32 channels)
+ * of the points q = fp32(2 / box_warp) * p.  Decoder arithmetic as hfagp_raymarch_fwd: split fp16 given planes_absmax, exact fp32
+ * without it, so a query reports the densities the renderer sees.  Two point sources:
+ *   explicit  coords != NULL: points [Bc][M][3]; Bc = 1 queries one point set for every identity; out [B][M] (rgb [B][M][32])
+ *   grid      coords == NULL: the lattice of EG3D's create_samples, generated in the kernel (nothing materialised): N points per
+ *             axis over a cube of side cube_length centred at the origin, coordinate k = fp32(i_k) * fp32(cube_length / (N-1))
+ *             + fp32(-cube_length / 2) (two fp32 roundings, as torch computes it).  Only x in [x_begin, x_begin + x_count) is
+ *             evaluated; out [B][x_count][N][N] indexed (ix - x_begin, iy, iz), iz fastest (rgb: x 32).
+ * Identity b's outputs start at sigma + b * out_stride (rgb + b * out_stride * 32); out_stride 0 = dense.  Offsets are 64-bit. */
+typedef struct {
+    const float* planes;      /* [B][3][H][W][32] fp32 (as HfagpRaymarchArgs::planes)                                     */
+    const float* coords;      /* [Bc][M][3] points in world units, or NULL: grid mode                                     */
+    const float* dec_w0;      /* decoder.net.0.weight [64][32]  (raw parameter)                                           */
+    const float* dec_b0;      /* decoder.net.0.bias   [64]                                                                */
+    const float* dec_w1;      /* decoder.net.2.weight [33][64]                                                            */
+    const float* dec_b1;      /* decoder.net.2.bias   [33]                                                                */
+    const float* planes_absmax; /* optional [HFAGP_ABSMAX_FLOATS] bound on |planes| (HfagpRaymarchArgs::planes_absmax):
+                               * given, the split-fp16 decoder; NULL, the exact fp32 decoder                              */
+    float*       sigma;       /* out: raw density, layout above                                                           */
+    float*       rgb;         /* optional out: the 32 decoder features; NULL = sigma only (layer 2's colour rows skipped) */
+    int64_t M;                /* explicit: points per identity                                                            */
+    int64_t out_stride;       /* elements between identities in sigma (0: M, grid x_count * N * N)                      */
+    int32_t B, H, W;          /* identities, plane height / width (> 1)                                                   */
+    int32_t Bc;               /* explicit: identities in coords, 1 (broadcast) or B                                       */
+    int32_t N;                /* grid: points per axis (>= 2)                                                             */
+    int32_t x_begin, x_count; /* grid: the slab of x evaluated by this launch, inside [0, N)                              */
+    int32_t plane_axes;       /* 0: (x,y),(x,z),(z,x) [eg3d original]; 1: third = (z,y)                                   */
+    float decoder_lr_mul;
+    double box_warp;          /* python float of rendering_kwargs (kept double: 2 / box_warp rounds once, to fp32)        */
+    double cube_length;       /* grid: side of the cube (EG3D: box_warp)                                                  */
+} HfagpPlanesQueryArgs;
+
+int hfagp_planes_query(const HfagpPlanesQueryArgs* a, void* stream);
 
 /* ------------------------------------------------------------------ styles
  * styles[b][i] = (w[b] . A[i]) / sqrt(w_dim) * 1 + bias[i]   (then * style_gain)

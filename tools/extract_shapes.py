@@ -1,0 +1,96 @@
+#!/usr/bin/env python
+"""Shape export in the spirit of EG3D's `gen_samples.py --shapes`: the density volume of a generated or fitted head as an
+MRC2014 map, one `seedNNNN.mrc` per seed (or `<ws file stem>_<b>.mrc` per identity of a saved ws).
+
+    python tools/extract_shapes.py --preset ffhq512_128 --weights ffhq512-128.safetensors --seeds 0-3 --outdir out/
+    python tools/extract_shapes.py --preset tiny14 --ws fitted_ws.npy --resolution 256 --outdir out/
+
+Seeds go through `mapping(z, c)` with z = RandomState(seed).randn(z_dim) and the frontal conditioning label EG3D uses
+(camera on the +z axis at radius 2.7 around the pivot (0, 0, 0.2), FFHQ intrinsics).  A `.npy` of ws [B, num_ws, w_dim]
+(e.g. `HeadNeRF_*.get_latent(...)` saved with numpy) skips the mapping.  The volume is `TriPlaneGenerator.density_grid`
+(one backbone pass, one launch per x slab) post-processed like EG3D (`render.shape_volume_eg3d`: flip along axis 0, borders
+set to -1000) and written with the lattice spacing box_warp / (resolution - 1) as voxel size.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def parse_seeds(text: str):
+    """'0,3,5-7' -> [0, 3, 5, 6, 7]"""
+    out = []
+    for part in text.split(","):
+        part = part.strip()
+        if not part:
+            continue
+        if "-" in part:
+            lo, hi = part.split("-", 1)
+            out.extend(range(int(lo), int(hi) + 1))
+        else:
+            out.append(int(part))
+    return out
+
+
+def build_parser() -> argparse.ArgumentParser:
+    from hfa_gp_amd.config import PRESETS
+    p = argparse.ArgumentParser(description="Export generator head shapes as .mrc density volumes (EG3D gen_samples --shapes).")
+    p.add_argument("--preset", default="ffhq512_128", choices=sorted(PRESETS), help="generator topology")
+    p.add_argument("--weights", default=None, help="safetensors file with EG3D key names (default: seeded random init)")
+    p.add_argument("--generator-seed", type=int, default=0, help="init seed when no --weights are given")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("--seeds", type=parse_seeds, help="latent seeds, e.g. '0-3' or '1,5,9'")
+    src.add_argument("--ws", help=".npy file of ws [B, num_ws, w_dim]")
+    p.add_argument("--trunc", type=float, default=1.0, help="truncation psi of the mapping (seeds only)")
+    p.add_argument("--resolution", type=int, default=512, help="lattice points per axis")
+    p.add_argument("--max-points", type=int, default=None, help="points per kernel launch (x slabs); default: one launch")
+    p.add_argument("--outdir", required=True, help="output directory")
+    return p
+
+
+def frontal_label(device):
+    import torch
+    from hfa_gp_amd.cam_utils import create_cam2world_matrix, make_label
+    pivot = torch.tensor([0.0, 0.0, 0.2], device=device)
+    origin = pivot + torch.tensor([0.0, 0.0, 2.7], device=device)
+    return make_label(create_cam2world_matrix((pivot - origin)[None], origin[None], device=device))
+
+
+def main(argv=None) -> int:
+    args = build_parser().parse_args(argv)
+    import numpy as np
+    import torch
+    from hfa_gp_amd.config import PRESETS
+    from hfa_gp_amd.generator import load_G_official
+    from hfa_gp_amd.render import save_mrc, shape_volume_eg3d
+
+    dev = torch.device("cuda", torch.cuda.current_device())
+    cfg = PRESETS[args.preset]()
+    gen = load_G_official(cfg=cfg, seed=args.generator_seed, weights=args.weights, device=dev)
+    os.makedirs(args.outdir, exist_ok=True)
+    voxel = cfg.box_warp / (args.resolution - 1)
+    with torch.no_grad():
+        if args.seeds is not None:
+            jobs = []
+            for seed in args.seeds:
+                z = torch.from_numpy(np.random.RandomState(seed).randn(1, cfg.z_dim)).float().to(dev)
+                jobs.append((f"seed{seed:04d}", gen.mapping(z, frontal_label(dev), truncation_psi=args.trunc)))
+        else:
+            ws = torch.from_numpy(np.load(args.ws)).float().to(dev)
+            stem = os.path.splitext(os.path.basename(args.ws))[0]
+            jobs = [(f"{stem}_{b}", ws[b:b + 1]) for b in range(ws.shape[0])]
+        for name, ws in jobs:
+            grid = gen.density_grid(ws, resolution=args.resolution, max_points=args.max_points)[0]
+            path = os.path.join(args.outdir, name + ".mrc")
+            save_mrc(path, shape_volume_eg3d(grid), voxel_size=voxel)
+            print(path)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
