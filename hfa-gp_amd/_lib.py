@@ -14,7 +14,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (HFAGP_LIB_PATH: developer override, used by the ablation builds of tools/dev/ — the product loads the in-tree library)
 LIB_PATH = os.environ.get("HFAGP_LIB_PATH") or os.path.join(_HERE, "libhfagp_hip.so")
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 c_float_p = C.c_void_p  # device pointers travel as integers
 
@@ -39,6 +39,13 @@ class PlanesQueryArgs(C.Structure):
         [("M", C.c_int64), ("out_stride", C.c_int64)] + \
         [(n, C.c_int32) for n in ("B", "H", "W", "Bc", "N", "x_begin", "x_count", "plane_axes")] + \
         [("decoder_lr_mul", C.c_float), ("box_warp", C.c_double), ("cube_length", C.c_double)]
+
+
+class MarchingCubesArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("volume", "workspace", "counts", "verts", "faces")] + \
+        [(n, C.c_int64) for n in ("workspace_bytes", "vert_capacity", "face_capacity")] + \
+        [(n, C.c_int32) for n in ("n0", "n1", "n2")] + \
+        [("level", C.c_float), ("origin", C.c_float * 3), ("spacing", C.c_float * 3)]
 
 
 class StyleArgs(C.Structure):
@@ -165,6 +172,9 @@ SYMBOLS = {
     "hfagp_last_error": (C.c_char_p, []),
     "hfagp_raymarch_fwd": (C.c_int, [C.POINTER(RaymarchArgs), C.c_void_p]),
     "hfagp_planes_query": (C.c_int, [C.POINTER(PlanesQueryArgs), C.c_void_p]),
+    "hfagp_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "hfagp_marching_cubes_count": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),
+    "hfagp_marching_cubes_emit": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),
     "hfagp_depth_clamp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "hfagp_style_fwd": (C.c_int, [C.POINTER(StyleArgs), C.c_void_p]),
     "hfagp_fc_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_float, C.c_float, C.c_void_p]),

@@ -30,6 +30,7 @@ units=()
 for src in elementwise modconv modconv_bf16 smallconv upconv_fir upfir_lean torgb_skip raymarch backward raymarch_bwd raymarch_rows wgrad wgrad_bf16 qr loss collective; do units+=("$src"); done
 # units added since ABI 13 (tests/test_kernel_resources.py pins the list above; tests/test_shape_cpu.py holds these to its checks)
 units+=(planes_query)
+units+=(marching_cubes)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

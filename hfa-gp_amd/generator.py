@@ -879,15 +879,53 @@ class TriPlaneGenerator(nn.Module):
         if b == 0:
             return vol
         cube = float(self.cfg.box_warp if cube_length is None else cube_length)
-        step = n if max_points is None else max(1, min(n, int(max_points) // (b * n * n)))
         with torch.no_grad():
             planes, pam = self._query_planes(ws)
-            kw = self._query_kwargs()
-            for x0 in range(0, n, step):
-                xc = min(step, n - x0)
-                ops.planes_query(planes, grid=(n, cube, x0, xc), planes_absmax=pam, want_rgb=False,
-                                 out=vol[:, x0:x0 + xc], **kw)
+            self._fill_density(vol, planes, pam, cube, max_points)
         return vol
+
+    def _fill_density(self, vol: torch.Tensor, planes: torch.Tensor, pam, cube: float, max_points: Optional[int]) -> None:
+        b, n = vol.shape[0], vol.shape[1]
+        step = n if max_points is None else max(1, min(n, int(max_points) // (b * n * n)))
+        kw = self._query_kwargs()
+        for x0 in range(0, n, step):
+            xc = min(step, n - x0)
+            ops.planes_query(planes, grid=(n, cube, x0, xc), planes_absmax=pam, want_rgb=False,
+                             out=vol[:, x0:x0 + xc], **kw)
+
+    def extract_mesh(self, ws: torch.Tensor, resolution: int = 512, level: float = 10.0, cube_length: Optional[float] = None,
+                     max_points: Optional[int] = None, colors: bool = False):
+        """Surface meshes of the heads of `ws`: `density_grid`, EG3D's border trim (voxels within int(30 N / 256) of a face
+        set to -1000; no flip), then marching cubes at `level` (ops.marching_cubes) with the lattice spacing
+        cube_length / (N - 1) and origin -cube_length / 2, so vertices are in WORLD units (the frame `sample_mixed` takes).
+        Returns one dict per identity: {'vertices' [V, 3] float32, 'faces' [F, 3] int32}, plus 'colors' [V, 3] uint8 when
+        `colors`: the first three decoder features at the vertices (ops.planes_query, as `sample_mixed`), quantised as
+        render.to_uint8 quantises image_raw.  One backbone pass.  Forward only."""
+        from .render import _border_eg3d, to_uint8
+        n = int(resolution)
+        if n < 2:
+            raise ValueError(f"extract_mesh: resolution must be >= 2, got {resolution}")
+        self._query_guard("extract_mesh", ws)
+        b = ws.shape[0]
+        cube = float(self.cfg.box_warp if cube_length is None else cube_length)
+        voxel = cube / (n - 1)
+        out = []
+        if b == 0:
+            return out
+        with torch.no_grad():
+            planes, pam = self._query_planes(ws)
+            vol = torch.empty(b, n, n, n, device=ws.device, dtype=torch.float32)
+            self._fill_density(vol, planes, pam, cube, max_points)
+            for i in range(b):
+                verts, faces = ops.marching_cubes(_border_eg3d(vol[i]), level, spacing=(voxel,) * 3, origin=(-cube / 2,) * 3)
+                mesh = {"vertices": verts, "faces": faces}
+                if colors:
+                    rgb = torch.zeros(verts.shape[0], 32, device=ws.device)
+                    if verts.shape[0]:
+                        rgb = ops.planes_query(planes[i:i + 1], verts[None], planes_absmax=pam, **self._query_kwargs())[1][0]
+                    mesh["colors"] = to_uint8(rgb[:, :3])
+                out.append(mesh)
+        return out
 
     def forward(self, *args, **kwargs):
         raise NotImplementedError("HFA-GP only calls generator.synthesis (headnerf.py:112); mapping is in mapping()")

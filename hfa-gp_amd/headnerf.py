@@ -180,6 +180,11 @@ class _LatentBasis(nn.Module):
         `render.shape_volume_eg3d` / `render.save_mrc` turn it into EG3D's .mrc export.  Forward only."""
         return self.generator.density_grid(latent, resolution=resolution, **kw)
 
+    def get_mesh(self, latent: torch.Tensor, **kw):
+        """Surface meshes of a fitted latent (`generator.extract_mesh`: one {'vertices', 'faces'[, 'colors']} dict per
+        identity, world units), the counterpart of `get_shape`; `render.save_ply` writes them.  Forward only."""
+        return self.generator.extract_mesh(latent, **kw)
+
     def _synthesis(self, latent, label, renderer_uniforms) -> torch.Tensor:
         """`generator.synthesis(latent, c=label, noise_mode='const')['image']` (headnerf.py:112).  `renderer_uniforms`
         (keyword-only `u_strat` [B,R,Sc], `u_imp` [B*R,Sf]) is a TEST HOOK: EG3D's renderer draws its stratified-jitter and

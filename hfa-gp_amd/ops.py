@@ -709,6 +709,37 @@ def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *,
     return sigma, rgb
 
 
+def marching_cubes(volume: torch.Tensor, level: float, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
+    """Iso-surface ``volume > level`` of a float32 [n0, n1, n2] volume (hfagp_marching_cubes_count / _emit) → ``(verts [V, 3]
+    float32, faces [F, 3] int32)`` on the volume's device.  Vertices ``origin + spacing * p`` at the crossed lattice edges,
+    welded, in the order of include/hfagp.h (owning point, then axis); faces counter-clockwise seen from outside (normals
+    toward decreasing values).  Count, one synchronisation to read the two totals, allocate, emit.  Forward only."""
+    _chk(volume, "volume")
+    if volume.dim() != 3 or min(volume.shape) < 2:
+        raise RuntimeError(f"marching_cubes: volume must be [n0, n1, n2] with every extent >= 2, got {tuple(volume.shape)}")
+    if torch.is_grad_enabled() and volume.requires_grad:
+        raise RuntimeError("marching_cubes: wrap in `torch.no_grad()`; the extraction has no backward")
+    dev = volume.device
+    n0, n1, n2 = volume.shape
+    h = L.lib()
+    ws = torch.empty(h.hfagp_marching_cubes_workspace_bytes(n0, n1, n2) // 8, device=dev, dtype=torch.int64)
+    counts = torch.zeros(2, device=dev, dtype=torch.int64)
+    a = L.MarchingCubesArgs()
+    a.volume, a.workspace, a.counts, a.workspace_bytes = _ptr(volume), _ptr(ws), _ptr(counts), ws.numel() * 8
+    a.n0, a.n1, a.n2, a.level = n0, n1, n2, float(level)
+    a.origin[:] = [float(x) for x in origin]
+    a.spacing[:] = [float(x) for x in spacing]
+    L.check(h.hfagp_marching_cubes_count(C.byref(a), _stream()), "marching_cubes")
+    nv, nf = (int(x) for x in counts.cpu())
+    verts = torch.empty(nv, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(nf, 3, device=dev, dtype=torch.int32)
+    if nv == 0 and nf == 0:
+        return verts, faces
+    a.verts, a.faces, a.vert_capacity, a.face_capacity = _ptr(verts), _ptr(faces), nv, nf
+    L.check(h.hfagp_marching_cubes_emit(C.byref(a), _stream()), "marching_cubes")
+    return verts, faces
+
+
 def depth_clamp_(depth: torch.Tensor, tminmax: torch.Tensor) -> torch.Tensor:
     """In place: depth.clamp_(tminmax[..., 0].min(), tminmax[..., 1].max()) — MipRayMarcher2's batch-global depth clamp — as ONE
     launch (hfagp_depth_clamp)."""

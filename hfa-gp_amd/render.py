@@ -79,6 +79,66 @@ def shape_volume_eg3d(sigma_grid) -> np.ndarray:
     return v
 
 
+def shape_mesh_eg3d(sigma_grid: torch.Tensor, level: float = 10.0):
+    """EG3D's .ply geometry (gen_samples.py --shapes: convert_sdf_samples_to_ply of the transposed volume, level 10) on the GPU:
+    the flip and -1000 border of `shape_volume_eg3d`, then transpose(2, 1, 0), then marching cubes with spacing 1 and origin 0
+    (EG3D's vertex units: lattice indices of the transposed volume).  `sigma_grid` [N, N, N] is one identity of
+    TriPlaneGenerator.density_grid, on the GPU.  Returns (verts [V, 3] float32, faces [F, 3] int32) on its device."""
+    from . import ops
+    if not isinstance(sigma_grid, torch.Tensor) or not sigma_grid.is_cuda:
+        raise RuntimeError("shape_mesh_eg3d: expected a CUDA/ROCm [N, N, N] tensor (the HIP path has no CPU fallback)")
+    if sigma_grid.dim() != 3 or len(set(sigma_grid.shape)) != 1:
+        raise ValueError(f"shape_mesh_eg3d: expected an [N, N, N] grid, got {tuple(sigma_grid.shape)}")
+    with torch.no_grad():
+        v = _border_eg3d(sigma_grid.detach().float().flip(0))
+        return ops.marching_cubes(v.permute(2, 1, 0).contiguous(), level)
+
+
+def _border_eg3d(v: torch.Tensor) -> torch.Tensor:
+    """EG3D's border trim of a shape volume (a fresh tensor): voxels within int(30 N / 256) of a face set to -1000"""
+    v = v.clone()
+    pad = int(30 * v.shape[0] / 256)
+    if pad > 0:
+        v[:pad] = -1000; v[-pad:] = -1000
+        v[:, :pad] = -1000; v[:, -pad:] = -1000
+        v[:, :, :pad] = -1000; v[:, :, -pad:] = -1000
+    return v
+
+
+def save_ply(path, verts, faces, colors=None) -> None:
+    """Write a triangle mesh as binary little-endian PLY in the layout plyfile writes for EG3D's shape export: `element vertex`
+    with float x / y / z (and uchar red / green / blue when `colors` [V, 3] uint8 is given), `element face` with
+    `property list uchar int vertex_indices`.  verts [V, 3], faces [F, 3]: numpy arrays or tensors."""
+    def host(a):
+        return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    v, f = host(verts), host(faces)
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"save_ply: expected verts [V, 3] and faces [F, 3], got {v.shape} and {f.shape}")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    props = ["property float x", "property float y", "property float z"]
+    if colors is not None:
+        c = host(colors)
+        if c.shape != v.shape or c.dtype != np.uint8:
+            raise ValueError(f"save_ply: colors must be uint8 [V, 3], got {c.dtype} {c.shape}")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    vert = np.empty(v.shape[0], dtype=fields)
+    for i, name in enumerate("xyz"):
+        vert[name] = v[:, i]
+    if colors is not None:
+        for i, name in enumerate(("red", "green", "blue")):
+            vert[name] = c[:, i]
+    face = np.empty(f.shape[0], dtype=[("n", "u1"), ("idx", "<i4", (3,))])
+    face["n"] = 3
+    face["idx"] = f
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {v.shape[0]}", *props,
+              f"element face {f.shape[0]}", "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as out:
+        out.write(("\n".join(header) + "\n").encode("ascii"))
+        out.write(vert.tobytes())
+        out.write(face.tobytes())
+
+
 def save_mrc(path, volume, voxel_size: float = 1.0) -> None:
     """Write a float32 volume [NZ, NY, NX] (C order: NX = last axis) as an MRC2014 map (MODE 2), the format EG3D's shape export
     writes through the `mrcfile` package: 1024-byte header, then the data.  Cell = N * voxel_size per axis, angles 90."""

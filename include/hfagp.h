@@ -26,6 +26,8 @@
  *   hfagp_qr_gram_fwd / hfagp_qr_refine_fwd <- torch.qr(bases.T) of get_latent (code/networks/headnerf.py:91,187,246)
  *   hfagp_planes_query      <- TriPlaneGenerator.sample / sample_mixed (sample_from_planes + OSGDecoder at given points) and the
  *                              density volume of gen_samples.py --shapes (create_samples lattice), one launch (ABI 13)
+ *   hfagp_marching_cubes_count / _emit (+ _workspace_bytes) <- the .ply mesh of gen_samples.py --shapes
+ *                              (skimage.measure.marching_cubes + plyfile in EG3D's shape_utils), on the GPU (ABI 14)
  *   hfagp_depth_clamp       <- MipRayMarcher2's torch.clamp(depth, min sample depth, max sample depth) over the batch, one launch (ABI 10)
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
@@ -63,7 +65,7 @@
 extern "C" {
 #endif
 
-#define HFAGP_ABI_VERSION 13
+#define HFAGP_ABI_VERSION 14
 
 enum { HFAGP_OK = 0, HFAGP_EBADARG = -1, HFAGP_EUNSUPPORTED = -2, HFAGP_ELAUNCH = -3 };
 
@@ -148,6 +150,43 @@ typedef struct {
 } HfagpPlanesQueryArgs;
 
 int hfagp_planes_query(const HfagpPlanesQueryArgs* a, void* stream);
+
+/* ------------------------------------------------------------------ marching cubes (ABI 14)
+ * The iso-surface of a fp32 volume V[n0][n1][n2] (last axis fastest, each extent >= 2) as a welded triangle mesh.
+ *   inside:   a lattice point is inside iff V > level (strict; NaN is outside).
+ *   vertices: one per crossed edge (two lattice points one step apart along one axis, exactly one inside), at
+ *             p0 + t (p1 - p0), t = (level - v0) / (v1 - v0), p0 the lower-index end, output origin + spacing * p (fp32).
+ *             ORDER: ascending by the owning (lower-index) point's linear index (i n1 + j) n2 + k, then axis 0, 1, 2.
+ *   faces:    int32 vertex index triples from a 256-case table over the 8 corners of each cube (corner c at offset
+ *             (c >> 2 & 1, c >> 1 & 1, c & 1)); ORDER: ascending by cube (i, j, k), k fastest, then the table's order.
+ *             WINDING: counter-clockwise seen from outside, the geometric normal points toward decreasing values.
+ *             Ambiguous cube faces are cut the same way from both sides (inside corners never connect across a face
+ *             diagonal): the mesh of a volume whose boundary layer is all outside is closed and edge-manifold.
+ * The output is bit-identical from run to run and independent of the launch: positions come from prefix sums, no atomics.
+ * Two phases, so that the caller can allocate in between:
+ *   hfagp_marching_cubes_count  fills the workspace (per lattice row offsets) and counts[0] = vertices, counts[1] = faces;
+ *   hfagp_marching_cubes_emit   writes verts / faces.  It reads counts back and SYNCHRONISES the stream (the one entry point
+ *                               that does): capacities below the counts return HFAGP_EBADARG, counts >= 2^31 return
+ *                               HFAGP_EUNSUPPORTED, and nothing is written; an empty mesh launches nothing.
+ * Both take the same arguments; the workspace must survive from count to emit.  Offsets are 64-bit. */
+typedef struct {
+    const float* volume;      /* [n0][n1][n2] fp32                                                                     */
+    void*        workspace;   /* >= hfagp_marching_cubes_workspace_bytes(n0, n1, n2) bytes, 8-byte aligned            */
+    int64_t*     counts;      /* [2]: vertices, faces (written by _count)                                              */
+    float*       verts;       /* out [vert_capacity][3] (emit)                                                         */
+    int32_t*     faces;       /* out [face_capacity][3] (emit)                                                         */
+    int64_t workspace_bytes;
+    int64_t vert_capacity;
+    int64_t face_capacity;
+    int32_t n0, n1, n2;       /* extents, each >= 2                                                                    */
+    float level;              /* iso level                                                                             */
+    float origin[3];          /* position of lattice point (0, 0, 0)                                                   */
+    float spacing[3];         /* lattice step per axis                                                                 */
+} HfagpMarchingCubesArgs;
+
+size_t hfagp_marching_cubes_workspace_bytes(int32_t n0, int32_t n1, int32_t n2);
+int hfagp_marching_cubes_count(const HfagpMarchingCubesArgs* a, void* stream);
+int hfagp_marching_cubes_emit(const HfagpMarchingCubesArgs* a, void* stream);
 
 /* ------------------------------------------------------------------ styles
  * styles[b][i] = (w[b] . A[i]) / sqrt(w_dim) * 1 + bias[i]   (then * style_gain)

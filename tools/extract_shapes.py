@@ -10,6 +10,11 @@ Seeds go through `mapping(z, c)` with z = RandomState(seed).randn(z_dim) and the
 (e.g. `HeadNeRF_*.get_latent(...)` saved with numpy) skips the mapping.  The volume is `TriPlaneGenerator.density_grid`
 (one backbone pass, one launch per x slab) post-processed like EG3D (`render.shape_volume_eg3d`: flip along axis 0, borders
 set to -1000) and written with the lattice spacing box_warp / (resolution - 1) as voxel size.
+
+`--format ply` (or `both`) writes the surface as `<name>.ply` instead (or as well), in EG3D's vertex units: marching cubes
+at `--level` (EG3D: 10) on the GPU over the same volume transposed (`render.shape_mesh_eg3d`), as `gen_samples.py --shapes
+--shape-format .ply` writes it.  `--colors` adds per-vertex RGB: the first three decoder features at each vertex, mapped back
+to world units.
 """
 from __future__ import annotations
 
@@ -39,7 +44,7 @@ def parse_seeds(text: str):
 
 def build_parser() -> argparse.ArgumentParser:
     from hfa_gp_amd.config import PRESETS
-    p = argparse.ArgumentParser(description="Export generator head shapes as .mrc density volumes (EG3D gen_samples --shapes).")
+    p = argparse.ArgumentParser(description="Export generator head shapes as .mrc density volumes and / or .ply meshes (EG3D gen_samples --shapes).")
     p.add_argument("--preset", default="ffhq512_128", choices=sorted(PRESETS), help="generator topology")
     p.add_argument("--weights", default=None, help="safetensors file with EG3D key names (default: seeded random init)")
     p.add_argument("--generator-seed", type=int, default=0, help="init seed when no --weights are given")
@@ -49,6 +54,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--trunc", type=float, default=1.0, help="truncation psi of the mapping (seeds only)")
     p.add_argument("--resolution", type=int, default=512, help="lattice points per axis")
     p.add_argument("--max-points", type=int, default=None, help="points per kernel launch (x slabs); default: one launch")
+    p.add_argument("--format", default="mrc", choices=("mrc", "ply", "both"), help="density volume, surface mesh, or both")
+    p.add_argument("--level", type=float, default=10.0, help="iso level of the .ply surface (EG3D: 10)")
+    p.add_argument("--colors", action="store_true", help="per-vertex colours in the .ply")
     p.add_argument("--outdir", required=True, help="output directory")
     return p
 
@@ -61,13 +69,22 @@ def frontal_label(device):
     return make_label(create_cam2world_matrix((pivot - origin)[None], origin[None], device=device))
 
 
+def eg3d_to_world(verts, n: int, cube: float):
+    """EG3D .ply vertex (a, b, c) (indices of the flipped, transposed lattice) -> world point
+    ((N-1-c) voxel - cube/2, b voxel - cube/2, a voxel - cube/2)"""
+    import torch
+    voxel = cube / (n - 1)
+    a, b, c = verts.unbind(-1)
+    return torch.stack([(n - 1 - c) * voxel, b * voxel, a * voxel], -1) - cube / 2
+
+
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     import numpy as np
     import torch
     from hfa_gp_amd.config import PRESETS
     from hfa_gp_amd.generator import load_G_official
-    from hfa_gp_amd.render import save_mrc, shape_volume_eg3d
+    from hfa_gp_amd.render import save_mrc, save_ply, shape_mesh_eg3d, shape_volume_eg3d, to_uint8
 
     dev = torch.device("cuda", torch.cuda.current_device())
     cfg = PRESETS[args.preset]()
@@ -86,9 +103,19 @@ def main(argv=None) -> int:
             jobs = [(f"{stem}_{b}", ws[b:b + 1]) for b in range(ws.shape[0])]
         for name, ws in jobs:
             grid = gen.density_grid(ws, resolution=args.resolution, max_points=args.max_points)[0]
-            path = os.path.join(args.outdir, name + ".mrc")
-            save_mrc(path, shape_volume_eg3d(grid), voxel_size=voxel)
-            print(path)
+            if args.format in ("mrc", "both"):
+                path = os.path.join(args.outdir, name + ".mrc")
+                save_mrc(path, shape_volume_eg3d(grid), voxel_size=voxel)
+                print(path)
+            if args.format in ("ply", "both"):
+                verts, faces = shape_mesh_eg3d(grid, level=args.level)
+                colors = None
+                if args.colors:
+                    world = eg3d_to_world(verts, args.resolution, cfg.box_warp)
+                    colors = to_uint8(gen.sample_mixed(world[None], None, ws)["rgb"][0, :, :3])
+                path = os.path.join(args.outdir, name + ".ply")
+                save_ply(path, verts, faces, colors)
+                print(path)
     return 0
 
 
