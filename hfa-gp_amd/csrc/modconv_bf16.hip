@@ -17,6 +17,7 @@
 //   fragment order: a lane's 8 K values are one 16-B load, straight from L2 into the fragment registers through a
 //   ring that stays 3 (F16: 6) taps ahead of the MFMAs.  The patch of the next chunk is converted under the last
 //   taps of the current one into the other LDS buffer: one barrier per chunk.
+#include <atomic>
 #include <type_traits>
 #include "conv16_common.h"
 
@@ -762,6 +763,264 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && KD != 3) ? HFAGP_UP4_OCC 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The forward 3x3 conv at F16X3 (KD = 4) on v_mfma_f32_16x16x32_f16 with 32-channel K chunks (modconv_bf16_kernel<4, 2, 9, 0, 1>;
+// make_plan / launch_group pick it for mode CONV3X3 at F16X3 with fp32 storage, Cin % 32 == 0 and Cout % 128 == 0).
+//   * Same block tile (8 x 16 positions x 128 channels, 4 waves of 64 positions x 64 channels), same split operands (the A parts
+//     are bit for bit those of the 16-channel loop), same weight image: lane group g = lane >> 4 of a 16x16x32 B fragment reads
+//     Cin octet 4 chunk + g of 16 consecutive Cout (256-B runs of [part][tap][Cin/8][Cout][8]).
+//   * B fragments by buffer loads: SGPR resource, one per-lane offset for the whole kernel, tap / chunk / part in the scalar
+//     offset and the N tile in the instruction's immediate: no 64-bit address arithmetic on the vector ALU.
+//   * Patch image per part [channel octet][position][16 B] (octet stride 3072 B = 0 mod 256 B): the 16 lanes of each
+//     ds_read_b128 group read 16 consecutive 16-B slots, the 16 lanes of each ds_write_b64 group 128 contiguous bytes.  Zero
+//     padding comes from out-of-range buffer loads of the activations (no mask multiply), the range-guard scale 2^-e is
+//     folded into the styles once.
+//   * One barrier per 32 channels (432 MFMAs), B ring of two items, the A fragments of the next tap read per M tile as soon
+//     as the current tap's MFMAs of that tile are issued.
+namespace c9 {
+constexpr int CK = 32;                            // channels per K chunk
+constexpr int LP = PW + 2, NPOS = (8 + 2) * LP;   // patch row pitch / positions (10 x 18)
+constexpr int OCT = 3072;                         // bytes per channel octet of one part: NPOS x 16 B rounded up to 256 B
+constexpr int A_PART = 4 * OCT, A_BUF = 2 * A_PART;
+constexpr int A_PER_T = 6;                        // float4 slots per thread: 180 positions x 8 quads over 256 threads
+static_assert(NPOS * 16 <= OCT && OCT % 256 == 0 && NPOS * 8 <= A_PER_T * 256, "patch layout");
+constexpr size_t lds_bytes(int cin) { return (size_t)2 * A_BUF + (size_t)(cin + 8) * sizeof(float); }
+}  // namespace c9
+
+template <int KD, int TM, int NTAPS, int IO, int LOOP>
+__global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p, const int) {
+    static_assert(KD == 4 && TM == 2 && NTAPS == 9 && IO == 0 && LOOP == 1, "the 32-channel loop is the F16X3 forward 3x3 conv");
+    using namespace c9;
+    typedef float f32x4v __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    char* As = lds_raw;                                                // [2][2 parts][4 octets][OCT]
+    float* Ss = reinterpret_cast<float*>(lds_raw + 2 * A_BUF);         // [Cin] styles x 2^-e
+
+    unsigned id = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int tn_blk = __builtin_amdgcn_readfirstlane(id % p.tiles_n); id /= p.tiles_n;
+    const int tw = __builtin_amdgcn_readfirstlane(id % p.tiles_w);     id /= p.tiles_w;
+    const int th = __builtin_amdgcn_readfirstlane(id % p.tiles_h);     id /= p.tiles_h;
+    const int b = __builtin_amdgcn_readfirstlane(id % p.B);            id /= p.B;
+    const int ks = __builtin_amdgcn_readfirstlane(id);
+    const int m0 = th * 8, n0 = tw * PW, co0 = tn_blk * BNB;
+    if (m0 >= p.Ho || n0 >= p.Wo) return;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int g = lane >> 4, i16 = lane & 15;
+    const int nch = p.Cin / CK;
+    const int c_begin = __builtin_amdgcn_readfirstlane((int)(((long long)nch * ks) / p.ksplit));
+    const int c_end = __builtin_amdgcn_readfirstlane((int)(((long long)nch * (ks + 1)) / p.ksplit));
+
+    float sback = 1.f;
+    const float sdown = style_range_guard(p.styles ? p.styles + (size_t)b * p.Cin : nullptr, p.Cin, lane, &sback, p.x_absmax);
+    for (int i = tid; i < p.Cin; i += 256) Ss[i] = (p.styles ? p.styles[(size_t)b * p.Cin + i] : 1.f) * sdown;
+
+    // ---- A staging: slot e = tid + 256 k holds channels 4q .. 4q+3 (q = 2 ((e >> 4) & 3) + (e & 1)) of patch position
+    // 8 (e >> 6) + ((e >> 1) & 7); q does not depend on k.  Positions past the patch repeat the last one (same value, same address).
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.x + (long long)b * p.x_batch_stride), 0, (unsigned)(p.in_h * p.in_w * p.Cin) * 4u, 0x00020000);
+    constexpr unsigned OOB = 0x80000000u;                              // beyond any image: the load returns zeros
+    const int qa = 2 * ((tid >> 4) & 3) + (tid & 1);
+    unsigned aoff[A_PER_T];
+    int lds_a[A_PER_T];
+#pragma unroll
+    for (int k = 0; k < A_PER_T; ++k) {
+        const int pix = min(8 * ((tid >> 6) + 4 * k) + ((tid >> 1) & 7), NPOS - 1);
+        lds_a[k] = (qa >> 1) * OCT + pix * 16 + (qa & 1) * 8;
+        const int iy = m0 - 1 + pix / LP, ix = n0 - 1 + pix % LP;
+        const bool inside = iy >= 0 && iy < p.in_h && ix >= 0 && ix < p.in_w;
+        aoff[k] = inside ? (unsigned)((iy * p.in_w + ix) * p.Cin + 4 * qa) * 4u : OOB;
+    }
+    // (in two halves of three slots: 12 staging registers instead of 24)
+    float4 ra[A_PER_T / 2];
+    auto load_a = [&](int chunk, auto half_tag) __attribute__((always_inline)) {
+        constexpr int HF = decltype(half_tag)::value;
+#pragma unroll
+        for (int k = 0; k < A_PER_T / 2; ++k)
+            ra[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, aoff[HF * 3 + k], chunk * CK * 4, 0));
+    };
+    auto store_a = [&](int chunk, auto buf_tag, auto k_tag) __attribute__((always_inline)) {
+        constexpr int BUF = decltype(buf_tag)::value, k = decltype(k_tag)::value;
+        const float4 sv = *reinterpret_cast<const float4*>(Ss + chunk * CK + 4 * qa);
+        const float4 x = ra[k % 3];
+        uint2 parts[2];
+        split4<KD>(make_float4(x.x * sv.x, x.y * sv.y, x.z * sv.z, x.w * sv.w), parts);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) *reinterpret_cast<uint2*>(As + BUF * A_BUF + q * A_PART + lds_a[k]) = parts[q];
+    };
+
+    // ---- B fragments: [part][tap][Cin/8][Cout][8] by buffer loads; lane offset (g Cout + co) x 16, N tile tn at +256 tn
+    const int cq8 = p.Cin >> 3;
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<void*>(p.wt), 0, (unsigned)(2 * 9 * cq8 * p.Cout) * 16u, 0x00020000);
+    const unsigned boff = (unsigned)(g * p.Cout + co0 + wn * 64 + i16) * 16u;
+    const int part_bytes = 9 * cq8 * p.Cout * 16, tap_bytes = cq8 * p.Cout * 16, chunk_bytes = 4 * p.Cout * 16;
+    // A fragment of M tile tm (patch row 4 wm + tm + dy, column i16 + dx), lane group g = channel octet g
+    const int abase = g * OCT + (4 * wm * LP + i16) * 16;
+
+    f32x4v acc[4][4];
+#pragma unroll
+    for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+        for (int tn = 0; tn < 4; ++tn) acc[tm][tn] = f32x4v{0.f, 0.f, 0.f, 0.f};
+
+    constexpr int PA[3] = {kind_pa(KD, 0), kind_pa(KD, 1), kind_pa(KD, 2)};
+    constexpr int PB[3] = {kind_pb(KD, 0), kind_pb(KD, 1), kind_pb(KD, 2)};
+    u32x4 bq[2][4][2];                                                 // ring slot, N tile, part
+    u32x4 af[4][2];                                                    // M tile, part (of the tap being computed)
+    auto issue_b = [&](int c, int t, auto slot_tag) __attribute__((always_inline)) {
+        constexpr int SL = decltype(slot_tag)::value;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int so = q * part_bytes + t * tap_bytes + c * chunk_bytes;   // scalar
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn) bq[SL][tn][q] = __builtin_amdgcn_raw_buffer_load_b128(rw, boff + 256 * tn, so, 0);
+        }
+    };
+    auto read_a = [&](auto u_tag, auto t_tag, auto tm_tag) __attribute__((always_inline)) {
+        constexpr int UU = decltype(u_tag)::value, T = decltype(t_tag)::value, TMI = decltype(tm_tag)::value;
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+            af[TMI][q] = *reinterpret_cast<const u32x4*>(As + UU * A_BUF + q * A_PART + ((TMI + T / 3) * LP + T % 3) * 16 + abase);
+    };
+    auto mfma_tile = [&](auto t_tag, auto tm_tag, auto sl_tag) __attribute__((always_inline)) {
+        constexpr int TMI = decltype(tm_tag)::value, SL = decltype(sl_tag)::value;
+#pragma unroll
+        for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn)
+                acc[TMI][tn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[TMI][PA[pr]]),
+                                                                     __builtin_bit_cast(f16x8, bq[SL][tn][PB[pr]]), acc[TMI][tn], 0, 0, 0);
+    };
+    // item = tap T of chunk c: B of the next item into the other ring slot, then per M tile its 12 MFMAs followed by the
+    // reads of that tile's fragments for tap T+1; the patch of chunk c+1 is fetched in two halves (at taps 0 and 4) and
+    // converted one slot per tap into the other LDS buffer under taps 2, 3, 4 and 6, 7, 8
+    auto item = [&](int c, auto u_tag, auto t_tag) __attribute__((always_inline)) {
+        constexpr int UU = decltype(u_tag)::value, T = decltype(t_tag)::value;
+        constexpr int SL = (UU * 9 + T) & 1;
+        issue_b(c + (T + 1) / 9, (T + 1) % 9, std::integral_constant<int, SL ^ 1>{});
+        if constexpr (T == 0) load_a(min(c + 1, c_end - 1), std::integral_constant<int, 0>{});
+        __builtin_amdgcn_sched_barrier(0);
+        auto tile = [&](auto tm_tag) __attribute__((always_inline)) {
+            mfma_tile(t_tag, tm_tag, std::integral_constant<int, SL>{});
+            if constexpr (T + 1 < 9) read_a(u_tag, std::integral_constant<int, T + 1>{}, tm_tag);
+            if constexpr (decltype(tm_tag)::value == 3 && ((T >= 2 && T <= 4) || T >= 6))
+                store_a(min(c + 1, c_end - 1), std::integral_constant<int, 1 - UU>{}, std::integral_constant<int, (T <= 4 ? T - 2 : T - 3)>{});
+            if constexpr (decltype(tm_tag)::value == 3 && T == 4) load_a(min(c + 1, c_end - 1), std::integral_constant<int, 1>{});
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        tile(std::integral_constant<int, 0>{});
+        tile(std::integral_constant<int, 1>{});
+        tile(std::integral_constant<int, 2>{});
+        tile(std::integral_constant<int, 3>{});
+    };
+    auto chunk = [&](int c, auto u_tag) __attribute__((always_inline)) {
+        __syncthreads();                                               // publishes the patch of chunk c
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+        __builtin_amdgcn_sched_barrier(0);
+        item(c, u_tag, std::integral_constant<int, 0>{});
+        item(c, u_tag, std::integral_constant<int, 1>{});
+        item(c, u_tag, std::integral_constant<int, 2>{});
+        item(c, u_tag, std::integral_constant<int, 3>{});
+        item(c, u_tag, std::integral_constant<int, 4>{});
+        item(c, u_tag, std::integral_constant<int, 5>{});
+        item(c, u_tag, std::integral_constant<int, 6>{});
+        item(c, u_tag, std::integral_constant<int, 7>{});
+        item(c, u_tag, std::integral_constant<int, 8>{});
+    };
+    if (c_begin < c_end) {
+        __syncthreads();                                               // styles are in LDS
+        load_a(c_begin, std::integral_constant<int, 0>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+        load_a(c_begin, std::integral_constant<int, 1>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 5>{});
+        issue_b(c_begin, 0, std::integral_constant<int, 0>{});
+        // pairs of chunks (LDS buffer and ring slots by chunk parity: compile time), then the odd one (an exit in the middle of
+        // the pair spilled 62 registers)
+        int cg = c_begin;
+        for (; cg + 1 < c_end; cg += 2) {
+            chunk(cg, std::integral_constant<int, 0>{});
+            chunk(cg + 1, std::integral_constant<int, 1>{});
+        }
+        if (cg < c_end) chunk(cg, std::integral_constant<int, 0>{});
+    }
+
+    // ---- epilogue.  C/D layout of 16x16: column = lane & 15 (channel), row = 4 (lane >> 4) + r (position): the 4 registers of
+    // tile (tm, tn) are columns n0 + 4g + r of patch row 4 wm + tm, channel co0 + 64 wn + 16 tn + i16.
+    float* out = p.out + (size_t)ks * p.slab;
+    float vmax = 0.f;
+    const bool do_rgb = p.fused && p.rgb_part != nullptr;
+    float rgbp[16 * 3];                                                // [position 4 tm + r][rgb]
+#pragma unroll
+    for (int i = 0; i < 16 * 3; ++i) rgbp[i] = 0.f;
+#pragma unroll
+    for (int tn = 0; tn < 4; ++tn) {
+        const int co = co0 + wn * 64 + tn * 16 + i16;
+        float rw3[3] = {0.f, 0.f, 0.f};
+        if (do_rgb) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) rw3[r] = p.rgb_w[((size_t)b * 3 + r) * p.Cout + co];
+        }
+        float d = sback, bs = 0.f;
+        if (p.fused) {
+            if (p.dcoef) d = p.dcoef[(size_t)b * p.Cout + co] * sback;
+            if (p.bias) bs = p.bias[co];
+        }
+#pragma unroll
+        for (int tm = 0; tm < 4; ++tm) {
+            const int m = m0 + 4 * wm + tm;
+            if (m >= p.Ho) continue;
+            float* rowp = out + ((size_t)b * p.Ho + m) * p.Wo * p.Cout + co;
+            const float* nrow = (p.fused && p.noise) ? p.noise + (size_t)m * p.Wo : nullptr;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = n0 + 4 * g + r;
+                const float nz = nrow ? nrow[min(n, p.Wo - 1)] * p.noise_strength : 0.f;
+                if (n >= p.Wo) continue;
+                float v = acc[tm][tn][r];
+                if (p.fused) v = lrelu_gain_clamp(v * d + bs + nz, p.act, p.alpha, p.gain, p.clamp);
+                else v *= sback;
+                vmax = fmaxf(vmax, fabsf(v));
+                if (p.out) rowp[n * p.Cout] = v;      // (NULL: only the fused toRGB sums are wanted)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgbp[(tm * 4 + r) * 3 + c] = fmaf(v, rw3[c], rgbp[(tm * 4 + r) * 3 + c]);
+            }
+        }
+    }
+    if (p.fused && p.y_absmax) publish_absmax(p.y_absmax, vmax, blockIdx.x * 4 + wave);
+    if (do_rgb) {
+        // reduce-scatter over the 16 channel lanes (as in the 16-channel loop): afterwards lane i16 owns position i16 = 4 tm + r
+        int n = 16 * 3;
+#pragma unroll
+        for (int mk = 8; mk >= 1; mk >>= 1) {
+            n >>= 1;
+            const bool up = (i16 & mk) != 0;
+#pragma unroll
+            for (int i = 0; i < 16 * 3 / 2; ++i) {
+                if (i < n) {
+                    const float keep = up ? rgbp[i + n] : rgbp[i];
+                    const float give = up ? rgbp[i] : rgbp[i + n];
+                    rgbp[i] = keep + __shfl_xor(give, mk);
+                }
+            }
+        }
+        const int m = m0 + 4 * wm + (i16 >> 2), nn = n0 + 4 * g + (i16 & 3);
+        if (m < p.Ho && nn < p.Wo) {
+            const int part = tn_blk * 2 + wn;
+            float4* dst = reinterpret_cast<float4*>(p.rgb_part) + (((size_t)part * p.B + b) * p.Ho + m) * p.Wo + nn;
+            *dst = make_float4(rgbp[0], rgbp[1], rgbp[2], 0.f);
+        }
+    }
+}
+
 template <int NP, int TM>
 static size_t bf16_lds_bytes(int cin) {
     constexpr int PH = 2 * TM * 32 / PW;
@@ -788,37 +1047,47 @@ static void launch_s2_merged(const Plan& pl, int cin, hipStream_t s) {
 
 // LDS of the merged up-conv: the two patch buffers + styles and range-guard scales of up_ns samples; beyond the 64 KB default the
 // kernel's dynamic-LDS limit is raised once per instantiation
+// Raise a kernel's dynamic-LDS limit beyond the 64 KB default.  The attribute belongs to the device that is current when it is set,
+// so it is set once per (kernel, device): `raised` (one per kernel) keeps a bit per device ordinal.
+static int raise_dynamic_lds(const void* fn, int bytes, std::atomic<unsigned long long>& raised, const char* what) {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    HFAGP_REQUIRE(e == hipSuccess && dev >= 0 && dev < 64, HFAGP_ELAUNCH, "%s: hipGetDevice: %s", what, hipGetErrorString(e));
+    const unsigned long long bit = 1ull << dev;
+    if (raised.load(std::memory_order_acquire) & bit) return HFAGP_OK;
+    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    HFAGP_REQUIRE(e == hipSuccess, HFAGP_ELAUNCH, "%s: cannot raise dynamic LDS to %d bytes on device %d: %s", what, bytes, dev,
+                  hipGetErrorString(e));
+    raised.fetch_or(bit, std::memory_order_release);
+    return HFAGP_OK;
+}
+
 template <int KD, int NW, int IO>
-static void launch_up_one(const Plan& pl, int cin, hipStream_t s) {
+static int launch_up_one(const Plan& pl, int cin, hipStream_t s) {
     const size_t lds = bf16_lds_bytes<kind_parts_a(KD), 2>(0) + (size_t)(pl.p.up_ns * (cin + 2)) * sizeof(float);
-    static bool raised = false;
-    if (lds > 64 * 1024 && !raised) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&upconv_bf16_kernel<KD, NW, IO>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        raised = true;
+    static std::atomic<unsigned long long> raised{0};
+    if (lds > 64 * 1024) {
+        const int rc = raise_dynamic_lds(reinterpret_cast<const void*>(&upconv_bf16_kernel<KD, NW, IO>), 128 * 1024, raised,
+                                         "upconv_bf16_kernel");
+        if (rc != HFAGP_OK) return rc;
     }
     upconv_bf16_kernel<KD, NW, IO><<<pl.grid, NW * 64, lds, s>>>(pl.p);
+    return HFAGP_OK;
 }
 
 // fp16-storage variants (KD = 1 only): io = x_f16 | y_f16 << 1
-static void launch_up_io(const Plan& pl, int cin, int io, hipStream_t s) {
+static int launch_up_io(const Plan& pl, int cin, int io, hipStream_t s) {
     const bool w8 = pl.up_waves == 8;
-    if (io == 2) {
-        if (w8) launch_up_one<1, 8, 2>(pl, cin, s); else launch_up_one<1, 4, 2>(pl, cin, s);
-    } else {
-        if (w8) launch_up_one<1, 8, 3>(pl, cin, s); else launch_up_one<1, 4, 3>(pl, cin, s);
-    }
+    if (io == 2) return w8 ? launch_up_one<1, 8, 2>(pl, cin, s) : launch_up_one<1, 4, 2>(pl, cin, s);
+    return w8 ? launch_up_one<1, 8, 3>(pl, cin, s) : launch_up_one<1, 4, 3>(pl, cin, s);
 }
 
 template <int KD>
-static void launch_up(const Plan& pl, int cin, hipStream_t s) {
+static int launch_up(const Plan& pl, int cin, hipStream_t s) {
     if constexpr (KD != 3) {            // (three parts: the 8-wave variant would spill; make_plan never asks for it)
-        if (pl.up_waves == 8) {
-            launch_up_one<KD, 8, 0>(pl, cin, s);
-            return;
-        }
+        if (pl.up_waves == 8) return launch_up_one<KD, 8, 0>(pl, cin, s);
     }
-    launch_up_one<KD, 4, 0>(pl, cin, s);
+    return launch_up_one<KD, 4, 0>(pl, cin, s);
 }
 
 int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
@@ -843,7 +1112,8 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
             HFAGP_REQUIRE(q.up_ns <= 1 || (long long)q.up_ns * a->x_batch_stride * (a->x_f16 ? 2 : 4) < (1ll << 32), HFAGP_EUNSUPPORTED,
                           "modconv (merged up-conv): %d samples of %lld elements exceed the 32-bit patch offsets", q.up_ns,
                           (long long)a->x_batch_stride);
-            launch_up_io(pl, a->Cin, io, s);
+            const int rc = launch_up_io(pl, a->Cin, io, s);
+            if (rc != HFAGP_OK) return rc;
             return check_launch("modconv_fwd (fp16 storage, merged up-conv)");
         }
         const dim3 grid(pl.grid.x, 1, 1);
@@ -858,13 +1128,15 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
         HFAGP_REQUIRE(p.up_ns <= 1 || (long long)p.up_ns * a->x_batch_stride * (a->x_f16 ? 2 : 4) < (1ll << 32), HFAGP_EUNSUPPORTED,
                       "modconv (merged up-conv): %d samples of %lld elements exceed the 32-bit patch offsets", p.up_ns,
                       (long long)a->x_batch_stride);
+        int rc;
         switch (kd) {
-            case 1: launch_up<1>(pl, a->Cin, s); break;
-            case 2: launch_up<2>(pl, a->Cin, s); break;
-            case 3: launch_up<3>(pl, a->Cin, s); break;
-            case 5: launch_up<5>(pl, a->Cin, s); break;
-            default: launch_up<4>(pl, a->Cin, s); break;
+            case 1: rc = launch_up<1>(pl, a->Cin, s); break;
+            case 2: rc = launch_up<2>(pl, a->Cin, s); break;
+            case 3: rc = launch_up<3>(pl, a->Cin, s); break;
+            case 5: rc = launch_up<5>(pl, a->Cin, s); break;
+            default: rc = launch_up<4>(pl, a->Cin, s); break;
         }
+        if (rc != HFAGP_OK) return rc;
         return check_launch("modconv_fwd (16-bit MFMA, merged up-conv)");
     }
     if (pl.merged_s2) {
@@ -876,6 +1148,10 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
             default: launch_s2_merged<4>(pl, a->Cin, s); break;
         }
         return check_launch("modconv_fwd (16-bit MFMA, merged adjoint of the up-conv)");
+    }
+    if (conv9_mfma16_takes(a)) {        // the forward 3x3 conv at F16X3: the 32-channel 16x16x32 loop
+        modconv_bf16_kernel<4, 2, 9, 0, 1><<<pl.grid, 256, c9::lds_bytes(a->Cin), s>>>(p, 0);
+        return check_launch("modconv_fwd (16-bit MFMA, 32-channel loop)");
     }
     for (int p0 = 0; p0 < p.nphase;) {
         int n = 1;

@@ -245,4 +245,13 @@ static inline bool smallconv_takes(const HfagpModconvArgs* a) {
            !a->rgb_w && !a->rgb_part && a->y != nullptr;
 }
 
+// The forward 3x3 conv at F16X3 with fp32 storage runs the 32-channel 16x16x32 loop of modconv_bf16_kernel<4, 2, 9, 0, 1> (split-K
+// included); everything else stays on the 16-channel loop.  Developer switch HFAGP_DEV_CONV9_LEGACY=1: the 16-channel loop for
+// these layers too (read at every call, so one process can time both).
+static inline bool conv9_mfma16_takes(const HfagpModconvArgs* a) {
+    const char* dev = getenv("HFAGP_DEV_CONV9_LEGACY");
+    return !(dev && atoi(dev) == 1) && a->precision == HFAGP_PREC_F16X3 && a->mode == HFAGP_CONV3X3 && !a->x_f16 && !a->y_f16 &&
+           a->Cin % 32 == 0 && a->Cin <= 512 && a->Cout % 128 == 0;
+}
+
 }  // namespace hfagp

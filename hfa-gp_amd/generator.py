@@ -449,8 +449,10 @@ class TriPlaneGenerator(nn.Module):
         # which kernel bench.py times
         key = ("modconv" if wt.dtype == torch.float32 else
                "modconv_f16" if wt.dtype == torch.float16 and wt.shape[0] == 1 else "modconv_split")
-        if (layer.up != 2 and wt.dtype != torch.float32 and x.shape[1] * x.shape[2] <= 256 and x.shape[3] % 16 == 0
-                and x.shape[3] <= 512 and cout % 32 == 0 and not half and rgb is None):
+        npos = x.shape[1] * x.shape[2]
+        if (layer.up != 2 and wt.dtype != torch.float32 and npos <= 256 and x.shape[3] % 16 == 0
+                and x.shape[3] <= 512 and cout % 32 == 0 and not half and rgb is None
+                and not (npos >= 64 and batch * npos >= 1024)):     # (the batch term of the predicate: staged kernel from 1024 positions)
             # the library runs these on smallconv_kernel (csrc/smallconv.hip, modconv_plan.h `smallconv_takes` — same predicate:
             # fp16-storage, Cin > 512 and fused-toRGB layers stay on the staged kernel): not the roofline kernel
             key = "modconv_small"

@@ -1,0 +1,68 @@
+"""Developer A/B of the forward 3x3 conv at F16X3: the 32-channel 16x16x32 loop against the 16-channel loop
+(HFAGP_DEV_CONV9_LEGACY=1), alternating in ONE process on the same seeded random data, per flagship layer.
+usage: conv9_ab.py [B] [pairs] [iters]   -> one line per layer: median / min / max us of each arm and the ratio"""
+import math
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from hfa_gp_amd import ops  # noqa: E402
+
+SHAPES = [(512, 128, 128), (256, 256, 256), (256, 128, 128), (128, 256, 256), (64, 512, 512), (32, 512, 512), (16, 512, 512),
+          (8, 512, 512)]
+
+
+def main():
+    B = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+    pairs = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    iters = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+    dev = torch.device("cuda:0")
+    tot = {"new": 0.0, "legacy": 0.0}
+    for H, cin, cout in SHAPES:
+        g = torch.Generator(device=dev).manual_seed(H + cin)
+        x = torch.randn(B, H, H, cin, device=dev, generator=g)
+        w = torch.randn(cout, cin, 3, 3, device=dev, generator=g) / math.sqrt(9 * cin)
+        wt = ops.weight_prep_prec(w, "f16x3")
+        s = torch.randn(B, cin, device=dev, generator=g) + 1.0
+        dcoef = torch.rand(B, cout, device=dev, generator=g)
+        bias = torch.randn(cout, device=dev, generator=g)
+
+        def run():
+            return ops.modconv(x, wt, cout, ops.CONV3X3, styles=s, dcoef=dcoef, bias=bias, act="lrelu", gain=math.sqrt(2),
+                               clamp=256.0)
+        times = {"new": [], "legacy": []}
+        for _ in range(pairs):
+            for arm in ("legacy", "new"):
+                if arm == "legacy":
+                    os.environ["HFAGP_DEV_CONV9_LEGACY"] = "1"
+                else:
+                    os.environ.pop("HFAGP_DEV_CONV9_LEGACY", None)
+                for _ in range(2):
+                    run()
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(iters):
+                    run()
+                e1.record()
+                torch.cuda.synchronize()
+                times[arm].append(e0.elapsed_time(e1) / iters * 1e3)
+        os.environ.pop("HFAGP_DEV_CONV9_LEGACY", None)
+        med = {a: statistics.median(t) for a, t in times.items()}
+        for a in tot:
+            tot[a] += med[a]
+        flops = 2.0 * B * H * H * cin * cout * 9
+        print(f"B={B} {H}^2 {cin}->{cout}: legacy {med['legacy']:.1f} us [{min(times['legacy']):.1f}, {max(times['legacy']):.1f}]  "
+              f"new {med['new']:.1f} us [{min(times['new']):.1f}, {max(times['new']):.1f}]  new/legacy {med['new'] / med['legacy']:.3f}  "
+              f"({flops / med['new'] / 1e6:.0f} vs {flops / med['legacy'] / 1e6:.0f} TFLOP/s)", flush=True)
+        del x, w, wt
+        torch.cuda.empty_cache()
+    print(f"B={B} 9-tap family, sum of medians: legacy {tot['legacy']:.0f} us, new {tot['new']:.0f} us, "
+          f"new/legacy {tot['new'] / tot['legacy']:.3f}", flush=True)
+
+
+if __name__ == "__main__":
+    main()
