@@ -262,30 +262,35 @@ using namespace hfagp;
 
 extern "C" {
 
-static int ck_of(const HfagpModconvArgs* a) { return a && a->precision != HFAGP_PREC_F32 ? 16 : CK; }
+// What a call resolves to on the host, for the workspace query and the launch alike: argument check, launch plan, and which
+// kernel runs — where the small-image kernel takes the call, its own K slices replace the plan's split.
+static int resolve_modconv(const HfagpModconvArgs* a, Plan& pl) {
+    const int ck = a && a->precision != HFAGP_PREC_F32 ? 16 : CK;
+    int rc = validate(a, ck);
+    if (rc == HFAGP_OK) rc = make_plan(a, pl, ck);
+    if (rc != HFAGP_OK) return rc;
+    pl.small = smallconv_takes(a);
+    if (pl.small) {
+        pl.p.ksplit = smallconv_ksplit(a);
+        pl.ws_bytes = pl.p.ksplit > 1 ? (size_t)pl.p.ksplit * pl.p.slab * sizeof(float) : 0;
+    }
+    return HFAGP_OK;
+}
 
 size_t hfagp_modconv_workspace_bytes(const HfagpModconvArgs* a) {
-    if (validate(a, ck_of(a)) != HFAGP_OK) return 0;
-    if (smallconv_takes(a)) {
-        const int ks = smallconv_ksplit(a);
-        return ks > 1 ? (size_t)ks * a->B * a->H * a->W * a->Cout * sizeof(float) : 0;
-    }
     Plan pl;
-    if (make_plan(a, pl, ck_of(a)) != HFAGP_OK) return 0;
-    return pl.ws_bytes;
+    return resolve_modconv(a, pl) == HFAGP_OK ? pl.ws_bytes : 0;
 }
 
 int32_t hfagp_modconv_rgb_parts(const HfagpModconvArgs* a) { return a ? ((a->Cout + 127) / 128) * 2 : 0; }
 
 int hfagp_modconv_fwd(const HfagpModconvArgs* a, void* stream) {
-    int rc = validate(a, ck_of(a));
-    if (rc != HFAGP_OK) return rc;
     Plan pl;
-    rc = make_plan(a, pl, ck_of(a));
+    int rc = resolve_modconv(a, pl);
     if (rc != HFAGP_OK) return rc;
     ConvParams& p = pl.p;
     HFAGP_REQUIRE((a->rgb_w == nullptr) == (a->rgb_part == nullptr), HFAGP_EBADARG, "modconv: rgb_w and rgb_part go together");
-    if (smallconv_takes(a)) {
+    if (pl.small) {
         rc = launch_smallconv(a, pl, (hipStream_t)stream);
         if (rc != HFAGP_OK || p.ksplit == 1) return rc;
         const long long n4 = p.slab / 4;           // the slabs: summed (in order) and finished by the reducer, as below

@@ -1090,6 +1090,18 @@ static int launch_up(const Plan& pl, int cin, hipStream_t s) {
     return launch_up_one<KD, 4, 0>(pl, cin, s);
 }
 
+// f(std::integral_constant<int, KD>{}) for the operand kind kd (kind_of(precision), not 0) as a compile-time constant
+template <class F>
+static auto with_kind(int kd, F&& f) {
+    switch (kd) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        default: return f(std::integral_constant<int, 4>{});
+    }
+}
+
 int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
     HFAGP_REQUIRE(a->Cin % CKB == 0 && (a->Cout % BNB == 0 || (a->Cout % BNB >= 96 && !pl.merged_up)), HFAGP_EUNSUPPORTED,
                   "modconv (16-bit MFMA): Cin=%d must be a multiple of %d and Cout=%d of %d (or 96 mod 128, 512-B tail pad)",
@@ -1128,25 +1140,12 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
         HFAGP_REQUIRE(p.up_ns <= 1 || (long long)p.up_ns * a->x_batch_stride * (a->x_f16 ? 2 : 4) < (1ll << 32), HFAGP_EUNSUPPORTED,
                       "modconv (merged up-conv): %d samples of %lld elements exceed the 32-bit patch offsets", p.up_ns,
                       (long long)a->x_batch_stride);
-        int rc;
-        switch (kd) {
-            case 1: rc = launch_up<1>(pl, a->Cin, s); break;
-            case 2: rc = launch_up<2>(pl, a->Cin, s); break;
-            case 3: rc = launch_up<3>(pl, a->Cin, s); break;
-            case 5: rc = launch_up<5>(pl, a->Cin, s); break;
-            default: rc = launch_up<4>(pl, a->Cin, s); break;
-        }
+        const int rc = with_kind(kd, [&](auto k) { return launch_up<decltype(k)::value>(pl, a->Cin, s); });
         if (rc != HFAGP_OK) return rc;
         return check_launch("modconv_fwd (16-bit MFMA, merged up-conv)");
     }
     if (pl.merged_s2) {
-        switch (kd) {
-            case 1: launch_s2_merged<1>(pl, a->Cin, s); break;
-            case 2: launch_s2_merged<2>(pl, a->Cin, s); break;
-            case 3: launch_s2_merged<3>(pl, a->Cin, s); break;
-            case 5: launch_s2_merged<5>(pl, a->Cin, s); break;
-            default: launch_s2_merged<4>(pl, a->Cin, s); break;
-        }
+        with_kind(kd, [&](auto k) { launch_s2_merged<decltype(k)::value>(pl, a->Cin, s); });
         return check_launch("modconv_fwd (16-bit MFMA, merged adjoint of the up-conv)");
     }
     if (conv9_mfma16_takes(a)) {        // the forward 3x3 conv at F16X3: the 32-channel 16x16x32 loop
@@ -1158,13 +1157,7 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
         while (p0 + n < p.nphase && p.phase[p0 + n].ntaps == p.phase[p0].ntaps) ++n;
         const int nt = p.phase[p0].ntaps;
         HFAGP_REQUIRE(nt == 9 || nt == 4 || nt == 2 || nt == 1, HFAGP_EUNSUPPORTED, "modconv (16-bit MFMA): %d taps", nt);
-        switch (kd) {
-            case 1: launch_group<1>(pl, p0, n, nt, a->Cin, s); break;
-            case 2: launch_group<2>(pl, p0, n, nt, a->Cin, s); break;
-            case 3: launch_group<3>(pl, p0, n, nt, a->Cin, s); break;
-            case 5: launch_group<5>(pl, p0, n, nt, a->Cin, s); break;
-            default: launch_group<4>(pl, p0, n, nt, a->Cin, s); break;
-        }
+        with_kind(kd, [&](auto k) { launch_group<decltype(k)::value>(pl, p0, n, nt, a->Cin, s); });
         p0 += n;
     }
     return check_launch("modconv_fwd (16-bit MFMA)");

@@ -51,6 +51,7 @@ struct Plan {
     dim3 grid;
     bool merged_up;   // split-bf16 CONVT3X3_UP2: one block computes all four output phases (upconv_bf16_kernel)
     bool merged_s2;   // split-bf16 CONVS2_BWD: one block runs the four parity phases into one accumulator set (no slabs)
+    bool small;       // the small-image kernel takes the call (smallconv_takes): p.ksplit / ws_bytes are ITS K slices (resolve_modconv)
     int up_waves;     // merged_up: 4 (N = 64 per block) or 8 waves (N = 128 per block, two waves per SIMD)
     size_t ws_bytes;
 };
@@ -183,7 +184,6 @@ static inline int make_plan(const HfagpModconvArgs* a, Plan& pl, int ck) {
     // batch (profiles/r06_up_waves_ab.log); it stays for bf16x6 (three parts: the 4-wave kernel only fits one block per CU there,
     // where the wider block at least halves the staging) behind the developer switch below.
     pl.up_waves = 4;
-    (void)up_tiles;
     { static const char* dev = getenv("HFAGP_DEV_UP_WAVES"); if (dev && pl.merged_up) pl.up_waves = atoi(dev) == 8 && a->Cout % 128 == 0 ? 8 : 4; }
     const int grid_tiles_n = pl.merged_up ? a->Cout / (pl.up_waves == 8 ? 128 : 64) : p.tiles_n;
     const int grid_phases = (pl.merged_up || pl.merged_s2) ? 1 : p.nphase;

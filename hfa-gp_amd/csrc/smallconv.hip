@@ -224,8 +224,7 @@ int smallconv_ksplit(const HfagpModconvArgs* a) {
 }
 
 int launch_smallconv(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
-    ConvParams& p = pl.p;
-    p.ksplit = smallconv_ksplit(a);
+    ConvParams& p = pl.p;                   // (p.ksplit: smallconv_ksplit, set with the plan — resolve_modconv)
     p.fused = p.ksplit == 1;
     p.out = p.ksplit == 1 ? a->y : a->workspace;
     HFAGP_REQUIRE(p.out, HFAGP_EBADARG, "modconv (small-image kernel): %d K slices need a workspace of %zu bytes", p.ksplit,

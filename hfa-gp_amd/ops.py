@@ -51,6 +51,20 @@ def _chk(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
+def _chk_act(t: torch.Tensor, name: str) -> torch.Tensor:
+    """An activation: float32 (`_chk`), or float16 storage — a contiguous device tensor read / written as stored."""
+    if t.dtype != torch.float16:
+        return _chk(t, name)
+    if not (t.is_cuda and t.is_contiguous()):
+        raise RuntimeError(f"{name}: expected a contiguous CUDA/ROCm tensor")
+    return t
+
+
+def _clamp(clamp: Optional[float]) -> float:
+    """The library's clamp encoding: a negative value = no clamp."""
+    return -1.0 if clamp is None else float(clamp)
+
+
 # ----------------------------------------------------------------------------- weights
 def weight_prep(weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """weight [Cout, Cin, k, k] → (wt [k*k, Cin/4, Cout, 4], wsq [Cout, Cin])."""
@@ -158,16 +172,14 @@ def weight_prep_split(weight: torch.Tensor, nparts: int) -> torch.Tensor:
     return weight_prep_prec(weight, {1: "f16", 2: "bf16x3", 3: "bf16x6"}[nparts])
 
 
-def styles_demod(w: torch.Tensor, affine_w: torch.Tensor, affine_b: torch.Tensor,
-                 wsq: Optional[torch.Tensor], style_gain: float = 1.0, eps: float = 1e-8):
-    """w [B, w_dim] (may be a strided row view of ws) → styles [B, Cin], dcoef [B, Cout] | None."""
+def _style_args(a, who: str, w, affine_w, affine_b, wsq, style_gain: float, eps: float):
+    """Fill the L.StyleArgs ``a`` of one layer; returns the outputs it points at: (styles [B, Cin], dcoef [B, Cout] | None)."""
     if w.dtype != torch.float32 or not w.is_cuda or w.stride(-1) != 1:
-        raise RuntimeError("styles_demod: w must be a CUDA fp32 tensor with unit inner stride")
+        raise RuntimeError(f"{who}: w must be a CUDA fp32 tensor with unit inner stride")
     b, wd = w.shape
     cin = affine_w.shape[0]
     styles = torch.empty(b, cin, device=w.device, dtype=torch.float32)
     dcoef = None
-    a = L.StyleArgs()
     a.w, a.affine_w, a.affine_b = _ptr(w), _ptr(_chk(affine_w, "affine_w")), _ptr(_chk(affine_b, "affine_b"))
     a.styles = _ptr(styles)
     a.B, a.w_dim, a.w_stride, a.Cin = b, wd, w.stride(0), cin
@@ -175,33 +187,24 @@ def styles_demod(w: torch.Tensor, affine_w: torch.Tensor, affine_b: torch.Tensor
     if wsq is not None:
         dcoef = torch.empty(b, wsq.shape[0], device=w.device, dtype=torch.float32)
         a.wsq, a.dcoef, a.Cout = _ptr(_chk(wsq, "wsq")), _ptr(dcoef), wsq.shape[0]
-    L.check(L.lib().hfagp_style_fwd(C.byref(a), _stream()), "style_fwd")
     return styles, dcoef
+
+
+def styles_demod(w: torch.Tensor, affine_w: torch.Tensor, affine_b: torch.Tensor,
+                 wsq: Optional[torch.Tensor], style_gain: float = 1.0, eps: float = 1e-8):
+    """w [B, w_dim] (may be a strided row view of ws) → styles [B, Cin], dcoef [B, Cout] | None."""
+    a = L.StyleArgs()
+    out = _style_args(a, "styles_demod", w, affine_w, affine_b, wsq, style_gain, eps)
+    L.check(L.lib().hfagp_style_fwd(C.byref(a), _stream()), "style_fwd")
+    return out
 
 
 def styles_demod_batch(items):
     """``items``: sequence of (w [B, w_dim] row view, affine_w, affine_b, wsq | None, style_gain, eps), at most 32.
     One launch for all the styles, one for all the demodulation coefficients.  Returns [(styles, dcoef | None)]."""
-    n = len(items)
-    arr = (L.StyleArgs * n)()
-    out = []
-    for i, (w, affine_w, affine_b, wsq, style_gain, eps) in enumerate(items):
-        if w.dtype != torch.float32 or not w.is_cuda or w.stride(-1) != 1:
-            raise RuntimeError("styles_demod_batch: w must be a CUDA fp32 tensor with unit inner stride")
-        b, wd = w.shape
-        cin = affine_w.shape[0]
-        styles = torch.empty(b, cin, device=w.device, dtype=torch.float32)
-        dcoef = None
-        a = arr[i]
-        a.w, a.affine_w, a.affine_b = _ptr(w), _ptr(_chk(affine_w, "affine_w")), _ptr(_chk(affine_b, "affine_b"))
-        a.styles = _ptr(styles)
-        a.B, a.w_dim, a.w_stride, a.Cin = b, wd, w.stride(0), cin
-        a.style_gain, a.eps = style_gain, eps
-        if wsq is not None:
-            dcoef = torch.empty(b, wsq.shape[0], device=w.device, dtype=torch.float32)
-            a.wsq, a.dcoef, a.Cout = _ptr(_chk(wsq, "wsq")), _ptr(dcoef), wsq.shape[0]
-        out.append((styles, dcoef))
-    L.check(L.lib().hfagp_style_batch_fwd(arr, n, _stream()), "style_batch_fwd")
+    arr = (L.StyleArgs * len(items))()
+    out = [_style_args(a, "styles_demod_batch", *item) for a, item in zip(arr, items)]
+    L.check(L.lib().hfagp_style_batch_fwd(arr, len(items), _stream()), "style_batch_fwd")
     return out
 
 
@@ -289,11 +292,53 @@ def absmax_slots(n: int, device) -> torch.Tensor:
     return torch.zeros(n, L.ABSMAX_FLOATS, device=device, dtype=torch.float32)
 
 
+_IMAGE_PRECISION = {(torch.float16, 1): PREC_F16, (torch.float16, 2): PREC_F16X3,
+                    (torch.bfloat16, 2): PREC_BF16X3, (torch.bfloat16, 3): PREC_BF16X6}
+
+
+def _image_precision(wt: torch.Tensor, x_parts: int = 0, who: str = "modconv") -> int:
+    """PREC_* of a weight image: the fp32 image of `weight_prep`, or the 16-bit kind that dtype and part count of a
+    `weight_prep_prec` image say; ``x_parts=1`` turns the two-part float16 image into 'f16x2' (see `modconv`)."""
+    if wt.dtype == torch.float32:
+        return PREC_F32
+    prec = _IMAGE_PRECISION.get((wt.dtype, wt.shape[0])) if wt.dim() == 5 else None
+    if prec is None:
+        raise RuntimeError(f"{who}: 16-bit weight images must come from weight_prep_prec")
+    if x_parts == 1 and prec != PREC_F16:
+        if prec != PREC_F16X3:
+            raise RuntimeError(f"{who}: x_parts=1 ('f16x2') goes with the two-part float16 weight image")
+        prec = PREC_F16X2
+    return prec
+
+
+def _modconv_args(x: torch.Tensor, wt: torch.Tensor, cout: int, mode: int, styles=None, dcoef=None, noise=None,
+                  noise_strength: float = 0.0, bias=None, act: str = "linear", alpha: float = 0.2, gain: float = 1.0,
+                  clamp: Optional[float] = None, batch: Optional[int] = None, ksplit: int = 0, x_absmax=None, y_absmax=None,
+                  rgb_w=None, y_f16: bool = False, x_parts: int = 0, who: str = "modconv"):
+    """The L.ModconvArgs of one call, everything but the buffers the caller allocates (y, workspace, rgb_part), and (B, H, W).
+    Launches and the questions put to the library about them (`_plan_unsplit`, `_fir_scratch_bytes`) are all built here."""
+    if mode == CONVS2_BWD:                      # x = four parity images [2,2,B,H+1,W+1,Cin]
+        _, _, xb, h, w, cin = x.shape
+        h, w = h - 1, w - 1
+    else:
+        xb, h, w, cin = x.shape
+    b = batch if batch is not None else xb
+    a = L.ModconvArgs()
+    a.x, a.wt, a.precision = x.data_ptr(), wt.data_ptr(), _image_precision(wt, x_parts, who)
+    a.styles, a.dcoef, a.noise, a.bias = _ptr(styles), _ptr(dcoef), _ptr(noise), _ptr(bias)
+    a.x_batch_stride = 0 if (xb == 1 and b > 1) else x.shape[-3] * x.shape[-2] * cin      # 0: one input broadcast over the batch
+    a.B, a.H, a.W, a.Cin, a.Cout = b, h, w, cin, cout
+    a.mode, a.act, a.ksplit = mode, _ACT[act], ksplit
+    a.noise_strength, a.alpha, a.gain, a.clamp = noise_strength, alpha, gain, _clamp(clamp)
+    a.x_absmax, a.y_absmax, a.rgb_w = _ptr(x_absmax), _ptr(y_absmax), _ptr(rgb_w)
+    a.x_f16, a.y_f16 = int(x.dtype == torch.float16), int(y_f16)
+    return a, b, h, w
+
+
 def modconv(x: torch.Tensor, wt: torch.Tensor, cout: int, mode: int, styles: Optional[torch.Tensor] = None,
-            dcoef: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-            noise_strength: float = 0.0, bias: Optional[torch.Tensor] = None, act: str = "linear",
-            alpha: float = 0.2, gain: float = 1.0, clamp: Optional[float] = None, batch: Optional[int] = None,
-            ksplit: int = 0, x_absmax: Optional[torch.Tensor] = None,
+            dcoef: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None, noise_strength: float = 0.0,
+            bias: Optional[torch.Tensor] = None, act: str = "linear", alpha: float = 0.2, gain: float = 1.0,
+            clamp: Optional[float] = None, batch: Optional[int] = None, ksplit: int = 0, x_absmax: Optional[torch.Tensor] = None,
             y_absmax: Optional[torch.Tensor] = None, rgb_w: Optional[torch.Tensor] = None, y_f16: bool = False,
             store_y: bool = True, x_parts: int = 0):
     """x [B|1, H, W, Cin] channels-last.  mode CONV3X3 / CONV1X1: fused epilogue, returns [B,H,W,Cout];
@@ -310,48 +355,20 @@ def modconv(x: torch.Tensor, wt: torch.Tensor, cout: int, mode: int, styles: Opt
     weights, two MFMAs per product (TF32 class; include/hfagp.h HFAGP_PREC_F16X2).
     fp16 STORAGE (single-pass fp16 weights only, `f16_storage_supported`): a float16 ``x`` is read as stored and
     ``y_f16`` writes the result as float16 (EG3D's fp16 super-resolution blocks keep their activations in fp16)."""
-    x_f16 = x.dtype == torch.float16
-    if x_f16 or y_f16:
-        if not (wt.dtype == torch.float16 and wt.dim() == 5 and wt.shape[0] == 1):
-            raise RuntimeError("modconv: fp16 storage (float16 x / y_f16) goes with the single-pass fp16 weight image")
-        if not (x.is_cuda and x.is_contiguous()):
-            raise RuntimeError("x: expected a contiguous CUDA/ROCm tensor")
-    if not x_f16:
-        _chk(x, "x")
-    if mode == CONVS2_BWD:                      # x = four parity images [2,2,B,H+1,W+1,Cin]
-        _, _, xb, h, w, cin = x.shape
-        h, w = h - 1, w - 1
-    else:
-        xb, h, w, cin = x.shape
-    b = batch if batch is not None else xb
-    a = L.ModconvArgs()
-    if wt.dtype in (torch.bfloat16, torch.float16):
-        nparts = (2, 3) if wt.dtype == torch.bfloat16 else (1, 2)
-        if not (wt.is_cuda and wt.is_contiguous() and wt.dim() == 5 and wt.shape[0] in nparts):
-            raise RuntimeError("modconv: 16-bit weight images must come from weight_prep_prec")
-        a.x, a.wt = x.data_ptr(), wt.data_ptr()
-        if wt.dtype == torch.float16:
-            a.precision = PREC_F16 if wt.shape[0] == 1 else PREC_F16X3
-        else:
-            a.precision = PREC_BF16X3 if wt.shape[0] == 2 else PREC_BF16X6
-        if x_parts == 1 and a.precision != PREC_F16:
-            if a.precision != PREC_F16X3:
-                raise RuntimeError("modconv: x_parts=1 ('f16x2') goes with the two-part float16 weight image")
-            a.precision = PREC_F16X2
-    else:
-        a.x, a.wt = _ptr(x), _ptr(_chk(wt, "wt"))
-        a.precision = PREC_F32
-    a.styles, a.dcoef, a.noise, a.bias = _ptr(styles), _ptr(dcoef), _ptr(noise), _ptr(bias)
-    a.x_batch_stride = 0 if (xb == 1 and b > 1) else x.shape[-3] * x.shape[-2] * cin
-    a.B, a.H, a.W, a.Cin, a.Cout = b, h, w, cin, cout
-    a.mode, a.act, a.ksplit = mode, _ACT[act], ksplit
-    a.noise_strength, a.alpha, a.gain = noise_strength, alpha, gain
-    a.clamp = -1.0 if clamp is None else float(clamp)
-    a.x_absmax, a.y_absmax = _ptr(x_absmax), _ptr(y_absmax)
-    a.x_f16, a.y_f16 = int(x_f16), int(y_f16)
+    if (x.dtype == torch.float16 or y_f16) and not (wt.dtype == torch.float16 and wt.dim() == 5 and wt.shape[0] == 1):
+        raise RuntimeError("modconv: fp16 storage (float16 x / y_f16) goes with the single-pass fp16 weight image")
+    _chk_act(x, "x")
+    if wt.dtype == torch.float32:
+        _chk(wt, "wt")
+    elif not (wt.is_cuda and wt.is_contiguous()):
+        raise RuntimeError("modconv: 16-bit weight images must come from weight_prep_prec")
+    if rgb_w is not None:
+        _chk(rgb_w, "rgb_w")
+    # (rgb_w is in the args BEFORE the workspace query: the kernel choice — small-image vs staged — reads it)
+    a, b, h, w = _modconv_args(x, wt, cout, mode, styles, dcoef, noise, noise_strength, bias, act, alpha, gain, clamp, batch,
+                               ksplit, x_absmax, y_absmax, rgb_w, y_f16, x_parts)
     ydt = torch.float16 if y_f16 else torch.float32
-    if not store_y:
-        # only the fused toRGB sums are wanted (`rgb_w`): the activation is not written at all
+    if not store_y:                             # only the fused toRGB sums are wanted (`rgb_w`): the activation is not written at all
         if rgb_w is None or y_absmax is not None:
             raise RuntimeError("modconv: store_y=False needs rgb_w (the fused toRGB is then the only output) and no y_absmax")
         y = None
@@ -359,39 +376,58 @@ def modconv(x: torch.Tensor, wt: torch.Tensor, cout: int, mode: int, styles: Opt
         y = torch.empty(b, 2 * h + 1, 2 * w + 1, cout, device=x.device, dtype=ydt)
     else:
         y = torch.empty(b, h, w, cout, device=x.device, dtype=ydt)
-    a.y = y.data_ptr() if y is not None else None
-    if rgb_w is not None:
-        a.rgb_w = _ptr(_chk(rgb_w, "rgb_w"))   # set BEFORE the workspace query: the kernel choice (small-image vs staged) reads it
+    a.y = _ptr(y)
     nbytes = L.lib().hfagp_modconv_workspace_bytes(C.byref(a))
-    ws = None
-    if nbytes:
-        ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32)
-        a.workspace = _ptr(ws)
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=torch.float32) if nbytes else None
     part = None
     if rgb_w is not None:
         part = torch.empty(L.lib().hfagp_modconv_rgb_parts(C.byref(a)), b, h, w, 4, device=x.device, dtype=torch.float32)
-        a.rgb_w, a.rgb_part = _ptr(_chk(rgb_w, "rgb_w")), _ptr(part)
+    a.workspace, a.rgb_part = _ptr(ws), _ptr(part)
     L.check(L.lib().hfagp_modconv_fwd(C.byref(a), _stream()), "modconv_fwd")
     return y if rgb_w is None else (y, part)
 
 
+_PLAN_UNSPLIT = {}       # (mode, B, H, W, Cin, Cout, precision, x_f16, y_f16, fused toRGB, broadcast x) -> hfagp_modconv_workspace_bytes() == 0
+_NONNULL = 1             # stands in for a buffer that does not exist yet when the library is only ASKED about a call
+
+
+def _plan_unsplit(key, build, rgb: bool = False) -> bool:
+    """Whether the library runs the call ``build()`` describes (`_modconv_args`; ``rgb``: with a fused toRGB) WITHOUT splitting K,
+    the epilogue in the conv kernel: hfagp_modconv_workspace_bytes() == 0 (include/hfagp.h), asked once per ``key`` (the fields
+    of the call that planning reads).  The plan's developer switches are not in the key: the library reads them once per process
+    (`static` in make_plan, csrc/modconv_plan.h).  Planning dereferences nothing, but wants x / wt / y (and rgb_w) non-null."""
+    r = _PLAN_UNSPLIT.get(key)
+    if r is None:
+        a = build()
+        a.x, a.wt, a.y, a.rgb_w = a.x or _NONNULL, a.wt or _NONNULL, _NONNULL, _NONNULL if rgb else None
+        r = _PLAN_UNSPLIT[key] = L.lib().hfagp_modconv_workspace_bytes(C.byref(a)) == 0
+    return r
+
+
 def f16_storage_supported(h: int, w: int, cin: int, cout: int, batch: int) -> bool:
-    """Whether a 3x3 / up-sampling modconv on an h x w input grid can keep its activations in fp16 (`modconv` y_f16,
-    float16 x): 128-channel output tiles and a launch the library does not split along K (its rule, modconv_plan.h: more than
-    half a block per CU — 129 blocks of 8 x 16 positions x 128 channels — or fewer than four 16-channel K chunks)."""
+    """Whether a 3x3 AND an up-sampling modconv on an h x w input grid can keep their activations in fp16 (`modconv` y_f16,
+    float16 x): Cin a multiple of 16, 128-channel output tiles, and launches the library does not split along K — its own
+    answer (`_plan_unsplit`) for the two calls, described here from their shapes alone."""
     if cin % 16 != 0 or cout % 128 != 0:
         return False
-    return cin < 64 or batch * ((h + 7) // 8) * ((w + 15) // 16) * (cout // 128) >= 129
+
+    def call(mode):
+        x = torch.empty(batch, h, w, cin, dtype=torch.float16, device="meta")
+        wt = torch.empty(1, 9, cin // 8, cout, 8, dtype=torch.float16, device="meta")      # (`weight_prep_prec(.., "f16")`)
+        return _modconv_args(x, wt, cout, mode, y_f16=True)[0]
+    return all(_plan_unsplit((mode, batch, h, w, cin, cout, PREC_F16, 1, 1, False, False), lambda: call(mode))
+               for mode in (CONV3X3, CONVT3X3_UP2))
 
 
 def fused_torgb_supported(x: torch.Tensor, wt: torch.Tensor, cout: int, batch: int) -> bool:
     """Whether `modconv(..., mode=CONV3X3, rgb_w=...)` can form the toRGB sums in its epilogue: 16-bit weight image,
-    Cout a multiple of 128, and a grid large enough that the library does not split K (then the epilogue lives in the
-    reducer): the library's own rule, at least 129 blocks of 8 x 16 positions x 128 channels (modconv_plan.h)."""
+    Cout a multiple of 128, and a launch the library does not split along K (then the epilogue lives in the reducer): its
+    own answer for that call (`_plan_unsplit`)."""
     if wt.dtype == torch.float32 or cout % 128 != 0:
         return False
-    h, w = x.shape[1], x.shape[2]
-    return batch * ((h + 7) // 8) * ((w + 15) // 16) * (cout // 128) >= 129
+    xb, h, w, cin = x.shape
+    key = (CONV3X3, batch, h, w, cin, cout, _image_precision(wt), int(x.dtype == torch.float16), 0, True, xb == 1 and batch > 1)
+    return _plan_unsplit(key, lambda: _modconv_args(x, wt, cout, CONV3X3, batch=batch)[0], rgb=True)
 
 
 def torgb_finish(part: torch.Tensor, bias: torch.Tensor, rgb_in: Optional[torch.Tensor], clamp: Optional[float],
@@ -404,33 +440,9 @@ def torgb_finish(part: torch.Tensor, bias: torch.Tensor, rgb_in: Optional[torch.
     a.part, a.bias, a.rgb_out, a.y_pre = _ptr(part), _ptr(_chk(bias, "bias")), _ptr(out), _ptr(y_pre)
     a.rgb_in = _ptr(_chk(rgb_in, "rgb_in")) if rgb_in is not None else None
     a.nparts, a.B, a.H, a.W, a.Cout = nparts, b, h, w, cout
-    a.clamp = -1.0 if clamp is None else float(clamp)
+    a.clamp = _clamp(clamp)
     L.check(L.lib().hfagp_torgb_finish_fwd(C.byref(a), _stream()), "torgb_finish_fwd")
     return out
-
-
-def _up_layer_args(x, wt, cout, styles, dcoef, noise, noise_strength, bias, act, alpha, gain, clamp, batch, x_absmax,
-                   y_absmax, y_f16):
-    x_f16 = x.dtype == torch.float16
-    xb, h, w, cin = x.shape
-    b = batch if batch is not None else xb
-    a = L.ModconvArgs()
-    a.x, a.wt = x.data_ptr(), wt.data_ptr()
-    if wt.dtype == torch.float16:
-        a.precision = PREC_F16 if wt.shape[0] == 1 else PREC_F16X3
-    elif wt.dtype == torch.bfloat16:
-        a.precision = PREC_BF16X3 if wt.shape[0] == 2 else PREC_BF16X6
-    else:
-        a.precision = PREC_F32
-    a.styles, a.dcoef, a.noise, a.bias = _ptr(styles), _ptr(dcoef), _ptr(noise), _ptr(bias)
-    a.x_batch_stride = 0 if (xb == 1 and b > 1) else h * w * cin
-    a.B, a.H, a.W, a.Cin, a.Cout = b, h, w, cin, cout
-    a.mode, a.act, a.ksplit = CONVT3X3_UP2, _ACT[act], 0
-    a.noise_strength, a.alpha, a.gain = noise_strength, alpha, gain
-    a.clamp = -1.0 if clamp is None else float(clamp)
-    a.x_absmax, a.y_absmax = _ptr(x_absmax), _ptr(y_absmax)
-    a.x_f16, a.y_f16 = int(x_f16), int(y_f16)
-    return a, b, h, w
 
 
 _FIR_SCRATCH = {}        # (device, stream) -> scratch tensor of upconv_fir, grown on demand to the next power of two
@@ -438,10 +450,10 @@ _FIR_RETIRED = []        # outgrown scratch tensors stay alive: a HIP graph capt
 _FIR_BYTES = {}          # (shape, precision, storage, developer switches) -> hfagp_upconv_fir_scratch_bytes (0 = not supported)
 
 
-def _fir_scratch_bytes(a, x_f16: bool) -> int:
+def _fir_scratch_bytes(a) -> int:
     """hfagp_upconv_fir_scratch_bytes, memoised per layer shape: the library builds the whole launch plan to answer, and the
     generator asks twice per up-sampling layer call (supported? / how much scratch?)."""
-    key = (a.B, a.H, a.W, a.Cin, a.Cout, a.precision, x_f16, a.x_batch_stride == 0,
+    key = (a.B, a.H, a.W, a.Cin, a.Cout, a.precision, a.x_f16, a.x_batch_stride == 0,
            os.environ.get("HFAGP_DEV_FIR_MIN_BLOCKS"), os.environ.get("HFAGP_DEV_FIR_NSEG"), os.environ.get("HFAGP_DEV_FIR_LEAN"))
     n = _FIR_BYTES.get(key)
     if n is None:
@@ -452,12 +464,10 @@ def _fir_scratch_bytes(a, x_f16: bool) -> int:
 def upconv_fir_supported(x: torch.Tensor, wt: torch.Tensor, cout: int, batch: Optional[int] = None) -> bool:
     """Whether `upconv_fir` takes this up-sampling layer (16-bit weight image with one or two parts, Cin % 16 == 0,
     Cout % 128 == 0 and a launch that fills the chip): the library's own rule, hfagp_upconv_fir_scratch_bytes() > 0."""
-    if wt.dtype == torch.float32 or not x.is_cuda:
+    if wt.dtype == torch.float32 or not x.is_cuda or (x.dtype == torch.float16 and not (wt.dtype == torch.float16 and wt.shape[0] == 1)):
         return False
-    if (x.dtype == torch.float16) and not (wt.dtype == torch.float16 and wt.shape[0] == 1):
-        return False
-    a, *_ = _up_layer_args(x, wt, cout, None, None, None, 0.0, None, "linear", 0.2, 1.0, None, batch, None, None, False)
-    return _fir_scratch_bytes(a, x.dtype == torch.float16) > 0
+    a, *_ = _modconv_args(x, wt, cout, CONVT3X3_UP2, batch=batch, who="upconv_fir")
+    return _fir_scratch_bytes(a) > 0
 
 
 def upconv_fir(x: torch.Tensor, wt: torch.Tensor, cout: int, styles: Optional[torch.Tensor], dcoef: Optional[torch.Tensor],
@@ -469,15 +479,12 @@ def upconv_fir(x: torch.Tensor, wt: torch.Tensor, cout: int, styles: Optional[to
     bias_act(FIR(conv_transpose2d(x * styles, W, stride 2)) * dcoef + noise) (EG3D conv2d_resample(up=2) + bias_act), the raw
     transposed-conv result never leaving the chip (`modconv(mode=CONVT3X3_UP2)` + `upfir_epilogue` move it through HBM in
     fp32).  Only where `upconv_fir_supported` says so."""
-    if x.dtype != torch.float16:
-        _chk(x, "x")
-    elif not (x.is_cuda and x.is_contiguous()):
-        raise RuntimeError("x: expected a contiguous CUDA/ROCm tensor")
+    _chk_act(x, "x")
     if wt.dtype == torch.float32 or not (wt.is_cuda and wt.is_contiguous() and wt.dim() == 5):
         raise RuntimeError("upconv_fir: needs a 16-bit weight image from weight_prep_prec")
-    a, b, h, w = _up_layer_args(x, wt, cout, styles, dcoef, noise, noise_strength, bias, act, alpha, gain, clamp, batch,
-                                x_absmax, y_absmax, y_f16)
-    nbytes = _fir_scratch_bytes(a, x.dtype == torch.float16)
+    a, b, h, w = _modconv_args(x, wt, cout, CONVT3X3_UP2, styles, dcoef, noise, noise_strength, bias, act, alpha, gain, clamp,
+                               batch, x_absmax=x_absmax, y_absmax=y_absmax, y_f16=y_f16, who="upconv_fir")
+    nbytes = _fir_scratch_bytes(a)
     if nbytes == 0:
         raise RuntimeError("upconv_fir: this layer shape / precision / batch is not supported (upconv_fir_supported)")
     key = (x.device, torch.cuda.current_stream(x.device).cuda_stream)
@@ -499,12 +506,7 @@ def upfir_epilogue(yt: torch.Tensor, dcoef: Optional[torch.Tensor], noise: Optio
                    y_absmax: Optional[torch.Tensor] = None) -> torch.Tensor:
     """yt [B, 2H+1, 2W+1, C] raw transposed conv → FIR(pad 1, gain 4) → demod/noise/bias/act → [B,2H,2W,C].
     A float16 ``yt`` (fp16 storage, `modconv` y_f16) gives a float16 result; the arithmetic is fp32 either way."""
-    half = yt.dtype == torch.float16
-    if half:
-        if not (yt.is_cuda and yt.is_contiguous()):
-            raise RuntimeError("yt: expected a contiguous CUDA/ROCm tensor")
-    else:
-        _chk(yt, "yt")
+    half = _chk_act(yt, "yt").dtype == torch.float16
     b, hi, wi, c = yt.shape
     h, w = (hi - 1) // 2, (wi - 1) // 2
     y = torch.empty(b, 2 * h, 2 * w, c, device=yt.device, dtype=yt.dtype)
@@ -513,7 +515,7 @@ def upfir_epilogue(yt: torch.Tensor, dcoef: Optional[torch.Tensor], noise: Optio
     a.io_f16 = int(half)
     a.B, a.H, a.W, a.C, a.act = b, h, w, c, _ACT[act]
     a.noise_strength, a.alpha, a.gain = noise_strength, alpha, gain
-    a.clamp = -1.0 if clamp is None else float(clamp)
+    a.clamp = _clamp(clamp)
     a.y_absmax = _ptr(y_absmax)
     L.check(L.lib().hfagp_upfir_epilogue_fwd(C.byref(a), _stream()), "upfir_epilogue_fwd")
     return y
@@ -561,10 +563,7 @@ def torgb_skip(x: torch.Tensor, wt: torch.Tensor, cout: int, styles: torch.Tenso
     if not (wt.is_cuda and wt.is_contiguous() and wt.dim() == 5 and wt.dtype in (torch.float16, torch.bfloat16)):
         raise RuntimeError("torgb_skip: the weight image must come from weight_prep_prec (16-bit kinds)")
     a = L.TorgbSkipArgs()
-    if wt.dtype == torch.float16:
-        a.precision = PREC_F16 if wt.shape[0] == 1 else PREC_F16X3
-    else:
-        a.precision = PREC_BF16X3 if wt.shape[0] == 2 else PREC_BF16X6
+    a.precision = _image_precision(wt, who="torgb_skip")
     out = torch.empty((b, 3, h, w, cout // 3) if plane_major else (b, h, w, cout), device=x.device, dtype=torch.float32)
     a.x, a.wt, a.styles, a.bias = _ptr(x), wt.data_ptr(), _ptr(_chk(styles, "styles")), _ptr(_chk(bias, "bias"))
     if img is not None:
@@ -592,7 +591,7 @@ def torgb_small(x: torch.Tensor, weight: torch.Tensor, styles: torch.Tensor, bia
     a.rgb_in = _ptr(_chk(rgb_in, "rgb_in")) if rgb_in is not None else None
     a.rgb_out = _ptr(out)
     a.B, a.H, a.W, a.Cin, a.Cout = b, h, w, cin, cout
-    a.clamp = -1.0 if clamp is None else float(clamp)
+    a.clamp = _clamp(clamp)
     L.check(L.lib().hfagp_torgb_fwd(C.byref(a), _stream()), "torgb_fwd")
     return out
 
@@ -817,7 +816,7 @@ def _bias_act_raw(x, b, dim, act, alpha, gain, clamp):
     for s in x.shape[dim + 1:]:
         inner *= s
     L.check(L.lib().hfagp_bias_act_fwd(_ptr(x), _ptr(b), _ptr(y), x.numel(), x.shape[dim], inner, _ACT[act],
-                                       alpha, gain, -1.0 if clamp is None else float(clamp), _stream()), "bias_act_fwd")
+                                       alpha, gain, _clamp(clamp), _stream()), "bias_act_fwd")
     return y
 
 
@@ -835,8 +834,8 @@ class _BiasAct(torch.autograd.Function):
         dim, act, alpha, gain, clamp, has_b = ctx.cfg
         dy = _chk(dy.contiguous(), "dy")
         dx = torch.empty_like(y)
-        L.check(L.lib().hfagp_bias_act_bwd(_ptr(dy), _ptr(y), _ptr(dx), y.numel(), _ACT[act], alpha, gain,
-                                           -1.0 if clamp is None else float(clamp), _stream()), "bias_act_bwd")
+        L.check(L.lib().hfagp_bias_act_bwd(_ptr(dy), _ptr(y), _ptr(dx), y.numel(), _ACT[act], alpha, gain, _clamp(clamp),
+                                           _stream()), "bias_act_bwd")
         db = dx.sum([d for d in range(dx.dim()) if d != dim]) if has_b else None
         return dx, db, None, None, None, None, None
 
@@ -848,7 +847,7 @@ def bias_act_bwd(dy: torch.Tensor, y: torch.Tensor, act: str, alpha: float, gain
     _chk(dy, "dy"), _chk(y, "y")
     dx = torch.empty_like(y)
     L.check(L.lib().hfagp_bias_act_bwd(_ptr(dy), _ptr(y), _ptr(dx), y.numel(), _ACT[act], alpha, gain,
-                                       -1.0 if clamp is None else float(clamp), _stream()), "bias_act_bwd")
+                                       _clamp(clamp), _stream()), "bias_act_bwd")
     return dx
 
 
@@ -945,7 +944,7 @@ def pointwise_bwd(x: torch.Tensor, dxs_conv=None, s_conv=None, dxs_rgb=None, s_r
     a.B, a.H, a.W, a.C, a.nchunks = b, h, w, c, nchunks
     a.Co = g_rgb_small.shape[1] if g_rgb_small is not None else 0
     a.y_rgb_small = _ptr(y_rgb_small) if (y_rgb_small is not None and clamp_rgb_small is not None) else None
-    a.clamp_rgb_small = -1.0 if clamp_rgb_small is None else float(clamp_rgb_small)
+    a.clamp_rgb_small = _clamp(clamp_rgb_small)
     for t in (g_nchw3_a, g_nchw3_b):
         if t is not None and tuple(t.shape) != (b, 3, h, w):
             raise RuntimeError(f"pointwise_bwd: g_nchw3_* must be [B, 3, H, W] = {(b, 3, h, w)}, got {tuple(t.shape)}")
@@ -960,7 +959,7 @@ def pointwise_bwd(x: torch.Tensor, dxs_conv=None, s_conv=None, dxs_rgb=None, s_r
         a.act_p = _ACT[producer.get("act", "lrelu")]
         a.alpha, a.gain = producer.get("alpha", 0.2), producer.get("gain", math.sqrt(2.0))
         clamp = producer.get("clamp")
-        a.clamp = -1.0 if clamp is None else float(clamp)
+        a.clamp = _clamp(clamp)
     L.check(L.lib().hfagp_pointwise_bwd(C.byref(a), _stream()), "pointwise_bwd")
     return g_out, sums
 
