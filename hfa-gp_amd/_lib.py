@@ -14,7 +14,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (HFAGP_LIB_PATH: developer override, used by the ablation builds of tools/dev/ — the product loads the in-tree library)
 LIB_PATH = os.environ.get("HFAGP_LIB_PATH") or os.path.join(_HERE, "libhfagp_hip.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 c_float_p = C.c_void_p  # device pointers travel as integers
 
@@ -69,6 +69,7 @@ class ModconvArgs(C.Structure):
         ("x_absmax", C.c_void_p), ("y_absmax", C.c_void_p),
         ("rgb_w", C.c_void_p), ("rgb_part", C.c_void_p),
         ("x_f16", C.c_int32), ("y_f16", C.c_int32),
+        ("w_absmax", C.c_void_p),
     ]
 
 
@@ -91,6 +92,7 @@ class TorgbSkipArgs(C.Structure):
         ("img_in", C.c_void_p), ("img_out", C.c_void_p), ("x_absmax", C.c_void_p), ("out_absmax", C.c_void_p),
         ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Cin", C.c_int32), ("Cout", C.c_int32),
         ("precision", C.c_int32), ("plane_major", C.c_int32),
+        ("w_absmax", C.c_void_p),
     ]
 
 
@@ -151,7 +153,7 @@ class BiasNoiseGradItem(C.Structure):
 
 class WeightPrepItem(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("weight", "image", "image_t", "wsq")] + \
-        [(n, C.c_int32) for n in ("Cout", "Cin", "taps", "precision", "precision_t")]
+        [(n, C.c_int32) for n in ("Cout", "Cin", "taps", "precision", "precision_t")] + [("w_absmax", C.c_void_p)]
 
 
 class StyleBwdItem(C.Structure):
@@ -187,6 +189,7 @@ SYMBOLS = {
     "hfagp_style_batch_fwd": (C.c_int, [C.POINTER(StyleArgs), C.c_int32, C.c_void_p]),
     "hfagp_weight_prep_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "hfagp_weight_prep_prec": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "hfagp_weight_prep_scaled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "hfagp_modconv_workspace_bytes": (C.c_size_t, [C.POINTER(ModconvArgs)]),
     "hfagp_modconv_fwd": (C.c_int, [C.POINTER(ModconvArgs), C.c_void_p]),
     "hfagp_upfir_epilogue_fwd": (C.c_int, [C.POINTER(UpfirEpilogueArgs), C.c_void_p]),

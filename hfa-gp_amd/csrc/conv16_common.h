@@ -16,7 +16,7 @@ constexpr int BNB = 128;         // output channels per block
 // the streaming up-sampling layer for Cin = 32 (upfir_lean.hip), planned and launched from upconv_fir.hip's entry points
 struct LeanParams {
     const float* x; const void* wt; const float* styles; const float* dcoef; const float* noise; const float* bias;
-    const float* x_absmax; float* y_absmax; float* y;
+    const float* x_absmax; const float* w_absmax; float* y_absmax; float* y;
     long long x_batch_stride;
     int B, H, W, Cout;
     int nstrip, nseg, nsteps;       // column strips of 28 output columns, row segments per strip, steps (8 output rows) per column

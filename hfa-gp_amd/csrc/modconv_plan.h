@@ -23,6 +23,7 @@ struct ConvParams {
     const float* x; const void* wt; const float* styles; const float* dcoef;
     const float* noise; const float* bias;
     const float* x_absmax; float* y_absmax;    // fp16 range tracking (hfagp.h), may be null
+    const float* w_absmax;                     // max |w| behind a scaled float16 weight image (hfagp.h), null: the image is the weight
     const float* rgb_w; float* rgb_part;       // fused toRGB (hfagp.h), may be null
     int x_f16, y_f16;                          // fp16 storage of x / y (hfagp.h)
     float* out;                  // y, or the split-K workspace
@@ -69,7 +70,7 @@ static inline int make_plan(const HfagpModconvArgs* a, Plan& pl, int ck) {
     ConvParams& p = pl.p;
     p = ConvParams{};
     p.x = a->x; p.wt = a->wt; p.styles = a->styles; p.dcoef = a->dcoef; p.noise = a->noise; p.bias = a->bias;
-    p.x_absmax = a->x_absmax; p.y_absmax = a->y_absmax;
+    p.x_absmax = a->x_absmax; p.y_absmax = a->y_absmax; p.w_absmax = a->w_absmax;
     p.rgb_w = a->rgb_w; p.rgb_part = a->rgb_part;
     p.x_f16 = a->x_f16; p.y_f16 = a->y_f16;
     p.x_batch_stride = a->x_batch_stride;

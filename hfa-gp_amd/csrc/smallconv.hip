@@ -50,7 +50,7 @@ __global__ void __launch_bounds__(kSmallWaves * 64, 2) smallconv_kernel(const Co
 
     for (int i = tid; i < p.Cin; i += kSmallWaves * 64) Ss[i] = p.styles ? p.styles[(size_t)b * p.Cin + i] : 1.f;
     float sback = 1.f, sdown = 1.f;
-    if constexpr (F16) sdown = style_range_guard(p.styles ? p.styles + (size_t)b * p.Cin : nullptr, p.Cin, lane, &sback, p.x_absmax);
+    if constexpr (F16) sdown = style_range_guard(p.styles ? p.styles + (size_t)b * p.Cin : nullptr, p.Cin, lane, &sback, p.x_absmax, p.w_absmax);
 
     // this lane's position of the tile and, per tap, the byte offset of its 8 channels in chunk 0 + the zero-padding mask
     const int pos = mt_blk * 32 + l31;

@@ -97,8 +97,24 @@ __device__ __forceinline__ void split4(float4 v, uint2 (&out)[kind_parts_a(KD)])
 // With x_absmax (the producer's max |x| of the whole input tensor, HFAGP_ABSMAX_SLOTS slots) the operand is also
 // scaled by the power of two that brings max |x| into [2^14, 2^15): a tensor beyond fp16's range (an fp32 backbone has
 // no clamp) cannot saturate, a tiny one keeps all 22 bits of its two parts; again exact.
+// With w_absmax (max |w| of the tensor a SCALED float16 weight image was made from, hfagp.h "Weight images") the image holds
+// w 2^-ew: 2^ew goes into *back with the rest, so the main loops never see it.
+// exponent ew of a scaled float16 weight image: max |w| = f 2^ex, f in [0.5, 1) -> ew = 8 floor((ex + 3) / 8), the multiple of 8 that
+// brings the image's maximum into [2^-4, 2^4): the low part's absolute step 2^-24 is then at most 2^-20 of the maximum (error
+// <= 2^-21 max |w| per element), nothing is near 65504, and ew = 0 — the image of the weight itself, the bits of a raw image — for
+// every tensor with 2^-4 <= max |w| < 2^4 (unit-scale and 1/sqrt(fan-in) initialisations).  0 without w_absmax, for an all-zero
+// and for a non-finite tensor.  The prep kernels and the consumers both call this.
+__device__ __forceinline__ int weight_image_exp(const float* w_absmax) {
+    if (!w_absmax) return 0;
+    const float m = *w_absmax;
+    int ex = 0;
+    if (m > 0.f && m < 3.0e38f) (void)frexpf(m, &ex);
+    const int t = ex + 3;
+    return max(-120, min(120, 8 * (t >= 0 ? t / 8 : -((7 - t) / 8))));
+}
+
 __device__ __forceinline__ float style_range_guard(const float* styles, int cin, int lane, float* back,
-                                                   const float* x_absmax) {
+                                                   const float* x_absmax, const float* w_absmax) {
     float m = styles ? 0.f : 1.f;
     if (styles)
         for (int i = lane; i < cin; i += 64) m = fmaxf(m, fabsf(styles[i]));
@@ -113,7 +129,7 @@ __device__ __forceinline__ float style_range_guard(const float* styles, int cin,
     if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &ex);        // mx = f 2^ex, f in [0.5, 1)
     e += ex - 15;
     e = max(-100, min(100, e));
-    *back = ldexpf(1.f, e);
+    *back = ldexpf(1.f, max(-126, min(127, e + weight_image_exp(w_absmax))));
     return ldexpf(1.f, -e);
 }
 

@@ -34,7 +34,7 @@ __global__ void __launch_bounds__(256, 3) torgb_skip_kernel(const HfagpTorgbSkip
     const int b = __builtin_amdgcn_readfirstlane((int)(((long long)blockIdx.x * 128) / HW));   // H*W % 128 == 0
     for (int i = tid; i < a.Cin; i += 256) Ss[i] = a.styles[(size_t)b * a.Cin + i];
     float sback = 1.f, sdown = 1.f;
-    if constexpr (F16) sdown = style_range_guard(a.styles + (size_t)b * a.Cin, a.Cin, lane, &sback, a.x_absmax);
+    if constexpr (F16) sdown = style_range_guard(a.styles + (size_t)b * a.Cin, a.Cin, lane, &sback, a.x_absmax, a.w_absmax);
     __syncthreads();
 
     const int nchunks = a.Cin / CKB;

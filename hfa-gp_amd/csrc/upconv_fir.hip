@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(512, 1) upconv_fir_kernel(const ConvParams p, 
     const char* xb = reinterpret_cast<const char*>(p.x) + (long long)b * p.x_batch_stride * XB;
     for (int i = tid; i < p.Cin; i += NTH) Ss[i] = p.styles ? p.styles[(size_t)b * p.Cin + i] : 1.f;
     float sback = 1.f, sdown = 1.f;
-    if constexpr (F16) sdown = style_range_guard(p.styles ? p.styles + (size_t)b * p.Cin : nullptr, p.Cin, lane, &sback, p.x_absmax);
+    if constexpr (F16) sdown = style_range_guard(p.styles ? p.styles + (size_t)b * p.Cin : nullptr, p.Cin, lane, &sback, p.x_absmax, p.w_absmax);
     if (tid < 128) {
         DB[tid] = p.dcoef ? p.dcoef[(size_t)b * p.Cout + co0 + tid] : 1.f;
         DB[128 + tid] = p.bias ? p.bias[co0 + tid] : 0.f;

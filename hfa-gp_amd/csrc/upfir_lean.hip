@@ -84,7 +84,7 @@ __global__ void __launch_bounds__(256, 2) upfir_lean_kernel(const LeanParams p) 
     // ---- styles + fp16 range guard of this sample
     if (tid < LCIN) Ss[tid] = p.styles ? p.styles[(size_t)b * LCIN + tid] : 1.f;
     float sback = 1.f, sdown = 1.f;
-    if constexpr (F16) sdown = style_range_guard(p.styles ? p.styles + (size_t)b * LCIN : nullptr, LCIN, lane, &sback, p.x_absmax);
+    if constexpr (F16) sdown = style_range_guard(p.styles ? p.styles + (size_t)b * LCIN : nullptr, LCIN, lane, &sback, p.x_absmax, p.w_absmax);
 
     // ---- weights of the wave's channels: A operand, lane (q, pc) = input channels 8q .. 8q+7 of output channel co + pc
     u32x4 wf[NITEM][NPB];
@@ -314,7 +314,7 @@ bool upfir_lean_plan(const HfagpModconvArgs* a, LeanParams& lp, long long min_bl
 
 int launch_upfir_lean(const HfagpModconvArgs* a, LeanParams& lp, hipStream_t s) {
     lp.x = a->x; lp.wt = a->wt; lp.styles = a->styles; lp.dcoef = a->dcoef; lp.noise = a->noise; lp.bias = a->bias;
-    lp.x_absmax = a->x_absmax; lp.y_absmax = a->y_absmax; lp.y = a->y;
+    lp.x_absmax = a->x_absmax; lp.w_absmax = a->w_absmax; lp.y_absmax = a->y_absmax; lp.y = a->y;
     lp.x_batch_stride = a->x_batch_stride;
     lp.act = a->act; lp.noise_strength = a->noise_strength; lp.alpha = a->alpha; lp.gain = a->gain; lp.clamp = a->clamp;
     HFAGP_REQUIRE(a->act != HFAGP_ACT_LRELU || (a->alpha >= 0.f && a->alpha <= 1.f), HFAGP_EUNSUPPORTED,

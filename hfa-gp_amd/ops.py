@@ -94,7 +94,15 @@ def split_supported(cin: int, cout: int, up: bool = False) -> bool:
 def weight_prep_prec(weight: torch.Tensor, precision: str) -> torch.Tensor:
     """weight [Cout, Cin, k, k] fp32 → B-operand image [parts, k*k, Cin/8, Cout, 8] of a 16-bit conv precision:
     'bf16x3' / 'bf16x6' = 2 / 3 bfloat16 parts, 'f16x3' = 2 float16 parts (each part the round-to-nearest value of
-    the residual left by the parts before it), 'f16' = one float16 part."""
+    the residual left by the parts before it), 'f16' = one float16 part.
+    The float16 kinds are SCALED images (include/hfagp.h "Weight images"): the parts of w * 2^-e, e the multiple of 8 that brings
+    max |w| of the tensor into [2^-4, 2^4) (0 for unit-scale weights), so their accuracy class does not depend on the weight's scale.  max |w| stays on the device, in
+    ``image.w_absmax`` (one float): `modconv` / `upconv_fir` / `torgb_skip` pass it on with the image, so hand them the returned
+    tensor itself — a copy or a view of it would be taken for an image of the raw weight (`weight_prep_split` makes those)."""
+    return _weight_prep_prec(weight, precision, scaled=_IMAGE_DTYPE[precision] == torch.float16)
+
+
+def _weight_prep_prec(weight: torch.Tensor, precision: str, scaled: bool) -> torch.Tensor:
     _chk(weight, "weight")
     co, ci, kh, kw = weight.shape
     nparts = NPARTS[precision]
@@ -106,8 +114,13 @@ def weight_prep_prec(weight: torch.Tensor, precision: str) -> torch.Tensor:
     numel = nparts * kh * kw * (ci // 8) * co * 8
     flat = torch.empty(numel + 256, device=weight.device, dtype=_IMAGE_DTYPE[precision])
     wb = flat[:numel].view(nparts, kh * kw, ci // 8, co, 8)
-    L.check(L.lib().hfagp_weight_prep_prec(_ptr(weight), wb.data_ptr(), co, ci, kh * kw, PRECISIONS[precision], _stream()),
-            "weight_prep_prec")
+    if scaled:
+        wb.w_absmax = torch.empty(1, device=weight.device, dtype=torch.float32)
+        L.check(L.lib().hfagp_weight_prep_scaled(_ptr(weight), wb.data_ptr(), _ptr(wb.w_absmax), co, ci, kh * kw,
+                                                 PRECISIONS[precision], _stream()), "weight_prep_scaled")
+    else:
+        L.check(L.lib().hfagp_weight_prep_prec(_ptr(weight), wb.data_ptr(), co, ci, kh * kw, PRECISIONS[precision], _stream()),
+                "weight_prep_prec")
     return wb
 
 
@@ -119,7 +132,8 @@ def weight_prep_batch_supported(weight: torch.Tensor) -> bool:
 def weight_prep_batch(items):
     """items: [(weight [Cout,Cin,k,k], precision | None, precision_t | None, want_wsq)] -> [(image | None, image_t | None, wsq | None)]
     in ONE launch per 48 weights (hfagp_weight_prep_batch): the forward image, the image of the Cin/Cout transpose and wsq of every
-    weight from a single read of it.  All outputs of a call live in three flat buffers (one allocation each)."""
+    weight from a single read of it.  All outputs of a call live in three flat buffers (one allocation each), max |w| of the items
+    with a float16 image (scaled images, `weight_prep_prec`: ``image.w_absmax``) in a fourth."""
     metas, n16 = [], {torch.float16: 0, torch.bfloat16: 0}
     nsq = 0
     for w, prec, prec_t, want_wsq in items:
@@ -140,6 +154,7 @@ def weight_prep_batch(items):
     dev = items[0][0].device
     flat = {dt: torch.empty(n, device=dev, dtype=dt) for dt, n in n16.items() if n}
     sq = torch.empty(nsq, device=dev, dtype=torch.float32) if nsq else None
+    amax = torch.empty(len(items), device=dev, dtype=torch.float32) if torch.float16 in flat else None
     out, arr = [], (L.WeightPrepItem * len(items))()
     for k, ((w, prec, prec_t, want_wsq), (sizes, sq_off)) in enumerate(zip(items, metas)):
         co, ci, kh, kw = w.shape
@@ -159,6 +174,10 @@ def weight_prep_batch(items):
         a.Cout, a.Cin, a.taps = co, ci, kh * kw
         a.precision = PRECISIONS[prec] if prec is not None else 0
         a.precision_t = PRECISIONS[prec_t] if prec_t is not None else 0
+        for v in views:
+            if v is not None and v.dtype == torch.float16:
+                v.w_absmax = amax[k: k + 1]
+                a.w_absmax = v.w_absmax.data_ptr()
         out.append((views[0], views[1], wsq))
     for k0 in range(0, len(items), 48):
         n = min(48, len(items) - k0)
@@ -168,8 +187,9 @@ def weight_prep_batch(items):
 
 
 def weight_prep_split(weight: torch.Tensor, nparts: int) -> torch.Tensor:
-    """`weight_prep_prec` by part count: 1 = 'f16', 2 = 'bf16x3', 3 = 'bf16x6'."""
-    return weight_prep_prec(weight, {1: "f16", 2: "bf16x3", 3: "bf16x6"}[nparts])
+    """The image of the RAW weight by part count (hfagp_weight_prep_split): 1 = 'f16' (a plain fp16 rounding of the weight: not
+    scaled, so good for 2^-14 <= |w| <= 65504 only), 2 = 'bf16x3', 3 = 'bf16x6'."""
+    return _weight_prep_prec(weight, {1: "f16", 2: "bf16x3", 3: "bf16x6"}[nparts], scaled=False)
 
 
 def _style_args(a, who: str, w, affine_w, affine_b, wsq, style_gain: float, eps: float):
@@ -332,6 +352,7 @@ def _modconv_args(x: torch.Tensor, wt: torch.Tensor, cout: int, mode: int, style
     a.noise_strength, a.alpha, a.gain, a.clamp = noise_strength, alpha, gain, _clamp(clamp)
     a.x_absmax, a.y_absmax, a.rgb_w = _ptr(x_absmax), _ptr(y_absmax), _ptr(rgb_w)
     a.x_f16, a.y_f16 = int(x.dtype == torch.float16), int(y_f16)
+    a.w_absmax = _ptr(getattr(wt, "w_absmax", None))              # a scaled float16 image (`weight_prep_prec`) brings max |w| along
     return a, b, h, w
 
 
@@ -572,6 +593,7 @@ def torgb_skip(x: torch.Tensor, wt: torch.Tensor, cout: int, styles: torch.Tenso
             raise RuntimeError(f"torgb_skip: img {tuple(img.shape)} is not the half-resolution image of {(b, h, w, cout)}")
         a.img_in = _ptr(img)
     a.img_out, a.x_absmax, a.out_absmax = _ptr(out), _ptr(x_absmax), _ptr(out_absmax)
+    a.w_absmax = _ptr(getattr(wt, "w_absmax", None))
     a.B, a.H, a.W, a.Cin, a.Cout, a.plane_major = b, h, w, cin, cout, int(plane_major)
     L.check(L.lib().hfagp_torgb_skip_fwd(C.byref(a), _stream()), "torgb_skip_fwd")
     return out

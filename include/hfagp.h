@@ -65,7 +65,7 @@
 extern "C" {
 #endif
 
-#define HFAGP_ABI_VERSION 14
+#define HFAGP_ABI_VERSION 15
 
 enum { HFAGP_OK = 0, HFAGP_EBADARG = -1, HFAGP_EUNSUPPORTED = -2, HFAGP_ELAUNCH = -3 };
 
@@ -248,6 +248,25 @@ int hfagp_weight_prep_split(const float* weight, void* wb, int32_t Cout, int32_t
  * F16X3: 2 fp16 parts = round-to-nearest fp16 of the weight and of its residual)                           */
 int hfagp_weight_prep_prec(const float* weight, void* wb, int32_t Cout, int32_t Cin, int32_t taps,
                            int32_t precision, void* stream);
+/* Weight images (ABI 15).  A bfloat16 image holds the weight itself: bfloat16 has fp32's exponent range, so BF16X3 / BF16X6 keep
+ * their class for ANY finite fp32 weight tensor.  A float16 image of the RAW weight (the two calls above) keeps its class only
+ * while the parts are fp16 normals: F16X3 has its 22 bits for 2^-3 <= |w| <= 65504 and loses one bit per factor of two below
+ * (4e-6 of max |y| is crossed near |w| ~ 4e-3), F16 for 2^-14 <= |w| <= 65504; beyond 65504 the image holds infinities.
+ * hfagp_weight_prep_scaled (F16, F16X3 / F16X2 only) lifts that: it finds max |w| of the tensor on the device, writes it to
+ * *w_absmax (one float, device memory, no host synchronisation) and stores the parts of  w * 2^-e,  e = 8 floor((ex + 3) / 8)
+ * where max |w| = f 2^ex, f in [0.5, 1)  — the multiple of 8 that brings the image's maximum into [2^-4, 2^4); e = 0 for an
+ * all-zero or non-finite tensor, and |e| <= 120.  For 2^-4 <= max |w| < 2^4 (unit-scale and 1/sqrt(fan-in) weights) e is 0 and
+ * the image has the bits of the raw one.  Every consumer of the image is given the same pointer (HfagpModconvArgs::w_absmax,
+ * HfagpTorgbSkipArgs::w_absmax), recomputes e from it and folds 2^e into the power of two it already applies to its fp32
+ * accumulators for the style / x_absmax scaling: exact, and no work in the main loops.  Contract: for any finite weight tensor
+ * with 2^-116 <= max |w| the image is off the weight by at most 2^-21 max |w| per element (F16X3; the low part's step 2^-24
+ * against a maximum of at least 2^-4; F16: 2^-11 |w| down to 2^-10 max |w|), nothing overflows, and the result is that of the
+ * same arithmetic at unit scale while the combined power of two 2^(e_styles + e_x + e_w) stays within [2^-126, 2^127] (it is
+ * clamped there); y(w 2^8j) = 2^8j y(w) bit for bit.  What remains is the spread INSIDE one tensor: elements far below the
+ * maximum have fewer bits of their own — against the products of the tensor's large elements in the same sum that is below
+ * the class's error.                                                                                                    */
+int hfagp_weight_prep_scaled(const float* weight, void* wb, float* w_absmax, int32_t Cout, int32_t Cin, int32_t taps,
+                             int32_t precision, void* stream);
 
 /* ABI 11: everything a step needs of a set of conv weights in ONE launch — for each item the forward image (layout of
  * hfagp_weight_prep_prec, `precision`), the image of the Cin/Cout TRANSPOSE (`precision_t`; the bwd-data GEMM's operand) and
@@ -260,6 +279,8 @@ typedef struct {
     float*       wsq;         /* [Cout][Cin] or NULL */
     int32_t Cout, Cin, taps;
     int32_t precision, precision_t;
+    float*       w_absmax;    /* ABI 15: one float, receives max |w|; the item's float16 images (either side) are then SCALED images
+                               * (hfagp_weight_prep_scaled; the transpose has the same maximum).  NULL: raw images */
 } HfagpWeightPrepItem;
 int hfagp_weight_prep_batch(const HfagpWeightPrepItem* items, int32_t n, void* stream);
 
@@ -285,6 +306,7 @@ enum { HFAGP_ACT_LINEAR = 0, HFAGP_ACT_LRELU = 1 };
  *   BF16X6  3 parts, 6 MFMAs per product: relative product error ~2^-23 (fp32 class)
  *   F16X3   operands split into 2 fp16 parts (11 + 11 mantissa bits), 3 v_mfma_f32_32x32x16_f16 per product
  *           (hi.hi + lo.hi + hi.lo): relative product error ~2^-22 — fp32 class at the cost of BF16X3
+ *           (at any weight scale with a scaled image, hfagp_weight_prep_scaled; a raw float16 image: "Weight images" above)
  *   F16     operands rounded to fp16, ONE v_mfma_f32_32x32x16_f16 per product: relative product error ~2^-11.
  *           The arithmetic EG3D's CUDA path uses in its fp16 blocks (super-resolution, sr_num_fp16_res = 4:
  *           SURVEY.md U4) except that tensors stay fp32 in HBM and accumulation is fp32.  The caller keeps
@@ -336,6 +358,9 @@ typedef struct {
      * Only with precision HFAGP_PREC_F16, modes 0 and 1, no split-K (hfagp_modconv_workspace_bytes() == 0); the styles
      * are applied with packed fp16 multiplies and staging is a copy instead of a conversion.                        */
     int32_t x_f16, y_f16;
+    /* ABI 15: max |w| as hfagp_weight_prep_scaled / hfagp_weight_prep_batch left it for a SCALED float16 image (see "Weight
+     * images"); NULL: wt is an image of the raw weight (bfloat16 images always are).  Also read by hfagp_upconv_fir_fwd. */
+    const float* w_absmax;
 } HfagpModconvArgs;
 /* number of partial-sum images a call with rgb_part writes: (Cout / 128) x 2 */
 int32_t hfagp_modconv_rgb_parts(const HfagpModconvArgs* a);
@@ -415,6 +440,7 @@ typedef struct {
     int32_t B, H, W, Cin, Cout;
     int32_t precision;        /* HFAGP_PREC_* of the weight image (not F32) */
     int32_t plane_major;
+    const float* w_absmax;    /* ABI 15: as HfagpModconvArgs::w_absmax (scaled float16 image), or NULL */
 } HfagpTorgbSkipArgs;
 
 int hfagp_torgb_skip_fwd(const HfagpTorgbSkipArgs* a, void* stream);

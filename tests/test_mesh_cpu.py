@@ -88,7 +88,7 @@ def test_marching_cubes_binding_matches_header(lib):
     body = re.sub(r"\[\d+\]", "", body)
     names = [re.findall(r"\w+", part)[-1] for decl in body.split(";") if decl.strip() for part in decl.split(",")]
     assert names == [f[0] for f in lib.MarchingCubesArgs._fields_]
-    assert lib.ABI_VERSION == 14
+    assert lib.ABI_VERSION == 15
     for name in ("hfagp_marching_cubes_count", "hfagp_marching_cubes_emit", "hfagp_marching_cubes_workspace_bytes"):
         assert name in lib.SYMBOLS
 
