@@ -1021,6 +1021,286 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The merged up-conv at F16X3 (KD = 4) on v_mfma_f32_16x16x32_f16 with 32-channel K chunks (upconv_bf16_kernel<4, 4, 0, LOOP>;
+// launch_modconv_bf16 picks it where upconv_mfma16_takes).  What the 16-channel kernel above computes, issued the way of the
+// 32-channel 3x3 loop:
+//   * Same block tile (8 x 16 positions x 64 channels x four parity phases, 128 accumulator registers, two blocks per CU), same
+//     stacked-row / fringe tiling, same grouping of the 9 (phase, tap) items by their four LDS shifts, same weight image, same A
+//     parts (split4<4> of x . style . 2^-e), same split-K slices (cut in 32-channel chunks; an empty slice stores zeros).  A wave
+//     owns patch rows 4 wm .. 4 wm + 3 (four 16-position M tiles) and channels 32 wn .. 32 wn + 31 (two 16-channel N tiles).
+//   * 216 MFMAs per wave per barrier (9 items x 8 tiles x 3 products); the A fragments of a shift group are read once per chunk,
+//     those of the next group per M tile under the last item of the current one.
+//   * Weight fragments by buffer loads (SGPR resource, one per-lane offset for the kernel; tap / chunk / part in the scalar
+//     offset, N tile in the immediate), ring of two items.
+//   * Patch image per part [channel octet][position][16 B], 9 x 17 positions, octet stride 2560 B = 0 mod 256 B: every 16-lane
+//     group of a ds_read_b128 reads 16 consecutive 16-B slots (one run per octet, the runs of a group's lanes 256 B apart modulo
+//     256), every 16-lane group of a ds_write_b64 128 contiguous bytes.  ONE buffer resource covers the up_ns samples from b_lo on
+//     (launch: that span stays below u16::OOB); slots outside an image — row m = H of the stacked pitch, columns outside 0 .. W-1,
+//     rows past up_rows, the fringe tile's column -1 — carry the offset u16::OOB and load zeros.  The range-guard scale 2^-e of
+//     each staged sample is folded into that sample's row of the style image in the prologue.
+//   * The MFMA is issued with the weights as its first operand (16 output channels) and the activations as its second (16
+//     positions) — the fragment layouts are the same, so are the products and their order: a lane's four accumulators are then
+//     four consecutive channels of one position and y_t leaves as 16-byte stores (lane groups lane >> 4: 64 contiguous bytes per
+//     position).  That is LOOP = 2.  LOOP = 1, the operands the other way round and 4-byte stores (16 channels x 4 positions per
+//     instruction, four times the store instructions), was built and measured slower on every flagship layer (family sum 6027
+//     against 5924 us, profiles/r08_upconv16_ab.log) and is not kept.
+namespace u16 {
+constexpr int CK = 32;                            // channels per K chunk
+constexpr int LP = PW + 1, NPOS = (8 + 1) * LP;   // patch row pitch / positions (9 x 17)
+constexpr int OCT = 2560;                         // bytes per channel octet of one part: NPOS x 16 B rounded up to 256 B
+constexpr int A_PART = 4 * OCT, A_BUF = 2 * A_PART;
+constexpr int A_PER_T = 5;                        // float4 slots per thread: 153 positions x 8 quads over 256 threads
+constexpr unsigned OOB = 0xfffff000u;             // patch offset beyond every staged sample (+ the chunk offset: no 32-bit wrap)
+static_assert(NPOS * 16 <= OCT && OCT % 256 == 0 && NPOS * 8 <= A_PER_T * 256 && 2 * A_BUF <= 48 * 1024, "patch layout");
+constexpr size_t lds_bytes(int cin, int ns) { return (size_t)2 * A_BUF + (size_t)ns * (cin + 1) * sizeof(float); }
+}  // namespace u16
+
+template <int KD, int NW, int IO, int LOOP>
+__global__ void __launch_bounds__(256, 2) upconv_bf16_kernel(const ConvParams p) {
+    static_assert(KD == 4 && NW == 4 && IO == 0 && LOOP == 2, "the 32-channel loop is the 4-wave F16X3 up-conv");
+    using namespace u16;
+    typedef float f32x4v __attribute__((ext_vector_type(4)));
+    constexpr int NITEM = 9, RB = 2;                                   // (phase, tap) items per chunk; weight ring slots
+    constexpr int ST = 0;                                              // M tile after which an item converts its patch slot
+    constexpr int I_GRP[NITEM] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
+    constexpr int I_PHASE[NITEM] = {0, 1, 2, 3, 0, 1, 0, 2, 0};
+    constexpr int I_W[NITEM] = {0, 1, 3, 4, 6, 7, 2, 5, 8};
+    constexpr int S_SLOT[NITEM] = {-1, -1, 0, 1, -1, 2, 3, -1, 4};      // patch slot converted under each item
+    constexpr int G_POS[4] = {1 * LP + 1, 0 * LP + 1, 1 * LP + 0, 0};   // patch position of tile position (0, 0) under each shift
+    extern __shared__ __attribute__((aligned(16))) char lds_raw[];
+    char* As = lds_raw;                                                // [2][2 parts][4 octets][OCT]
+    float* Ss = reinterpret_cast<float*>(lds_raw + 2 * A_BUF);         // [up_ns][Cin] styles x 2^-e, then [up_ns] 2^e
+
+    // ---- tiling: as in the 16-channel kernel
+    unsigned id = p.xcd ? xcd_remap(blockIdx.x, gridDim.x) : blockIdx.x;
+    const int tiles_nu = p.Cout / 64;
+    const int tn_blk = __builtin_amdgcn_readfirstlane(id % tiles_nu);  id /= tiles_nu;
+    const int n_reg = p.up_tr * p.up_tw, n_tile = n_reg + p.up_nf;
+    const int T = __builtin_amdgcn_readfirstlane(id % n_tile);         id /= n_tile;
+    const int ks = __builtin_amdgcn_readfirstlane(id);
+    const bool fringe = T >= n_reg;                                    // block-uniform
+    const int RP = p.up_rp, R_total = p.up_rows;
+    const int r0 = fringe ? (T - n_reg) * 64 : (T / p.up_tw) * 8, n0 = fringe ? 0 : (T % p.up_tw) * PW;
+    const int co0 = tn_blk * 64;
+    const int b_lo = min(max(r0 - 1, 0) / RP, p.B - 1);                // first sample the patch touches
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int g = lane >> 4, i16 = lane & 15;
+    const int nch = p.Cin / CK;
+    const int c_begin = __builtin_amdgcn_readfirstlane((int)(((long long)nch * ks) / p.ksplit));
+    const int c_end = __builtin_amdgcn_readfirstlane((int)(((long long)nch * (ks + 1)) / p.ksplit));
+
+    // styles of the up_ns samples from b_lo on (ones past the batch), each row times its sample's range-guard scale 2^-e
+    float* Gb = Ss + p.up_ns * p.Cin;
+    for (int sI = 0; sI < p.up_ns; ++sI) {
+        const float* st = (p.styles && b_lo + sI < p.B) ? p.styles + (size_t)(b_lo + sI) * p.Cin : nullptr;
+        float bk = 1.f;
+        const float dn = style_range_guard(st, p.Cin, lane, &bk, p.x_absmax, p.w_absmax);
+        for (int i = tid; i < p.Cin; i += 256) Ss[sI * p.Cin + i] = (st ? st[i] : 1.f) * dn;
+        if (tid == 0) Gb[sI] = bk;
+    }
+
+    // ---- A staging: slot e = tid + 256 k holds channels 4q .. 4q+3 (q = 2 ((e >> 4) & 3) + (e & 1)) of patch position
+    // 8 (e >> 6) + ((e >> 1) & 7); q does not depend on k.  Positions 153 .. 159 are the padding of the octet: zeros that nobody reads.
+    const int nsamp = min(p.up_ns, p.B - b_lo);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(p.x + (long long)b_lo * p.x_batch_stride), 0,
+        (unsigned)(((long long)(nsamp - 1) * p.x_batch_stride + (long long)p.H * p.W * p.Cin) * 4), 0x00020000);
+    const int qa = 2 * ((tid >> 4) & 3) + (tid & 1);
+    // (registers that live through the K loop are scarce: slot k is 32 k positions after slot 0 in LDS, and the staged sample of
+    // each slot, 0 .. 7, is three bits of the same register above the 14 bits of that address)
+    static_assert(A_PART <= (1 << 14) && 14 + 3 * A_PER_T <= 32, "LDS address and sample indices share a register");
+    unsigned aoff[A_PER_T];
+    unsigned sels = (qa >> 1) * OCT + (8 * (tid >> 6) + ((tid >> 1) & 7)) * 16 + (qa & 1) * 8;
+#pragma unroll
+    for (int k = 0; k < A_PER_T; ++k) {
+        const int pix = 8 * ((tid >> 6) + 4 * k) + ((tid >> 1) & 7);
+        const int pi = pix / LP, pj = pix % LP;
+        int r, n;
+        if (!fringe) { r = r0 - 1 + pi; n = n0 - 1 + pj; }
+        else { r = pj == 0 ? -1 : r0 + 8 * ((pj - 1) >> 1) + pi - 1; n = p.W - 1 + ((pj - 1) & 1); }
+        const bool row_ok = r >= 0 && r < R_total;
+        const int bb = row_ok ? r / RP : b_lo, m = r - bb * RP;
+        const bool inside = pix < NPOS && row_ok && m < p.H && n >= 0 && n < p.W;
+        const int sel = inside ? bb - b_lo : 0;
+        aoff[k] = inside ? (unsigned)(((long long)sel * p.x_batch_stride + (long long)(m * p.W + n) * p.Cin + 4 * qa) * 4) : OOB;
+        sels |= (unsigned)sel << (14 + 3 * k);
+    }
+    static_assert((8 * (3 + 4 * (A_PER_T - 1)) + 7) * 16 < OCT, "every slot lies inside its octet");
+    // (in three parts of two, two and one slots: 8 staging registers instead of 20)
+    float4 ra[2];
+    auto load_a = [&](int chunk, auto part_tag) __attribute__((always_inline)) {
+        constexpr int PT = decltype(part_tag)::value;
+#pragma unroll
+        for (int k = 0; k < (PT < 2 ? 2 : 1); ++k)
+            ra[k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rx, aoff[PT * 2 + k], chunk * CK * 4, 0));
+    };
+    auto store_a = [&](int chunk, auto buf_tag, auto k_tag) __attribute__((always_inline)) {
+        constexpr int BUF = decltype(buf_tag)::value, k = decltype(k_tag)::value;
+        const int sel = (int)((sels >> (14 + 3 * k)) & 7u);
+        const float4 sv = *reinterpret_cast<const float4*>(Ss + chunk * CK + sel * p.Cin + 4 * qa);
+        const int lds_a = (int)(sels & 0x3fffu) + k * 32 * 16;
+        const float4 x = ra[k % 2];
+        uint2 parts[2];
+        split4<KD>(make_float4(x.x * sv.x, x.y * sv.y, x.z * sv.z, x.w * sv.w), parts);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) *reinterpret_cast<uint2*>(As + BUF * A_BUF + q * A_PART + lds_a) = parts[q];
+    };
+
+    // ---- weight fragments: [part][tap][Cin/8][Cout][8] by buffer loads; lane offset (g Cout + co) x 16, N tile tn at +256 tn
+    const int cq8 = p.Cin >> 3;
+    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<void*>(p.wt), 0, (unsigned)(2 * 9 * cq8 * p.Cout) * 16u, 0x00020000);
+    const unsigned boff = (unsigned)(g * p.Cout + co0 + wn * 32 + i16) * 16u;
+    const int part_bytes = 9 * cq8 * p.Cout * 16, tap_bytes = cq8 * p.Cout * 16, chunk_bytes = 4 * p.Cout * 16;
+    // activation fragment of M tile tm (patch row 4 wm + tm, column i16, + the group's shift), lane group g = channel octet g
+    const char* const afrag = As + g * OCT + (4 * wm * LP + i16) * 16;
+
+    f32x4v acc[4][4][2];                                               // phase, M tile, N tile
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn) acc[f][tm][tn] = f32x4v{0.f, 0.f, 0.f, 0.f};
+
+    constexpr int PA[3] = {kind_pa(KD, 0), kind_pa(KD, 1), kind_pa(KD, 2)};
+    constexpr int PB[3] = {kind_pb(KD, 0), kind_pb(KD, 1), kind_pb(KD, 2)};
+    u32x4 bq[RB][2][2];                                                // ring slot, N tile, part
+    u32x4 af[4][2];                                                    // M tile, part (of the shift group being computed)
+    auto issue_b = [&](int c, int w, auto slot_tag) __attribute__((always_inline)) {
+        constexpr int SL = decltype(slot_tag)::value;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int so = q * part_bytes + w * tap_bytes + c * chunk_bytes;   // scalar
+#pragma unroll
+            for (int tn = 0; tn < 2; ++tn) bq[SL][tn][q] = __builtin_amdgcn_raw_buffer_load_b128(rw, boff + 256 * tn, so, 0);
+        }
+    };
+    auto read_a = [&](auto u_tag, auto g_tag, auto tm_tag) __attribute__((always_inline)) {
+        constexpr int UU = decltype(u_tag)::value, G = decltype(g_tag)::value, TMI = decltype(tm_tag)::value;
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+            af[TMI][q] = *reinterpret_cast<const u32x4*>(afrag + UU * A_BUF + q * A_PART + (TMI * LP + G_POS[G]) * 16);
+    };
+    // item = (phase, tap) I of chunk c: the weights of item I + RB - 1 into the ring, then per M tile its 6 MFMAs followed, under the
+    // last item of a shift group, by the reads of that tile's fragments for the next group; the patch of chunk c+1 is fetched at
+    // three parts (at items 0, 3 and 6) and converted one slot per item into the other LDS buffer under items 2, 3 | 5, 6 | 8
+    auto item = [&](int c, auto u_tag, auto i_tag) __attribute__((always_inline)) {
+        constexpr int UU = decltype(u_tag)::value, I = decltype(i_tag)::value, G = I_GRP[I], F = I_PHASE[I];
+        constexpr int SL = (UU * NITEM + I) % RB, IN = I + RB - 1;
+        issue_b(c + IN / NITEM, I_W[IN % NITEM], std::integral_constant<int, (SL + RB - 1) % RB>{});
+        if constexpr (I == 0) load_a(min(c + 1, c_end - 1), std::integral_constant<int, 0>{});
+        __builtin_amdgcn_sched_barrier(0);
+        auto tile = [&](auto tm_tag) __attribute__((always_inline)) {
+            constexpr int TMI = decltype(tm_tag)::value;
+#pragma unroll
+            for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+                for (int tn = 0; tn < 2; ++tn) {
+                    const f16x8 xa = __builtin_bit_cast(f16x8, af[TMI][PA[pr]]), wb = __builtin_bit_cast(f16x8, bq[SL][tn][PB[pr]]);
+                    acc[F][TMI][tn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb, xa, acc[F][TMI][tn], 0, 0, 0);
+                }
+            if constexpr (I + 1 < NITEM && I_GRP[(I + 1) % NITEM] != G) read_a(u_tag, std::integral_constant<int, G + 1>{}, tm_tag);
+            if constexpr (TMI == ST && S_SLOT[I] >= 0)
+                store_a(min(c + 1, c_end - 1), std::integral_constant<int, 1 - UU>{}, std::integral_constant<int, (S_SLOT[I] < 0 ? 0 : S_SLOT[I])>{});
+            if constexpr (TMI == ST && (I == 3 || I == 6))
+                load_a(min(c + 1, c_end - 1), std::integral_constant<int, I / 3>{});
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        tile(std::integral_constant<int, 0>{});
+        tile(std::integral_constant<int, 1>{});
+        tile(std::integral_constant<int, 2>{});
+        tile(std::integral_constant<int, 3>{});
+    };
+    auto chunk = [&](int c, auto u_tag) __attribute__((always_inline)) {
+        __syncthreads();                                               // publishes the patch of chunk c
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+        read_a(u_tag, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+        __builtin_amdgcn_sched_barrier(0);
+        item(c, u_tag, std::integral_constant<int, 0>{});
+        item(c, u_tag, std::integral_constant<int, 1>{});
+        item(c, u_tag, std::integral_constant<int, 2>{});
+        item(c, u_tag, std::integral_constant<int, 3>{});
+        item(c, u_tag, std::integral_constant<int, 4>{});
+        item(c, u_tag, std::integral_constant<int, 5>{});
+        item(c, u_tag, std::integral_constant<int, 6>{});
+        item(c, u_tag, std::integral_constant<int, 7>{});
+        item(c, u_tag, std::integral_constant<int, 8>{});
+    };
+    static_assert((2 * NITEM) % RB == 0, "ring slots must repeat every chunk pair");
+    __syncthreads();                                                   // styles and back-scales are in LDS
+    if (c_begin < c_end) {
+        load_a(c_begin, std::integral_constant<int, 0>{});
+        issue_b(c_begin, I_W[0], std::integral_constant<int, 0>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+        load_a(c_begin, std::integral_constant<int, 1>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+        load_a(c_begin, std::integral_constant<int, 2>{});
+        store_a(c_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 4>{});
+        // pairs of chunks (LDS buffer and ring slots by chunk parity: compile time), then the odd one
+        int cg = c_begin;
+        for (; cg + 1 < c_end; cg += 2) {
+            chunk(cg, std::integral_constant<int, 0>{});
+            chunk(cg + 1, std::integral_constant<int, 1>{});
+        }
+        if (cg < c_end) chunk(cg, std::integral_constant<int, 0>{});
+    }
+
+    // ---- raw stores of the four phases: y_t[2m + (f>>1)][2n + (f&1)], extents (H+1-(f>>1)) x (W+1-(f&1)), times the sample's 2^e.
+    // C/D layout of 16x16: column = lane & 15 = tile column of patch row 4 wm + tm, rows 4 (lane >> 4) + v = channels 4g .. 4g+3
+    // of the N tile (one 16-byte store).
+    // (the lane index from the execution mask, counted up from a zero the compiler cannot see before the loop: no register holds a
+    // thread index through the K loop for the stores)
+    unsigned zero;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zero));
+    const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero)), ge = lane_e >> 4, ie = lane_e & 15;
+    float* out = p.out + (size_t)ks * p.slab;
+    auto put = [&](auto f_tag, auto tm_tag, size_t pos, float sb) __attribute__((always_inline)) {
+        constexpr int F = decltype(f_tag)::value, TMI = decltype(tm_tag)::value;
+        float* dst = out + pos * p.Cout + co0 + wn * 32;
+#pragma unroll
+        for (int tn = 0; tn < 2; ++tn) {
+            // (component by component: a vector multiply would be packed fp32 arithmetic, which build.sh keeps out of the library)
+            const f32x4v a = acc[F][TMI][tn];
+            *reinterpret_cast<f32x4v*>(dst + 16 * tn + 4 * ge) = f32x4v{a[0] * sb, a[1] * sb, a[2] * sb, a[3] * sb};
+        }
+    };
+    auto rows = [&](auto tm_tag) __attribute__((always_inline)) {
+        constexpr int TMI = decltype(tm_tag)::value;
+        const int ru = r0 + 4 * wm + TMI, bu = ru / RP;
+        {
+            const int j = ie;                                          // tile column
+            // regular tile: stacked row r0 + patch row, image column n0 + j; fringe tile: tile column j is image column W of
+            // row block j >> 1 for odd j (even j: column W-1, which the regular tiles own), even-column parities only
+            int r = ru, bb = bu;                                        // (block-uniform branch: the regular tiles divide on the scalar ALU)
+            if (fringe) { r += 8 * (j >> 1); bb = r / RP; }
+            const int n = fringe ? p.W : n0 + j, m = r - bb * RP;
+            if (r >= R_total || (fringe && !(j & 1))) return;
+            const float sb = Gb[min(max(bb - b_lo, 0), p.up_ns - 1)];
+            auto phase = [&](auto f_tag) __attribute__((always_inline)) {
+                constexpr int F = decltype(f_tag)::value, FY = F >> 1, FX = F & 1;
+                if (m >= p.H + 1 - FY || n >= p.W + 1 - FX) return;
+                put(f_tag, tm_tag, ((size_t)bb * p.Ho + 2 * m + FY) * p.Wo + 2 * n + FX, sb);
+            };
+            phase(std::integral_constant<int, 0>{});
+            phase(std::integral_constant<int, 1>{});
+            phase(std::integral_constant<int, 2>{});
+            phase(std::integral_constant<int, 3>{});
+        }
+    };
+    rows(std::integral_constant<int, 0>{});
+    rows(std::integral_constant<int, 1>{});
+    rows(std::integral_constant<int, 2>{});
+    rows(std::integral_constant<int, 3>{});
+}
+
 template <int NP, int TM>
 static size_t bf16_lds_bytes(int cin) {
     constexpr int PH = 2 * TM * 32 / PW;
@@ -1075,6 +1355,18 @@ static int launch_up_one(const Plan& pl, int cin, hipStream_t s) {
     return HFAGP_OK;
 }
 
+// the 32-channel loop of the F16X3 up-conv (upconv_mfma16_takes)
+static int launch_up16(const Plan& pl, int cin, hipStream_t s) {
+    // (make_plan stages at most 8 samples and Cin <= 512: 57,376 B at the most, under the 64 KB a kernel gets without asking and
+    // two blocks per CU; the 16-channel loop above is the one that has to raise its limit)
+    static_assert(u16::lds_bytes(512, 8) <= 64 * 1024, "the 32-channel up-conv loop stays within the default dynamic LDS");
+    HFAGP_REQUIRE(cin <= 512 && pl.p.up_ns <= 8, HFAGP_EUNSUPPORTED, "modconv (merged up-conv, 32-channel loop): Cin=%d up_ns=%d",
+                  cin, pl.p.up_ns);
+    const size_t lds = u16::lds_bytes(cin, pl.p.up_ns);
+    upconv_bf16_kernel<4, 4, 0, 2><<<pl.grid, 256, lds, s>>>(pl.p);
+    return HFAGP_OK;
+}
+
 // fp16-storage variants (KD = 1 only): io = x_f16 | y_f16 << 1
 static int launch_up_io(const Plan& pl, int cin, int io, hipStream_t s) {
     const bool w8 = pl.up_waves == 8;
@@ -1103,9 +1395,11 @@ static auto with_kind(int kd, F&& f) {
 }
 
 int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
-    HFAGP_REQUIRE(a->Cin % CKB == 0 && (a->Cout % BNB == 0 || (a->Cout % BNB >= 96 && !pl.merged_up)), HFAGP_EUNSUPPORTED,
-                  "modconv (16-bit MFMA): Cin=%d must be a multiple of %d and Cout=%d of %d (or 96 mod 128, 512-B tail pad)",
-                  a->Cin, CKB, a->Cout, BNB);
+    // (the 4-wave block of the merged up-conv, both loops, tiles Cout in 64s; fp16 storage asks for 128 below)
+    HFAGP_REQUIRE(a->Cin % CKB == 0 && (a->Cout % BNB == 0 || (a->Cout % BNB >= 96 && !pl.merged_up) ||
+                                        (pl.merged_up && pl.up_waves == 4 && a->Cout % 64 == 0)), HFAGP_EUNSUPPORTED,
+                  "modconv (16-bit MFMA): Cin=%d must be a multiple of %d and Cout=%d of %d (or 96 mod 128, 512-B tail pad; the merged "
+                  "up-conv: of 64)", a->Cin, CKB, a->Cout, BNB);
     HFAGP_REQUIRE(pl.bn == BNB && pl.bm == 128, HFAGP_EUNSUPPORTED, "modconv (16-bit MFMA): unexpected plan");
     HFAGP_REQUIRE(a->Cin <= 512, HFAGP_EUNSUPPORTED, "modconv (16-bit MFMA): Cin=%d > 512 (style image in LDS)", a->Cin);
     const int kd = kind_of(a->precision);
@@ -1140,7 +1434,11 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
         HFAGP_REQUIRE(p.up_ns <= 1 || (long long)p.up_ns * a->x_batch_stride * (a->x_f16 ? 2 : 4) < (1ll << 32), HFAGP_EUNSUPPORTED,
                       "modconv (merged up-conv): %d samples of %lld elements exceed the 32-bit patch offsets", p.up_ns,
                       (long long)a->x_batch_stride);
-        const int rc = with_kind(kd, [&](auto k) { return launch_up<decltype(k)::value>(pl, a->Cin, s); });
+        // (the 32-channel loop marks a patch slot outside the images by the offset u16::OOB: the staged span must end below it)
+        const bool loop32 = pl.up_waves == 4 && upconv_mfma16_takes(a) &&
+                            (long long)p.up_ns * a->x_batch_stride * 4 <= (long long)u16::OOB;
+        const int rc = loop32 ? launch_up16(pl, a->Cin, s)
+                              : with_kind(kd, [&](auto k) { return launch_up<decltype(k)::value>(pl, a->Cin, s); });
         if (rc != HFAGP_OK) return rc;
         return check_launch("modconv_fwd (16-bit MFMA, merged up-conv)");
     }

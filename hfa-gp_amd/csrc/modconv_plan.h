@@ -255,4 +255,16 @@ static inline bool conv9_mfma16_takes(const HfagpModconvArgs* a) {
            a->Cin % 32 == 0 && a->Cin <= 512 && a->Cout % 128 == 0;
 }
 
+// The merged up-conv at F16X3 with fp32 storage runs the 32-channel 16x16x32 loop of upconv_bf16_kernel<4, 4, 0, 2> in its
+// 4-wave block (launch_modconv_bf16 checks the block and the staged span); f16, f16x2, the bf16 kinds, fp16 storage, Cin = 16 and
+// the 8-wave developer variant stay on the 16-channel loop.  No shape is excluded: at B = 32 all seven flagship layers, 4^2 to
+// 256^2, ran faster on it with the slowest new run below the fastest legacy run (profiles/r08_upconv16_ab.log; 0.89 - 0.97 per
+// layer).  Developer switch HFAGP_DEV_UP_LEGACY_LOOP=1: the 16-channel loop for these layers too (read at every call, so one
+// process can time both).
+static inline bool upconv_mfma16_takes(const HfagpModconvArgs* a) {
+    const char* dev = getenv("HFAGP_DEV_UP_LEGACY_LOOP");
+    return !(dev && atoi(dev) == 1) && a->precision == HFAGP_PREC_F16X3 && a->mode == HFAGP_CONVT3X3_UP2 && !a->x_f16 && !a->y_f16 &&
+           a->Cin % 32 == 0 && a->Cin <= 512 && a->Cout % 64 == 0;
+}
+
 }  // namespace hfagp
