@@ -168,6 +168,10 @@ class RaymarchBwdArgs(C.Structure):
                 ("df_scratch", C.c_void_p), ("rows_scratch", C.c_void_p), ("rows_scratch_bytes", C.c_uint64)]
 
 
+class RaymarchGeomGrads(C.Structure):
+    _fields_ = [("g_depth", C.c_void_p), ("g_wsum", C.c_void_p), ("depth_range", C.c_void_p)]
+
+
 # every symbol include/hfagp.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "hfagp_abi_version": (C.c_int, []),
@@ -209,6 +213,7 @@ SYMBOLS = {
     "hfagp_style_bwd": (C.c_int, [C.POINTER(StyleBwdArgs), C.c_void_p]),
     "hfagp_style_batch_bwd": (C.c_int, [C.POINTER(StyleBwdItem), C.c_int32, C.c_void_p]),
     "hfagp_raymarch_bwd": (C.c_int, [C.POINTER(RaymarchBwdArgs), C.c_void_p]),
+    "hfagp_raymarch_bwd_geom": (C.c_int, [C.POINTER(RaymarchBwdArgs), C.POINTER(RaymarchGeomGrads), C.c_void_p]),
     "hfagp_raymarch_bwd_rows_bytes": (C.c_size_t, [C.POINTER(RaymarchArgs)]),
     "hfagp_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "hfagp_adam_chunk": (C.c_int32, []),

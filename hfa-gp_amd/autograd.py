@@ -330,22 +330,29 @@ class SynthesisFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, ws, c, u_strat, u_imp, gen, *params):
+        return SynthesisFn._forward(ctx, False, ws, c, u_strat, u_imp, gen, params)
+
+    @staticmethod
+    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params):
         tape = {}
         ws_c = ws.detach().float().contiguous()
         with torch.no_grad():
-            img, rgb_raw, depth, planes, feat_img = gen._forward_impl(ws_c, c.detach().float().contiguous(), u_strat,
-                                                                      u_imp, tape)
+            img, rgb_raw, depth, planes, feat_img, *mask = gen._forward_impl(ws_c, c.detach().float().contiguous(), u_strat,
+                                                                             u_imp, tape, geometry)
         gen._last_extras = (planes, feat_img)        # for synthesis(return_planes=True)
         ctx.gen, ctx.tape, ctx.ws_c = gen, tape, ws_c
         ctx.params = params
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape = ws.shape
+        if geometry:
+            ctx.set_materialize_grads(False)         # an output the loss does not use hands backward None, not a zero image
+            return img, rgb_raw, depth, mask[0]
         ctx.mark_non_differentiable(depth)
         return img, rgb_raw, depth
 
     @staticmethod
     @torch.no_grad()
-    def backward(ctx, g_img, g_raw, _g_depth):
+    def backward(ctx, g_img, g_raw, g_depth, g_mask=None):
         gen, tape = ctx.gen, ctx.tape
         if tape is None:
             raise RuntimeError("TriPlaneGenerator.synthesis: backward called a second time — the saved activations "
@@ -376,6 +383,12 @@ class SynthesisFn(torch.autograd.Function):
         bw.finish_layer(c0rec0)
         # ---- renderer
         res = cfg.neural_rendering_resolution
+        geom = {}
+        if "depth_range" in tape:    # synthesis(geometry=True); without it image_depth is marked non-differentiable
+            if g_depth is not None:
+                geom.update(g_depth=g_depth.float().reshape(b, res * res).contiguous(), depth_range=tape["depth_range"])
+            if g_mask is not None:
+                geom.update(g_wsum=g_mask.float().reshape(b, res * res).contiguous())
         net = gen.decoder.net
         dec_prm = (net["0"].weight, net["0"].bias, net["2"].weight, net["2"].bias)
         # (the kernel's ~9 M end-of-kernel atomics landing in the .grad slices themselves — `dec_out` — instead of four fresh zeroed
@@ -387,7 +400,7 @@ class SynthesisFn(torch.autograd.Function):
                         u_strat=tape["u_strat"], u_imp=tape["u_imp"], decoder_grads=ctx.pg,
                         planes_absmax=tape.get("planes_absmax"), state=tape.get("ray_state"),
                         dec_out=tuple(p.grad for p in dec_prm) if dec_direct else None,
-                        **gen._render_args(tape["c"]))
+                        **geom, **gen._render_args(tape["c"]))
         if ctx.pg:
             d_planes, dec = rb
             for prm, g in zip(dec_prm, dec):
@@ -418,3 +431,11 @@ class SynthesisFn(torch.autograd.Function):
         ctx.tape = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
         return (d_ws, None, None, None, None) + pgrads
+
+
+class SynthesisGeomFn(SynthesisFn):
+    """`synthesis(geometry=True)`: outputs image, image_raw, image_depth, image_mask; the gradients of the last two join the
+    compositing adjoint of the ray marcher (ops.raymarch_bwd g_depth / g_wsum)."""
+    @staticmethod
+    def forward(ctx, ws, c, u_strat, u_imp, gen, *params):
+        return SynthesisFn._forward(ctx, True, ws, c, u_strat, u_imp, gen, params)

@@ -329,7 +329,7 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
         // ---- backward only: P_j = sum_c 2 dL/dfeat[c] * colour_j[c]
         float gsum2 = 0.f;
         if constexpr (GRADS) {
-            if (lane < 32) lds.g2[lane] = 2.f * p.g_feat[(size_t)ray * 32 + lane];
+            if (lane < 32) lds.g2[lane] = p.g_feat ? 2.f * p.g_feat[(size_t)ray * 32 + lane] : 0.f;
             WAVE_SYNC();
             gsum2 = wave_sum(lane < 32 ? lds.g2[lane] : 0.f);
 #pragma unroll
@@ -389,6 +389,7 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
             if constexpr (GRADS) {
                 // adjoint of the compositing.  rgb = sum_e w_e cbar_e (+ white_back term),
                 //   G_e = g . cbar_e - wb * sum(g),   dL/dalpha_e = G_e T_e - (sum_{k>e} G_k w_k) / (1 - alpha_e + eps)
+                //   with depth / opacity gradients (hfagp.h HfagpRaymarchGeomGrads):  G_e += gamma_W + gamma_d (tbar_e - d) / W
                 //   dalpha/dsigma~ = delta (1 - alpha),  dsigma~/dsigmabar = sigmoid(sigmabar - 1)
                 const float wb = a.white_back ? gsum2 : 0.f;
                 float G[2];
@@ -396,6 +397,21 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
                 for (int k = 0; k < 2; ++k) {
                     const int e = lane + 64 * k;
                     G[k] = e < S - 1 ? 0.5f * (lds.pp[lds.sid[e]] + lds.pp[lds.sid[e + 1]]) - wb : 0.f;
+                }
+                if (p.g_depth || p.g_wsum) {          // (wave-uniform; the image-only call never enters)
+                    // W = sum w_e, d = D / W = sum w_e tbar_e / W with the sample depths constant: dW/dw_e = 1, dd/dw_e = (tbar_e - d) / W.
+                    // The forward maps a NaN d (W == 0) to inf and clamps d to the batch-global [lo, hi]: no depth gradient where W == 0,
+                    // d is not finite or d lies outside [lo, hi] (the comparisons are false for NaN; no 0 * inf is formed).
+                    const float gW = p.g_wsum ? p.g_wsum[ray] : 0.f;
+                    float gD = 0.f;
+                    const float d = dsum / wsum;       // (the forward's expression: the same side of the clamp)
+                    if (p.g_depth) {
+                        const float lo = p.depth_range[0], hi = p.depth_range[1];
+                        if (wsum > 0.f && fabsf(d) < INFINITY && d >= lo && d <= hi) gD = p.g_depth[ray] / wsum;
+                    }
+#pragma unroll
+                    for (int k = 0; k < 2; ++k)
+                        if (lane + 64 * k < S - 1) G[k] += gW + (gD != 0.f ? gD * (tm[k] - d) : 0.f);
                 }
                 const float gw0 = G[0] * w0, gw1 = G[1] * w1;
                 const float inc0 = wave_scan_add(gw0, lane), inc1 = wave_scan_add(gw1, lane);

@@ -145,7 +145,7 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
         r.rec = *reinterpret_cast<const float4*>(p.rec + ((size_t)r.ray * S + 16 * tt + j) * 4);
         r.zq = p.rec[((size_t)r.ray * S + 16 * tt + (lane >> 2)) * 4];
 #pragma unroll
-        for (int ot = 0; ot < 2; ++ot) r.gf[ot] = *reinterpret_cast<const float4*>(p.g_feat + (size_t)r.ray * 32 + 16 * ot + 4 * g);
+        for (int ot = 0; ot < 2; ++ot) r.gf[ot] = load_g_feat4(p, (size_t)r.ray * 32 + 16 * ot + 4 * g);
         if (ro.dfs) r.slots = load_df_slots(ro, (size_t)r.ray * S + 16 * tt + j);
         return r;
     };
@@ -231,7 +231,7 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
             rayw = __builtin_amdgcn_readfirstlane(bw * R + pi * a.res + pj);
             ray_setup(a, bw, pi, pj, o3w, d3w);
 #pragma unroll
-            for (int ot = 0; ot < 2; ++ot) gfw[ot] = *reinterpret_cast<const float4*>(p.g_feat + (size_t)rayw * 32 + 16 * ot + 4 * g);
+            for (int ot = 0; ot < 2; ++ot) gfw[ot] = load_g_feat4(p, (size_t)rayw * 32 + 16 * ot + 4 * g);
             zqw = p.rec[((size_t)rayw * S + 16 * tt + (lane >> 2)) * 4];
         }
         b = bw; ray = rayw;
@@ -583,7 +583,7 @@ raymarch_bwd_cols_kernel(const RayParams p, float* __restrict__ d_planes, const 
                 f32x4 dO[2];
 #pragma unroll
                 for (int ot = 0; ot < 2; ++ot) {
-                    const float4 gf = *reinterpret_cast<const float4*>(p.g_feat + (size_t)ray * 32 + 16 * ot + 4 * g);
+                    const float4 gf = load_g_feat4(p, (size_t)ray * 32 + 16 * ot + 4 * g);
                     const float gv[4] = {gf.x, gf.y, gf.z, gf.w};
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -836,7 +836,7 @@ raymarch_bwd_df_kernel(const RayParams p, float* __restrict__ df_out, const Rows
         ray_setup(a, b, pi, pj, o3, d3);
         float4 gfeat[2];
 #pragma unroll
-        for (int ot = 0; ot < 2; ++ot) gfeat[ot] = *reinterpret_cast<const float4*>(p.g_feat + (size_t)ray * 32 + 16 * ot + 4 * g);
+        for (int ot = 0; ot < 2; ++ot) gfeat[ot] = load_g_feat4(p, (size_t)ray * 32 + 16 * ot + 4 * g);
         // the depth the gather of a tile hangs on is loaded a tile ahead (the chain  depth -> taps -> 24 texel loads -> decoder
         // is what a wave waits on: two waves per SIMD hide one of its two memory round trips, not both)
         float zq = p.rec[((size_t)ray * S + (lane >> 2)) * 4];
@@ -1209,11 +1209,23 @@ static int launch_cols(unsigned blocks, size_t lds, const RayParams& p, float* d
 using namespace hfagp;
 
 extern "C" int hfagp_raymarch_bwd(const HfagpRaymarchBwdArgs* a, void* stream) {
-    HFAGP_REQUIRE(a && a->g_feat && a->d_planes && a->rec, HFAGP_EBADARG, "raymarch_bwd: null pointer");
+    return hfagp_raymarch_bwd_geom(a, nullptr, stream);
+}
+
+extern "C" int hfagp_raymarch_bwd_geom(const HfagpRaymarchBwdArgs* a, const HfagpRaymarchGeomGrads* geom, void* stream) {
+    HFAGP_REQUIRE(a && a->d_planes && a->rec, HFAGP_EBADARG, "raymarch_bwd: null pointer");
+    const float* g_depth = geom ? geom->g_depth : nullptr;
+    const float* g_wsum = geom ? geom->g_wsum : nullptr;
+    HFAGP_REQUIRE(a->g_feat || g_depth || g_wsum, HFAGP_EBADARG,
+                  "raymarch_bwd: no upstream gradient (g_feat, g_depth and g_wsum are all null)");
+    HFAGP_REQUIRE(!g_depth || geom->depth_range, HFAGP_EBADARG, "raymarch_bwd: g_depth needs depth_range");
     RayParams p;
     int rc = fill_ray_params(&a->fwd, p, "raymarch_bwd");
     if (rc != HFAGP_OK) return rc;
     p.g_feat = a->g_feat;
+    p.g_depth = g_depth;
+    p.g_wsum = g_wsum;
+    p.depth_range = g_depth ? geom->depth_range : nullptr;
     p.rec = a->rec;
     hipStream_t s = (hipStream_t)stream;
     rc = launch_raymarch(p, true, s);

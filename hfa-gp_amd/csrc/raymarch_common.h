@@ -16,7 +16,9 @@ struct RayParams {
     float delta;         // float( (end - start) / (Sc - 1) )        [python double -> fp32]
     float coord_scale;   // 2 / box_warp
     int total_rays;
-    const float* g_feat; // backward only: [B][R][32]
+    const float* g_feat; // backward only: [B][R][32]; null = zeros (a geometry gradient alone)
+    const float* g_depth, *g_wsum;   // backward only, optional: [B][R] dL/d (clamped depth), dL/d opacity (hfagp.h HfagpRaymarchGeomGrads)
+    const float* depth_range;        // with g_depth: 2 floats on the device, the batch-global clamp range of the depth
     float* rec;          // backward only: per-sample records [B*R][S][4] = (depth, omega, d sigma, -)
 };
 
@@ -36,11 +38,17 @@ inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char*
     HFAGP_REQUIRE(total < (1ll << 31), HFAGP_EUNSUPPORTED, "%s: too many rays", who);
     p.total_rays = (int)total;
     p.g_feat = nullptr;
+    p.g_depth = p.g_wsum = p.depth_range = nullptr;
     p.rec = nullptr;
     return HFAGP_OK;
 }
 
 int launch_raymarch(const RayParams& p, bool grads, hipStream_t s);   // raymarch.hip
+
+// 4 channels of a ray's dL/dfeat for pass 2 of the backward (off = ray * 32 + channel); no image gradient = zeros
+__device__ __forceinline__ float4 load_g_feat4(const RayParams& p, size_t off) {
+    return p.g_feat ? *reinterpret_cast<const float4*>(p.g_feat + off) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
 
 // sort + gather form of the backward pass 2 (raymarch_rows.hip): where the dL/dF producers write a sample's line
 struct RowsOut {

@@ -716,17 +716,18 @@ class TriPlaneGenerator(nn.Module):
             raise ValueError(f"expected ws [B,{cfg.num_ws},{cfg.w_dim}] and c [B,{cfg.c_dim}], got "
                              f"{tuple(ws.shape)} and {tuple(c.shape)}")
 
-    def _forward_impl(self, ws, c, u_strat, u_imp, tape):
-        """ws, c: detached contiguous fp32 CUDA tensors.  Returns image, image_raw, depth, planes, feat_img;
-        when `tape` is a dict it is filled with everything the backward pass needs."""
+    def _forward_impl(self, ws, c, u_strat, u_imp, tape, geometry=False):
+        """ws, c: detached contiguous fp32 CUDA tensors.  Returns image, image_raw, depth, planes, feat_img — and, with
+        `geometry`, the opacity image [B,1,r,r] as a sixth; when `tape` is a dict it is filled with everything the backward
+        pass needs."""
         self._refresh_tuned(tape is not None)
         self._in_forward = True          # (backbone_planes / superres below must not rebuild the images a second time)
         try:
-            return self._forward_body(ws, c, u_strat, u_imp, tape)
+            return self._forward_body(ws, c, u_strat, u_imp, tape, geometry)
         finally:
             self._in_forward = False
 
-    def _forward_body(self, ws, c, u_strat, u_imp, tape):
+    def _forward_body(self, ws, c, u_strat, u_imp, tape, geometry=False):
         cfg = self.cfg
         b = ws.shape[0]
         res = cfg.neural_rendering_resolution
@@ -749,35 +750,51 @@ class TriPlaneGenerator(nn.Module):
         if tape is not None:
             tape.update(backbone=bb_tape, sr=sr_tape, planes=planes, c=c, u_strat=u_strat, u_imp=u_imp,
                         feat_img=feat_img, batch=b, planes_absmax=pam, ray_state=ray_state)
+            if geometry:      # the clamp range of the depth, for its adjoint (autograd.SynthesisFn.backward)
+                tape["depth_range"] = ops.depth_range(tmm)
+        if geometry:
+            return img, rgb_raw, depth.view(b, 1, res, res), planes, feat_img, wsum.view(b, 1, res, res)
         return img, rgb_raw, depth.view(b, 1, res, res), planes, feat_img
 
     def synthesis(self, ws: torch.Tensor, c: torch.Tensor, noise_mode: str = "const",
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
-                  return_planes: bool = False, **_unused) -> Dict[str, torch.Tensor]:
+                  return_planes: bool = False, geometry: bool = False, **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
-        HFA-GP) and w.r.t. the generator parameters that require grad (after `tune_generator()`)."""
+        HFA-GP) and w.r.t. the generator parameters that require grad (after `tune_generator()`).
+        `geometry=True`: the dict also has 'image_mask' [B,1,r,r] (the per-ray opacity, sum of the compositing weights), and
+        'image_depth' and 'image_mask' are differentiable — silhouette / matting losses and depth priors reach `ws` and the
+        generator.  Off (the default), 'image_depth' carries no gradient and the dict has EG3D's three keys."""
         self._check_inputs(ws, c, noise_mode)
         if ws.shape[0] == 0:          # empty batch (ragged last batch of a frame shard): nothing to launch
             cfg, dev = self.cfg, ws.device
             r = cfg.neural_rendering_resolution
             out = {"image": torch.zeros(0, cfg.img_channels, cfg.img_resolution, cfg.img_resolution, device=dev),
                    "image_raw": torch.zeros(0, 3, r, r, device=dev), "image_depth": torch.zeros(0, 1, r, r, device=dev)}
+            if geometry:
+                out["image_mask"] = torch.zeros(0, 1, r, r, device=dev)
             out["image"] = out["image"] + 0.0 * ws.sum()          # keeps the autograd edge to ws
             return out
         params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
         need_grad = torch.is_grad_enabled() and (ws.requires_grad or any(p.requires_grad for p in params))
         if need_grad:
             from .autograd import SynthesisFn
-            img, rgb_raw, depth = SynthesisFn.apply(ws, c.detach(), u_strat, u_imp, self, *params)
-            out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
+            if geometry:
+                from .autograd import SynthesisGeomFn
+                img, rgb_raw, depth, mask = SynthesisGeomFn.apply(ws, c.detach(), u_strat, u_imp, self, *params)
+                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth, "image_mask": mask}
+            else:
+                img, rgb_raw, depth = SynthesisFn.apply(ws, c.detach(), u_strat, u_imp, self, *params)
+                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
             if return_planes:
                 out["planes"], out["feature_image"] = self._last_extras
             self._last_extras = None
             return out
         with torch.no_grad():
-            img, rgb_raw, depth, planes, feat_img = self._forward_impl(
-                ws.detach().float().contiguous(), c.detach().float().contiguous(), u_strat, u_imp, None)
+            img, rgb_raw, depth, planes, feat_img, *mask = self._forward_impl(
+                ws.detach().float().contiguous(), c.detach().float().contiguous(), u_strat, u_imp, None, geometry)
         out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
+        if geometry:
+            out["image_mask"] = mask[0]
         if return_planes:
             out["planes"] = planes
             out["feature_image"] = feat_img

@@ -1196,13 +1196,26 @@ def rows_scratch_cap(device=None) -> int:
     return cap
 
 
-def raymarch_bwd(g_feat: torch.Tensor, planes: torch.Tensor, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0,
+def depth_range(tminmax: torch.Tensor) -> torch.Tensor:
+    """tminmax [..., 2] as `raymarch` writes it → [2] device tensor (lo, hi): the batch-global range `depth_clamp_` clamps the
+    expected depth to, for `raymarch_bwd(g_depth=..., depth_range=...)`.  No host sync."""
+    _chk(tminmax, "tminmax")
+    t = tminmax.reshape(-1, 2)
+    return torch.stack((t[:, 0].amin(), t[:, 1].amax()))
+
+
+def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0,
                  dec_w1, dec_b1, res: int, ray_start: float, ray_end: float, box_warp: float,
                  decoder_lr_mul: float = 1.0, plane_axes: int = 0, white_back: bool = False,
                  return_rec: bool = False, decoder_grads: bool = False, decoder_precision: str = "f16x3",
                  planes_absmax: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
-                 two_kernel: bool = False, rows: Optional[bool] = None, dec_out=None, _out=None):
-    """g_feat [B,R,32] → d planes [B,3,H,W,32].  ``state``: what the forward call of this step left behind
+                 two_kernel: bool = False, rows: Optional[bool] = None, dec_out=None, _out=None,
+                 g_depth: Optional[torch.Tensor] = None, g_wsum: Optional[torch.Tensor] = None,
+                 depth_range: Optional[torch.Tensor] = None):
+    """g_feat [B,R,32] → d planes [B,3,H,W,32].  ``g_depth`` / ``g_wsum`` [B,R]: gradients w.r.t. the CLAMPED expected depth and
+    the opacity `raymarch` returns, added to the compositing adjoint (hfagp.h HfagpRaymarchGeomGrads); ``depth_range``
+    (`ops.depth_range(tminmax)`, required with g_depth) is the forward's batch-global clamp range; g_feat may be None when one of
+    the two is given.  ``state``: what the forward call of this step left behind
     (`raymarch(..., state=)`): the compositing adjoint reads it instead of recomputing.  ``rows``: pass 2 as sort + gather
     (hfagp.h `rows_scratch`, csrc/raymarch_rows.hip) — None = whenever it applies (HFAGP_RAYBWD_ROWS=0 turns the default off: A/B
     timing), False = the scatter kernels.  The sort's scratch (~0.9 GB per frame at 128^2 rays x 96 samples) is bounded by
@@ -1210,10 +1223,17 @@ def raymarch_bwd(g_feat: torch.Tensor, planes: torch.Tensor, cam2world, intrinsi
     kernels above 16 GiB, i.e. from B = 19 on, without a word); where the sort does not apply at all (more than 8192 bins per frame)
     or its scratch cannot be allocated, the scatter kernels run and say so once."""
     _chk(planes, "planes")
-    _chk(g_feat, "g_feat")
     b, _, h, w, _ = planes.shape
     r = res * res
     sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    geom = g_depth is not None or g_wsum is not None or depth_range is not None
+    if g_feat is not None:
+        _chk(g_feat, "g_feat")
+    for t, name in ((g_depth, "g_depth"), (g_wsum, "g_wsum")):
+        if t is not None and _chk(t, name).shape != (b, r):
+            raise RuntimeError(f"raymarch_bwd: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
+    if depth_range is not None and _chk(depth_range, "depth_range").shape != (2,):
+        raise RuntimeError(f"raymarch_bwd: depth_range must be [2] (ops.depth_range), got {tuple(depth_range.shape)}")
     if _out is not None:
         d_planes, rec = _out
     else:
@@ -1234,6 +1254,10 @@ def raymarch_bwd(g_feat: torch.Tensor, planes: torch.Tensor, cam2world, intrinsi
             raise RuntimeError(f"raymarch_bwd: state must be [B, R, {(sc + sf) * 35}], got {tuple(state.shape)}")
         f.state = _ptr(_chk(state, "state"))
     a.g_feat, a.d_planes, a.rec = _ptr(g_feat), _ptr(d_planes), _ptr(rec)
+    gg = None
+    if geom:
+        gg = L.RaymarchGeomGrads()
+        gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
     # pass 2 as two kernels (dL/dF through a scratch buffer, then the scatter alone: hfagp.h `df_scratch`) where the column
     # variant applies; 201 MB per frame at 128^2 rays x 96 samples.  OFF by default: measured SLOWER than the fused kernel
     # (B = 2: dL/dF 0.51 ms + scatter 1.41 ms against 1.58 ms fused — the scatter alone is the bound, the arithmetic already
@@ -1252,10 +1276,12 @@ def raymarch_bwd(g_feat: torch.Tensor, planes: torch.Tensor, cam2world, intrinsi
                 dec_out = tuple(torch.zeros_like(t) for t in (dec_w0, dec_b0, dec_w1, dec_b1))
             for b0 in range(0, b, nb):
                 b1 = min(b, b0 + nb)
-                raymarch_bwd(g_feat[b0:b1], planes[b0:b1], cam2world[b0:b1], intrinsics[b0:b1], u_strat[b0:b1], u_imp[b0 * r:b1 * r],
+                raymarch_bwd(None if g_feat is None else g_feat[b0:b1], planes[b0:b1], cam2world[b0:b1], intrinsics[b0:b1], u_strat[b0:b1], u_imp[b0 * r:b1 * r],
                              dec_w0, dec_b0, dec_w1, dec_b1, res, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back,
                              False, decoder_grads, decoder_precision, planes_absmax, None if state is None else state[b0:b1],
-                             two_kernel, rows, dec_out, _out=(d_planes[b0:b1], rec[b0:b1]))
+                             two_kernel, rows, dec_out, _out=(d_planes[b0:b1], rec[b0:b1]),
+                             g_depth=None if g_depth is None else g_depth[b0:b1],
+                             g_wsum=None if g_wsum is None else g_wsum[b0:b1], depth_range=depth_range)   # (the range is batch-global)
             ROWS_STATS.update(bytes=min(need, cap), chunks=-(-b // nb), path="rows")
             if decoder_grads:
                 return d_planes, tuple(dec_out)
@@ -1284,7 +1310,10 @@ def raymarch_bwd(g_feat: torch.Tensor, planes: torch.Tensor, cam2world, intrinsi
             if t.shape != like.shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
                 raise RuntimeError("raymarch_bwd: dec_out must be four contiguous fp32 device tensors shaped like the decoder parameters")
         a.d_dec_w0, a.d_dec_b0, a.d_dec_w1, a.d_dec_b1 = (_ptr(t) for t in dec)
-    L.check(L.lib().hfagp_raymarch_bwd(C.byref(a), _stream()), "raymarch_bwd")
+    if gg is None:
+        L.check(L.lib().hfagp_raymarch_bwd(C.byref(a), _stream()), "raymarch_bwd")
+    else:
+        L.check(L.lib().hfagp_raymarch_bwd_geom(C.byref(a), C.byref(gg), _stream()), "raymarch_bwd")
     if decoder_grads:
         return d_planes, dec
     return (d_planes, rec) if return_rec else d_planes

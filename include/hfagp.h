@@ -37,6 +37,7 @@
  *                              (code/trainer_rgb.py:56, code/trainer_3dmm.py:29, code/trainer_audio.py:30-34; NCCL group: code/train_rgb.py:57)
  * backward (the reference gets these from torch.autograd through EG3D's custom ops; g_loss.backward(), code/trainer_rgb.py:93):
  *   hfagp_raymarch_bwd      <- autograd of the renderer: grid_sample / decoder / compositing adjoints
+ *   hfagp_raymarch_bwd_geom <- the same with gradients of the expected depth and the opacity (silhouette / depth losses)
  *   hfagp_modconv_fwd modes HFAGP_CONV3X3_BWD / HFAGP_CONVS2_BWD <- conv2d_gradfix data gradients (the same GEMM kernel)
  *   hfagp_conv_wgrad (+ _workspace_bytes) <- conv2d_gradfix weight gradients
  *   hfagp_pointwise_bwd     <- bias_act backward + noise-strength / bias gradients + demodulation adjoint of a SynthesisLayer
@@ -611,6 +612,26 @@ typedef struct {
 } HfagpRaymarchBwdArgs;
 
 int hfagp_raymarch_bwd(const HfagpRaymarchBwdArgs* a, void* stream);
+
+/* Depth and opacity gradients through the same backward (additive to ABI 15: HfagpRaymarchBwdArgs keeps its layout).
+ * With the kernel's notation — midpoints e = 0 .. S-2 of the depth-sorted samples, compositing weights w_e = alpha_e T_e,
+ * midpoint depths tbar_e, W = sum_e w_e (the `wsum` output), D = sum_e w_e tbar_e, d = D / W (the `depth` output) — the
+ * per-midpoint adjoint that pass 1 forms becomes
+ *     G_e = dL/dw_e = g . cbar_e  -  white_back * sum(g)  +  gamma_W  +  gamma_d * (tbar_e - d) / W
+ * gamma_W = g_wsum[ray].  gamma_d = g_depth[ray] taken back through what follows d in the forward (NaN -> inf, then the clamp
+ * to the batch-global range [lo, hi] = depth_range): it is 0 where W == 0, where d is not finite and where d lies outside
+ * [lo, hi] (a depth ON a bound passes, as torch.clamp's gradient does).  The sample depths carry no gradient (stratified
+ * depths come from the uniforms, importance depths are detached as in EG3D), so everything after G_e — d alpha, d sigma, the
+ * per-sample records, all of pass 2 — is what the image gradient alone goes through.
+ * hfagp_raymarch_bwd(a, s) == hfagp_raymarch_bwd_geom(a, NULL, s).  a->g_feat may be NULL (zeros) when g_depth or g_wsum is
+ * given.  HFAGP_EBADARG, nothing launched: g_depth without depth_range; no upstream gradient at all.                        */
+typedef struct {
+    const float* g_depth;      /* [B][R] dL/d image_depth (the CLAMPED depth), or NULL            */
+    const float* g_wsum;       /* [B][R] dL/d opacity, or NULL                                     */
+    const float* depth_range;  /* 2 floats ON THE DEVICE: the batch-global clamp range lo, hi;    */
+                               /* required with g_depth                                            */
+} HfagpRaymarchGeomGrads;
+int hfagp_raymarch_bwd_geom(const HfagpRaymarchBwdArgs* a, const HfagpRaymarchGeomGrads* g, void* stream);
 /* bytes of HfagpRaymarchBwdArgs::rows_scratch for this forward configuration (B, H, W, res, Sc, Sf, plane_axes are read);
  * 0 = the sort + gather form does not apply (more than 8192 bins per frame: planes beyond ~256 x 341 texels, or more than
  * 2^31 slots): leave rows_scratch NULL.  At 2 frames x 128^2 rays x 96 samples on mirrored 256^2 planes: 1.8 GB.            */

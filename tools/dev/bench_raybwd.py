@@ -1,5 +1,7 @@
 """Developer timing of the ray-march backward (GPU box): sort + gather form (rows) against the scatter kernels.
-usage: bench_raybwd.py [B] [iters] [rows|cols|both] [dec]"""
+usage: bench_raybwd.py [B] [iters] [rows|cols|both] [dec] [state] [geom]
+state: the compositing adjoint reads the forward's per-sample state (what a fitting step does); geom: depth and opacity gradients
+(g_depth, g_wsum) beside g_feat."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -11,7 +13,8 @@ from hfa_gp_amd.generator import TriPlaneGenerator
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 2
 iters = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 which = sys.argv[3] if len(sys.argv) > 3 else "both"
-dec = len(sys.argv) > 4 and sys.argv[4] == "dec"
+dec = "dec" in sys.argv[4:]
+use_state, geom = "state" in sys.argv[4:], "geom" in sys.argv[4:]
 dev = torch.device("cuda:0")
 cfg = ffhq512_128()
 gen = TriPlaneGenerator(cfg, seed=0).to(dev)
@@ -24,9 +27,18 @@ with torch.no_grad():
     g = torch.randn(B, 128 * 128, 32, device=dev)
     kw = gen._render_args(c)
     pam = getattr(gen, "_planes_absmax", None)
+    extra = {}
+    if use_state or geom:
+        st = ops.raymarch_state(B, 128, cfg.depth_resolution, cfg.depth_resolution_importance, dev) if use_state else None
+        tmm = ops.raymarch(planes, u_strat=u_s, u_imp=u_i, planes_absmax=pam, state=st, **kw)[3]
+        if use_state:
+            extra["state"] = st
+        if geom:
+            extra.update(g_depth=torch.randn(B, 128 * 128, device=dev), g_wsum=torch.randn(B, 128 * 128, device=dev),
+                         depth_range=ops.depth_range(tmm))
     res = {}
     for rows in {"rows": (True,), "cols": (False,), "both": (False, True, False, True)}[which]:
-        call = lambda: ops.raymarch_bwd(g, planes, u_strat=u_s, u_imp=u_i, planes_absmax=pam, rows=rows, decoder_grads=dec, **kw)
+        call = lambda: ops.raymarch_bwd(g, planes, u_strat=u_s, u_imp=u_i, planes_absmax=pam, rows=rows, decoder_grads=dec, **extra, **kw)
         for _ in range(2):
             call()
         torch.cuda.synchronize()
@@ -38,7 +50,7 @@ with torch.no_grad():
         torch.cuda.synchronize()
         res[rows] = d
         dp = d[0] if dec else d
-        print(f"raymarch_bwd B={B} rows={rows} dec={dec}: {e0.elapsed_time(e1)/iters:.3f} ms/call ({e0.elapsed_time(e1)/iters/B:.3f} ms/frame), "
+        print(f"raymarch_bwd B={B} rows={rows} dec={dec} state={use_state} geom={geom}: {e0.elapsed_time(e1)/iters:.3f} ms/call ({e0.elapsed_time(e1)/iters/B:.3f} ms/frame), "
               f"checksum {dp.double().abs().sum().item():.4f}")
     if len(res) == 2:
         a, b = (res[True][0], res[False][0]) if dec else (res[True], res[False])
