@@ -31,6 +31,7 @@ for src in elementwise modconv modconv_bf16 smallconv upconv_fir upfir_lean torg
 # units added since ABI 13 (tests/test_kernel_resources.py pins the list above; tests/test_shape_cpu.py holds these to its checks)
 units+=(planes_query)
 units+=(marching_cubes)
+units+=(weight_prep)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

@@ -32,17 +32,8 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
     constexpr bool XH = (IO & 1) != 0, YH = (IO & 2) != 0;
     constexpr int XB = XH ? 2 : 4;                       // bytes per input element
     static_assert(IO == 0 || KD == 1, "fp16 storage goes with the single-pass fp16 arithmetic");
-#ifndef HFAGP_WAVES_N
-#define HFAGP_WAVES_N 2
-#endif
-#ifndef HFAGP_LOADA_EARLY
-#define HFAGP_LOADA_EARLY 1
-#endif
-#ifndef HFAGP_B_EARLY
-#define HFAGP_B_EARLY 1
-#endif
     // wave grid WM x WN over the 128 x 128 block tile; TM here is the M tiles per wave for WN = 2
-    constexpr int WN = HFAGP_WAVES_N, WM = 4 / WN, TN = 4 / WN, TMW = 4 / WM, BM = 128, PH = BM / PW;
+    constexpr int WN = 2, WM = 4 / WN, TN = 4 / WN, TMW = 4 / WM, BM = 128, PH = BM / PW;
     static_assert(TM == 2, "block tile is 128 positions");
     constexpr int LPWB = RowPitch<NP>::value;
     constexpr int APOS = (PH + 2) * LPWB;                 // positions of the staged patch
@@ -102,41 +93,11 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
         amask[k] = inside ? sdown : 0.f;          // zero padding and the fp16 range guard in one factor
         soff[k] = 4 * q;
     }
-    auto load_a = [&](int chunk) __attribute__((always_inline)) {
-        const char* xc = xb + (long long)chunk * (CKB * XB);
-#pragma unroll
-        for (int k = 0; k < A_PER_T; ++k) {
-            if constexpr (XH) {
-                const uint2 u = *reinterpret_cast<const uint2*>(xc + aoff[k]);
-                ra[k].x = __builtin_bit_cast(float, u.x);
-                ra[k].y = __builtin_bit_cast(float, u.y);
-            } else {
-                ra[k] = *reinterpret_cast<const float4*>(xc + aoff[k]);
-            }
-        }
-    };
+    auto load_a = [&](int chunk) __attribute__((always_inline)) { a16_load<XH>(ra, xb, chunk, aoff); };
     // slot K of the staged patch of `chunk`: scale by the style, split, write the parts to LDS buffer BUF
     auto store_a = [&](int chunk, auto buf_tag, auto k_tag) __attribute__((always_inline)) {
         constexpr int BUF = decltype(buf_tag)::value, k = decltype(k_tag)::value;
-        {
-            const float m = amask[k];
-            const float4 sv = *reinterpret_cast<const float4*>(Ss + chunk * CKB + soff[k]);
-            uint2 parts[NP];
-            if constexpr (XH) {
-                // fp16 storage: the halves are the operand already; the style (|s| <= 1 after the range guard, |x| <= the
-                // layer's clamp) goes on with two packed fp16 multiplies, as EG3D's fp16 blocks do
-                const f32x2 s01 = {sv.x * m, sv.y * m}, s23 = {sv.z * m, sv.w * m};
-                const f16x2 x01 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, ra[k].x));
-                const f16x2 x23 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, ra[k].y));
-                parts[0] = make_uint2(__builtin_bit_cast(unsigned, x01 * __builtin_convertvector(s01, f16x2)),
-                                      __builtin_bit_cast(unsigned, x23 * __builtin_convertvector(s23, f16x2)));
-            } else
-            split4<KD>(make_float4(ra[k].x * (sv.x * m), ra[k].y * (sv.y * m), ra[k].z * (sv.z * m),
-                                   ra[k].w * (sv.w * m)), parts);     // (F16X2: one saturating fp16 part)
-#pragma unroll
-            for (int q = 0; q < NP; ++q)
-                *reinterpret_cast<uint2*>(As + BUF * A_BUF + q * A_PART + lds_a[k]) = parts[q];
-        }
+        a16_store<KD, XH>(As + BUF * A_BUF, A_PART, lds_a[k], amask[k], *reinterpret_cast<const float4*>(Ss + chunk * CKB + soff[k]), ra[k]);
     };
 
     // ---- B operand: straight from global/L2 into the fragment registers (no LDS, no barrier): a lane's fragment
@@ -187,22 +148,17 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
 
-    // part products in the order they are issued: (A part, B part)
-    constexpr int NPROD = kind_nprod(KD);
-    constexpr int PA[6] = {kind_pa(KD, 0), kind_pa(KD, 1), kind_pa(KD, 2), kind_pa(KD, 3), kind_pa(KD, 4), kind_pa(KD, 5)};
-    constexpr int PB[6] = {kind_pb(KD, 0), kind_pb(KD, 1), kind_pb(KD, 2), kind_pb(KD, 3), kind_pb(KD, 4), kind_pb(KD, 5)};
+    constexpr PartOrder PO = kind_order(KD);
+    constexpr int NPROD = PO.nprod;
 
     // the K loop for a compile-time tap count NT (9: 3x3, 4/2/1: the phases of the stride-2 transposed conv and
     // the 1x1 conv).  U chunks are unrolled so that U*NT is a multiple of the ring size: every item then has a
     // compile-time ring slot and the whole group is straight-line code.
     auto run = [&](auto nt_tag) __attribute__((always_inline)) {
         constexpr int NT = decltype(nt_tag)::value;
-        constexpr bool EARLY_A = HFAGP_LOADA_EARLY && NT == 9;
-#ifndef HFAGP_RB9
-#define HFAGP_RB9 3
-#endif
+        constexpr bool EARLY_A = NT == 9;
         // ring size: divides U*NT (the single-pass fp16 mode has a third of the MFMA time per item: deeper ring)
-        constexpr int RB = NT == 9 ? (NPROD == 1 ? 6 : HFAGP_RB9) : NT == 4 ? 4 : 2;
+        constexpr int RB = NT == 9 ? (NPROD == 1 ? 6 : 3) : NT == 4 ? 4 : 2;
         constexpr int U = 2;                                   // chunk pairs: chunk parity = A buffer = compile time
         u32x4 bq[RB][TN][NPB];
         // loads of item (chunk c, tap t) into ring slot `slot`; c is clamped so that the look-ahead past the last
@@ -243,14 +199,12 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
             // (sched_barrier: without it the scheduler sinks every load to just before its first use to save
             // registers, i.e. it undoes the look-ahead)
             if constexpr (T + 1 < NT) read_a(u_tag, std::integral_constant<int, T + 1>{});
-#if HFAGP_B_EARLY
             {   // B fragments of the item RB-1 ahead, into the slot the PREVIOUS item has just finished with: issued in
                 // front of this item's MFMAs, so the youngest load at the loop's back edge (where hipcc drains vmcnt
                 // to 0) is a whole item old instead of brand new
                 constexpr int TE = (T + RB - 1) % NT, DCE = (T + RB - 1) / NT, SLE = (UU * NT + T + RB - 1) % RB;
                 issue_b(c + DCE, std::integral_constant<int, TE>{}, std::integral_constant<int, SLE>{});
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr)
@@ -258,7 +212,7 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
                 for (int tm = 0; tm < TMW; ++tm)
 #pragma unroll
                     for (int tn = 0; tn < TN; ++tn)
-                        acc[tm][tn] = mfma16<F16>(af[T & 1][tm][PA[pr]], bq[SL][tn][PB[pr]], acc[tm][tn]);
+                        acc[tm][tn] = mfma16<F16>(af[T & 1][tm][PO.pa[pr]], bq[SL][tn][PO.pb[pr]], acc[tm][tn]);
 #pragma unroll
             for (int k = 0; k < A_PER_T; ++k) {
                 const int tk = NT - A_PER_T + k < 0 ? 0 : NT - A_PER_T + k;      // tap that carries slot k
@@ -268,11 +222,6 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
                     if (k == 2) store_a(min(c + 1, c_end - 1), std::integral_constant<int, 1 - UU>{}, std::integral_constant<int, 2>{});
                 }
             }
-            // refill the slot with the item RB ahead
-            constexpr int T2 = (T + RB) % NT, DC = (T + RB) / NT;
-#if !HFAGP_B_EARLY
-            issue_b(c + DC, std::integral_constant<int, T2>{}, std::integral_constant<int, SL>{});
-#endif
             // 9 taps: the patch of chunk c+1 is fetched at the FIRST tap of chunk c and converted under its last taps, so
             // nothing but B fragments is in flight at the loop's back edge, where hipcc drains vmcnt to 0 (its wait-count
             // analysis is conservative at loop headers) — with the fetch at the last tap that drain waited for HBM.
@@ -311,8 +260,8 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
         if constexpr (!EARLY_A) load_a(min(c_begin + 1, c_end - 1));
         // prologue: the first RB items
         issue_b(c_begin + 0 / NT, std::integral_constant<int, 0 % NT>{}, std::integral_constant<int, 0>{});
-        // (HFAGP_B_EARLY: the item itself issues the fragments RB-1 ahead, so the prologue stops one item short)
-        constexpr int NPRO = HFAGP_B_EARLY ? RB - 1 : RB;
+        // (the item itself issues the fragments RB-1 ahead, so the prologue stops one item short)
+        constexpr int NPRO = RB - 1;
         if constexpr (NPRO > 1)
             issue_b(c_begin + 1 / NT, std::integral_constant<int, 1 % NT>{}, std::integral_constant<int, 1>{});
         if constexpr (NPRO > 2)
@@ -454,26 +403,20 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
 // channels per block and two waves per SIMD (256 registers each) — the patch is staged once for twice the MFMA
 // work and the second wave of a SIMD covers the barrier / staging bubbles of the first; used when the layer
 // still fills the chip with the larger tile (make_plan).
-#ifndef HFAGP_UP4_OCC
-#define HFAGP_UP4_OCC 2
-#endif
+constexpr int UP4_OCC = 2;          // blocks per CU the 4-wave variant is compiled for (128 accumulators + 128 registers)
 template <int KD, int NW, int IO = 0>
-__global__ void __launch_bounds__(NW * 64, (NW == 4 && KD != 3) ? HFAGP_UP4_OCC : 1) upconv_bf16_kernel(const ConvParams p) {
+__global__ void __launch_bounds__(NW * 64, (NW == 4 && KD != 3) ? UP4_OCC : 1) upconv_bf16_kernel(const ConvParams p) {
     constexpr int NP = kind_parts_a(KD), NPB = kind_parts(KD);    // parts of the activations (LDS patch) / of the weight image
     constexpr bool F16 = kind_f16(KD);
     constexpr bool XH = (IO & 1) != 0, YH = (IO & 2) != 0;       // fp16 storage of x / y_t (see modconv_bf16_kernel)
     constexpr int XB = XH ? 2 : 4;
     static_assert(IO == 0 || KD == 1, "fp16 storage goes with the single-pass fp16 arithmetic");
     constexpr int NTH = NW * 64;
-    constexpr int TM = 2, TN = 1, WN = NW / 2, BM = 128, BNU = WN * TN * 32, PH = BM / PW, NITEM = 9, RB = kind_nprod(KD) == 1 ? 6 : 3;
+    constexpr int TM = 2, TN = 1, WN = NW / 2, BM = 128, BNU = WN * TN * 32, PH = BM / PW, RB = kind_nprod(KD) == 1 ? 6 : 3;
     constexpr int LPWB = RowPitch<NP>::value;
     constexpr int APOS = (PH + 2) * LPWB;
     constexpr int A_PART = APOS * APITCH, A_BUF = NP * A_PART;
-    constexpr int I_GRP[NITEM] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
-    constexpr int I_PHASE[NITEM] = {0, 1, 2, 3, 0, 1, 0, 2, 0};
-    constexpr int I_W[NITEM] = {0, 1, 3, 4, 6, 7, 2, 5, 8};
-    constexpr int G_FIRST[4] = {0, 4, 6, 8};               // first item of each shift group
-    constexpr int G_OFF[4] = {(1 * LPWB + 1) * APITCH, (0 * LPWB + 1) * APITCH, (1 * LPWB + 0) * APITCH, 0};
+    using namespace up_items;
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     char* As = lds_raw;
     float* Ss = reinterpret_cast<float*>(lds_raw + 2 * A_BUF);
@@ -546,38 +489,10 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && KD != 3) ? HFAGP_UP4_OCC 
         amask[k] = inside ? Gd[sel] : 0.f;          // zero padding and the fp16 range guard in one factor
         soff[k] = sel * p.Cin + 4 * q;
     }
-    auto load_a = [&](int chunk) __attribute__((always_inline)) {
-        const char* xc = xb + (long long)chunk * (CKB * XB);
-#pragma unroll
-        for (int k = 0; k < A_PER_T; ++k) {
-            if constexpr (XH) {
-                const uint2 u = *reinterpret_cast<const uint2*>(xc + aoff[k]);
-                ra[k].x = __builtin_bit_cast(float, u.x);
-                ra[k].y = __builtin_bit_cast(float, u.y);
-            } else {
-                ra[k] = *reinterpret_cast<const float4*>(xc + aoff[k]);
-            }
-        }
-    };
+    auto load_a = [&](int chunk) __attribute__((always_inline)) { a16_load<XH>(ra, xb, chunk, aoff); };
     auto store_a = [&](int chunk, auto buf_tag, auto k_tag) __attribute__((always_inline)) {
         constexpr int BUF = decltype(buf_tag)::value, k = decltype(k_tag)::value;
-        {
-            const float m = amask[k];
-            const float4 sv = *reinterpret_cast<const float4*>(Ss + chunk * CKB + soff[k]);
-            uint2 parts[NP];
-            if constexpr (XH) {
-                const f32x2 s01 = {sv.x * m, sv.y * m}, s23 = {sv.z * m, sv.w * m};
-                const f16x2 x01 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, ra[k].x));
-                const f16x2 x23 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, ra[k].y));
-                parts[0] = make_uint2(__builtin_bit_cast(unsigned, x01 * __builtin_convertvector(s01, f16x2)),
-                                      __builtin_bit_cast(unsigned, x23 * __builtin_convertvector(s23, f16x2)));
-            } else
-            split4<KD>(make_float4(ra[k].x * (sv.x * m), ra[k].y * (sv.y * m), ra[k].z * (sv.z * m),
-                                   ra[k].w * (sv.w * m)), parts);     // (F16X2: one saturating fp16 part)
-#pragma unroll
-            for (int q = 0; q < NP; ++q)
-                *reinterpret_cast<uint2*>(As + BUF * A_BUF + q * A_PART + lds_a[k]) = parts[q];
-        }
+        a16_store<KD, XH>(As + BUF * A_BUF, A_PART, lds_a[k], amask[k], *reinterpret_cast<const float4*>(Ss + chunk * CKB + soff[k]), ra[k]);
     };
 
     // ---- B fragments: one 32-column tile per wave, ring of RB items
@@ -604,9 +519,8 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && KD != 3) ? HFAGP_UP4_OCC 
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[f][tm][tn][r] = 0.f;
 
-    constexpr int NPROD = kind_nprod(KD);
-    constexpr int PA[6] = {kind_pa(KD, 0), kind_pa(KD, 1), kind_pa(KD, 2), kind_pa(KD, 3), kind_pa(KD, 4), kind_pa(KD, 5)};
-    constexpr int PB[6] = {kind_pb(KD, 0), kind_pb(KD, 1), kind_pb(KD, 2), kind_pb(KD, 3), kind_pb(KD, 4), kind_pb(KD, 5)};
+    constexpr PartOrder PO = kind_order(KD);
+    constexpr int NPROD = PO.nprod;
     u32x4 bq[RB][TN][NPB];
     u32x4 af[2][TM][NP];                  // A fragments of the current and the next shift group
     auto issue_b = [&](int c, auto i_tag, auto slot_tag) __attribute__((always_inline)) {
@@ -625,7 +539,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && KD != 3) ? HFAGP_UP4_OCC 
         for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
             for (int q = 0; q < NP; ++q)
-                af[G & 1][tm][q] = *reinterpret_cast<const u32x4*>(As + UU * A_BUF + q * A_PART + G_OFF[G] + apos[tm]);
+                af[G & 1][tm][q] = *reinterpret_cast<const u32x4*>(As + UU * A_BUF + q * A_PART + group_pos(G, LPWB) * APITCH + apos[tm]);
     };
     auto item = [&](int c, auto u_tag, auto i_tag) __attribute__((always_inline)) {
         constexpr int I = decltype(i_tag)::value, G = I_GRP[I], F = I_PHASE[I];
@@ -638,7 +552,7 @@ __global__ void __launch_bounds__(NW * 64, (NW == 4 && KD != 3) ? HFAGP_UP4_OCC 
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                 for (int tn = 0; tn < TN; ++tn)
-                    acc[F][tm][tn] = mfma16<F16>(af[G & 1][tm][PA[pr]], bq[SL][tn][PB[pr]], acc[F][tm][tn]);
+                    acc[F][tm][tn] = mfma16<F16>(af[G & 1][tm][PO.pa[pr]], bq[SL][tn][PO.pb[pr]], acc[F][tm][tn]);
         // the patch of the next chunk is converted into the other LDS buffer under the last A_PER_T items
         if constexpr (I >= NITEM - A_PER_T)
             store_a(min(c + 1, c_end - 1), std::integral_constant<int, 1 - decltype(u_tag)::value>{},
@@ -865,8 +779,7 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
 #pragma unroll
         for (int tn = 0; tn < 4; ++tn) acc[tm][tn] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
-    constexpr int PA[3] = {kind_pa(KD, 0), kind_pa(KD, 1), kind_pa(KD, 2)};
-    constexpr int PB[3] = {kind_pb(KD, 0), kind_pb(KD, 1), kind_pb(KD, 2)};
+    constexpr PartOrder PO = kind_order(KD);
     u32x4 bq[2][4][2];                                                 // ring slot, N tile, part
     u32x4 af[4][2];                                                    // M tile, part (of the tap being computed)
     auto issue_b = [&](int c, int t, auto slot_tag) __attribute__((always_inline)) {
@@ -890,8 +803,8 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
         for (int pr = 0; pr < 3; ++pr)
 #pragma unroll
             for (int tn = 0; tn < 4; ++tn)
-                acc[TMI][tn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[TMI][PA[pr]]),
-                                                                     __builtin_bit_cast(f16x8, bq[SL][tn][PB[pr]]), acc[TMI][tn], 0, 0, 0);
+                acc[TMI][tn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, af[TMI][PO.pa[pr]]),
+                                                                     __builtin_bit_cast(f16x8, bq[SL][tn][PO.pb[pr]]), acc[TMI][tn], 0, 0, 0);
     };
     // item = tap T of chunk c: B of the next item into the other ring slot, then per M tile its 12 MFMAs followed by the
     // reads of that tile's fragments for tap T+1; the patch of chunk c+1 is fetched in two halves (at taps 0 and 4) and
@@ -905,8 +818,10 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
         auto tile = [&](auto tm_tag) __attribute__((always_inline)) {
             mfma_tile(t_tag, tm_tag, std::integral_constant<int, SL>{});
             if constexpr (T + 1 < 9) read_a(u_tag, std::integral_constant<int, T + 1>{}, tm_tag);
-            if constexpr (decltype(tm_tag)::value == 3 && ((T >= 2 && T <= 4) || T >= 6))
-                store_a(min(c + 1, c_end - 1), std::integral_constant<int, 1 - UU>{}, std::integral_constant<int, (T <= 4 ? T - 2 : T - 3)>{});
+            if constexpr ((T >= 2 && T <= 4) || T >= 6) {     // (nested: a tap without a slot must not instantiate store_a)
+                if constexpr (decltype(tm_tag)::value == 3)
+                    store_a(min(c + 1, c_end - 1), std::integral_constant<int, 1 - UU>{}, std::integral_constant<int, (T <= 4 ? T - 2 : T - 3)>{});
+            }
             if constexpr (decltype(tm_tag)::value == 3 && T == 4) load_a(min(c + 1, c_end - 1), std::integral_constant<int, 1>{});
             __builtin_amdgcn_sched_barrier(0);
         };
@@ -1061,13 +976,10 @@ __global__ void __launch_bounds__(256, 2) upconv_bf16_kernel(const ConvParams p)
     static_assert(KD == 4 && NW == 4 && IO == 0 && LOOP == 2, "the 32-channel loop is the 4-wave F16X3 up-conv");
     using namespace u16;
     typedef float f32x4v __attribute__((ext_vector_type(4)));
-    constexpr int NITEM = 9, RB = 2;                                   // (phase, tap) items per chunk; weight ring slots
+    using namespace up_items;
+    constexpr int RB = 2;                                              // weight ring slots
     constexpr int ST = 0;                                              // M tile after which an item converts its patch slot
-    constexpr int I_GRP[NITEM] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
-    constexpr int I_PHASE[NITEM] = {0, 1, 2, 3, 0, 1, 0, 2, 0};
-    constexpr int I_W[NITEM] = {0, 1, 3, 4, 6, 7, 2, 5, 8};
     constexpr int S_SLOT[NITEM] = {-1, -1, 0, 1, -1, 2, 3, -1, 4};      // patch slot converted under each item
-    constexpr int G_POS[4] = {1 * LP + 1, 0 * LP + 1, 1 * LP + 0, 0};   // patch position of tile position (0, 0) under each shift
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     char* As = lds_raw;                                                // [2][2 parts][4 octets][OCT]
     float* Ss = reinterpret_cast<float*>(lds_raw + 2 * A_BUF);         // [up_ns][Cin] styles x 2^-e, then [up_ns] 2^e
@@ -1166,8 +1078,7 @@ __global__ void __launch_bounds__(256, 2) upconv_bf16_kernel(const ConvParams p)
 #pragma unroll
             for (int tn = 0; tn < 2; ++tn) acc[f][tm][tn] = f32x4v{0.f, 0.f, 0.f, 0.f};
 
-    constexpr int PA[3] = {kind_pa(KD, 0), kind_pa(KD, 1), kind_pa(KD, 2)};
-    constexpr int PB[3] = {kind_pb(KD, 0), kind_pb(KD, 1), kind_pb(KD, 2)};
+    constexpr PartOrder PO = kind_order(KD);
     u32x4 bq[RB][2][2];                                                // ring slot, N tile, part
     u32x4 af[4][2];                                                    // M tile, part (of the shift group being computed)
     auto issue_b = [&](int c, int w, auto slot_tag) __attribute__((always_inline)) {
@@ -1183,7 +1094,7 @@ __global__ void __launch_bounds__(256, 2) upconv_bf16_kernel(const ConvParams p)
         constexpr int UU = decltype(u_tag)::value, G = decltype(g_tag)::value, TMI = decltype(tm_tag)::value;
 #pragma unroll
         for (int q = 0; q < 2; ++q)
-            af[TMI][q] = *reinterpret_cast<const u32x4*>(afrag + UU * A_BUF + q * A_PART + (TMI * LP + G_POS[G]) * 16);
+            af[TMI][q] = *reinterpret_cast<const u32x4*>(afrag + UU * A_BUF + q * A_PART + (TMI * LP + group_pos(G, LP)) * 16);
     };
     // item = (phase, tap) I of chunk c: the weights of item I + RB - 1 into the ring, then per M tile its 6 MFMAs followed, under the
     // last item of a shift group, by the reads of that tile's fragments for the next group; the patch of chunk c+1 is fetched at
@@ -1200,7 +1111,7 @@ __global__ void __launch_bounds__(256, 2) upconv_bf16_kernel(const ConvParams p)
             for (int pr = 0; pr < 3; ++pr)
 #pragma unroll
                 for (int tn = 0; tn < 2; ++tn) {
-                    const f16x8 xa = __builtin_bit_cast(f16x8, af[TMI][PA[pr]]), wb = __builtin_bit_cast(f16x8, bq[SL][tn][PB[pr]]);
+                    const f16x8 xa = __builtin_bit_cast(f16x8, af[TMI][PO.pa[pr]]), wb = __builtin_bit_cast(f16x8, bq[SL][tn][PO.pb[pr]]);
                     acc[F][TMI][tn] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb, xa, acc[F][TMI][tn], 0, 0, 0);
                 }
             if constexpr (I + 1 < NITEM && I_GRP[(I + 1) % NITEM] != G) read_a(u_tag, std::integral_constant<int, G + 1>{}, tm_tag);
@@ -1461,241 +1372,4 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
     return check_launch("modconv_fwd (16-bit MFMA)");
 }
 
-// Scaled float16 weight images (hfagp.h "Weight images"): max |w| of the tensor first — as the bit pattern of a non-negative float,
-// which orders like an unsigned integer, one atomic per block into a slot cleared before — then the prep kernels store w 2^-e
-// (weight_image_exp of that maximum: exact) and leave the maximum where the consumers find it.  No host synchronisation.
-__device__ __forceinline__ void publish_weight_absmax(float absmax, bool nan, float* slot) {
-    unsigned m = nan ? 0x7fffffffu : __builtin_bit_cast(unsigned, absmax);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    __shared__ unsigned wmax[4];
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(reinterpret_cast<unsigned*>(slot), max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3])));
-}
-// (a NaN weight must not vanish in fmaxf: the slot then holds a NaN pattern, above every finite one, and e is 0)
-__global__ void __launch_bounds__(256) weight_absmax_kernel(const float* __restrict__ w, long long n, float* slot) {
-    float m = 0.f;
-    bool nan = false;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-        const float v = w[i];
-        nan |= v != v;
-        m = fmaxf(m, fabsf(v));
-    }
-    publish_weight_absmax(m, nan, slot);
-}
-
-// weight [Cout][Cin][taps] -> wb [parts][taps][Cin/8][Cout][8] bf16 or fp16 (operand kind kd); thread = (tap, ci group, co)
-__global__ void __launch_bounds__(256) weight_prep_split_kernel(const float* __restrict__ w, uint4* __restrict__ wb,
-                                                                int Cout, int Cin, int taps, int kd, const float* w_absmax) {
-    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int cq8 = Cin >> 3;
-    const long long n = (long long)taps * cq8 * Cout;
-    if (idx >= n) return;
-    const int co = (int)(idx % Cout);
-    const int g = (int)((idx / Cout) % cq8);
-    const int t = (int)(idx / ((long long)Cout * cq8));
-    float r[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = w[((size_t)co * Cin + 8 * g + e) * taps + t];
-    if (kd == 5) kd = 4;          // F16X2 reads the F16X3 image (two fp16 parts of the weights)
-    if (kd == 1 || kd == 4) {
-        const float sc = ldexpf(1.f, -weight_image_exp(w_absmax));
-        unsigned u[4];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) r[e] *= sc;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = pack_f16(r[2 * e], r[2 * e + 1]);
-        wb[idx] = make_uint4(u[0], u[1], u[2], u[3]);
-        if (kd == 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                u[e] = pack_f16(r[2 * e] - f16_lo_back(u[e]), r[2 * e + 1] - f16_hi_back(u[e]));
-            wb[n + idx] = make_uint4(u[0], u[1], u[2], u[3]);
-        }
-        return;
-    }
-    const int nparts = kd;
-    for (int q = 0; q < nparts; ++q) {
-        unsigned u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            u[e] = pack_bf16(r[2 * e], r[2 * e + 1]);
-            r[2 * e] -= __builtin_bit_cast(float, u[e] << 16);
-            r[2 * e + 1] -= __builtin_bit_cast(float, u[e] & 0xffff0000u);
-        }
-        wb[q * n + idx] = make_uint4(u[0], u[1], u[2], u[3]);
-    }
-}
-
-// Batched weight preparation (round 5; ABI 11): while the generator is being TUNED its weights change every step, and every step
-// needs, per conv layer, the forward B-operand image, the image of the Cin/Cout TRANSPOSE for the bwd-data GEMM and wsq for the
-// demodulation — 47 weight_prep_split launches + 23 weight_prep launches (which also wrote an fp32 image nobody read) = 1.2 ms of a
-// 15 ms step.  Here ONE launch serves all layers: a block stages a 32 (co) x 32 (ci) x taps tile of one weight in LDS with coalesced
-// reads and emits the three outputs from it — the weight is read once, every output leaves in 512-byte runs.
-constexpr int kWPMax = 48;
-struct WPItem { const float* w; uint4* img; uint4* img_t; float* wsq; float* amax; int Cout, Cin, taps, kd, kd_t, tile0; };
-struct WPBatch { WPItem it[kWPMax]; int n; };
-
-__device__ __forceinline__ void wp_emit(float (&r)[8], uint4* dst, long long n_img, long long idx, int kd, float sc) {
-    if (kd == 5) kd = 4;
-    if (kd == 1 || kd == 4) {
-        unsigned u[4];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) r[e] *= sc;          // (2^-e of a scaled image, 1 otherwise)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) u[e] = pack_f16(r[2 * e], r[2 * e + 1]);
-        dst[idx] = make_uint4(u[0], u[1], u[2], u[3]);
-        if (kd == 4) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) u[e] = pack_f16(r[2 * e] - f16_lo_back(u[e]), r[2 * e + 1] - f16_hi_back(u[e]));
-            dst[n_img + idx] = make_uint4(u[0], u[1], u[2], u[3]);
-        }
-        return;
-    }
-    float t[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) t[e] = r[e];
-    for (int q = 0; q < kd; ++q) {
-        unsigned u[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            u[e] = pack_bf16(t[2 * e], t[2 * e + 1]);
-            t[2 * e] -= __builtin_bit_cast(float, u[e] << 16);
-            t[2 * e + 1] -= __builtin_bit_cast(float, u[e] & 0xffff0000u);
-        }
-        dst[q * n_img + idx] = make_uint4(u[0], u[1], u[2], u[3]);
-    }
-}
-
-__global__ void __launch_bounds__(64) weight_absmax_clear_kernel(const WPBatch b) {
-    if ((int)threadIdx.x < b.n && b.it[threadIdx.x].amax) *b.it[threadIdx.x].amax = 0.f;
-}
-
-// (the grid of weight_prep_batch_kernel: a block takes the same 32 x 32 x taps tile)
-__global__ void __launch_bounds__(256) weight_absmax_batch_kernel(const WPBatch b) {
-    int i = 0;
-    while (i + 1 < b.n && (int)blockIdx.x >= b.it[i + 1].tile0) ++i;
-    const WPItem& a = b.it[i];
-    if (!a.amax) return;
-    const int tci_n = a.Cin >> 5;
-    const int tl = blockIdx.x - a.tile0, co0 = (tl / tci_n) * 32, ci0 = (tl % tci_n) * 32;
-    const int row = 32 * a.taps;
-    float m = 0.f;
-    bool nan = false;
-    for (int e = threadIdx.x; e < 32 * row; e += 256) {
-        const int co = e / row, r = e - co * row;
-        const float v = a.w[((size_t)(co0 + co) * a.Cin + ci0) * a.taps + r];
-        nan |= v != v;
-        m = fmaxf(m, fabsf(v));
-    }
-    publish_weight_absmax(m, nan, a.amax);
-}
-
-__global__ void __launch_bounds__(256) weight_prep_batch_kernel(const WPBatch b) {
-    __shared__ float tile[32][32 * 9 + 1];                     // [co][ci * taps + t]
-    int i = 0;
-    while (i + 1 < b.n && (int)blockIdx.x >= b.it[i + 1].tile0) ++i;
-    const WPItem& a = b.it[i];
-    const float sc = ldexpf(1.f, -weight_image_exp(a.amax));
-    const int tci_n = a.Cin >> 5;
-    const int tl = blockIdx.x - a.tile0, co0 = (tl / tci_n) * 32, ci0 = (tl % tci_n) * 32;
-    const int taps = a.taps, row = 32 * taps;
-    for (int e = threadIdx.x; e < 32 * row; e += 256) {
-        const int co = e / row, r = e - co * row;
-        tile[co][r] = a.w[((size_t)(co0 + co) * a.Cin + ci0) * taps + r];
-    }
-    __syncthreads();
-    const long long n_f = (long long)taps * (a.Cin >> 3) * a.Cout, n_t = (long long)taps * (a.Cout >> 3) * a.Cin;
-    for (int e = threadIdx.x; e < taps * 4 * 32; e += 256) {
-        const int c = e & 31, g = (e >> 5) & 3, t = e >> 7;
-        float r[8];
-        if (a.img) {                                           // forward image: 8 consecutive ci of (tap t, co c)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) r[k] = tile[c][(8 * g + k) * taps + t];
-            wp_emit(r, a.img, n_f, ((long long)t * (a.Cin >> 3) + (ci0 >> 3) + g) * a.Cout + co0 + c, a.kd, sc);
-        }
-        if (a.img_t) {                                         // image of the transpose: 8 consecutive co of (tap t, ci c)
-#pragma unroll
-            for (int k = 0; k < 8; ++k) r[k] = tile[8 * g + k][c * taps + t];
-            wp_emit(r, a.img_t, n_t, ((long long)t * (a.Cout >> 3) + (co0 >> 3) + g) * a.Cin + ci0 + c, a.kd_t, sc);
-        }
-    }
-    if (a.wsq)
-        for (int e = threadIdx.x; e < 32 * 32; e += 256) {
-            const int ci = e & 31, co = e >> 5;
-            float sq = 0.f;
-            for (int t = 0; t < taps; ++t) { const float v = tile[co][ci * taps + t]; sq += v * v; }
-            a.wsq[(size_t)(co0 + co) * a.Cin + ci0 + ci] = sq;
-        }
-}
-
 }  // namespace hfagp
-
-using namespace hfagp;
-
-static int weight_prep_kind(const float* weight, void* wb, float* w_absmax, int32_t Cout, int32_t Cin, int32_t taps, int kd,
-                            void* stream) {
-    HFAGP_REQUIRE(weight && wb, HFAGP_EBADARG, "weight_prep_split: null pointer");
-    HFAGP_REQUIRE(Cin % 8 == 0 && Cout > 0 && (taps == 1 || taps == 9), HFAGP_EUNSUPPORTED,
-                  "weight_prep_split: Cin=%d must be a multiple of 8, taps=%d in {1,9}", Cin, taps);
-    const long long n = (long long)taps * (Cin / 8) * Cout;
-    if (w_absmax) {
-        HFAGP_REQUIRE(kind_f16(kd), HFAGP_EBADARG, "weight_prep_scaled: only the float16 kinds have a scaled image");
-        if (hipMemsetAsync(w_absmax, 0, sizeof(float), (hipStream_t)stream) != hipSuccess) return check_launch("weight_prep_scaled");
-        weight_absmax_kernel<<<(unsigned)std::min<long long>((8 * n + 1023) / 1024, 1024), 256, 0, (hipStream_t)stream>>>(
-            weight, 8 * n, w_absmax);
-    }
-    weight_prep_split_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(
-        weight, reinterpret_cast<uint4*>(wb), Cout, Cin, taps, kd, w_absmax);
-    return check_launch("weight_prep_split");
-}
-
-extern "C" int hfagp_weight_prep_split(const float* weight, void* wb, int32_t Cout, int32_t Cin, int32_t taps,
-                                       int32_t nparts, void* stream) {
-    HFAGP_REQUIRE(nparts >= 1 && nparts <= 3, HFAGP_EUNSUPPORTED, "weight_prep_split: nparts=%d in {1,2,3}", nparts);
-    return weight_prep_kind(weight, wb, nullptr, Cout, Cin, taps, nparts, stream);
-}
-
-extern "C" int hfagp_weight_prep_prec(const float* weight, void* wb, int32_t Cout, int32_t Cin, int32_t taps,
-                                      int32_t precision, void* stream) {
-    const int kd = kind_of(precision);
-    HFAGP_REQUIRE(kd != 0, HFAGP_EBADARG, "weight_prep_prec: precision %d has no 16-bit weight image", precision);
-    return weight_prep_kind(weight, wb, nullptr, Cout, Cin, taps, kd, stream);
-}
-
-extern "C" int hfagp_weight_prep_scaled(const float* weight, void* wb, float* w_absmax, int32_t Cout, int32_t Cin, int32_t taps,
-                                        int32_t precision, void* stream) {
-    const int kd = kind_of(precision);
-    HFAGP_REQUIRE(kd != 0 && w_absmax, HFAGP_EBADARG, "weight_prep_scaled: precision %d / null w_absmax", precision);
-    return weight_prep_kind(weight, wb, w_absmax, Cout, Cin, taps, kd, stream);
-}
-
-extern "C" int hfagp_weight_prep_batch(const HfagpWeightPrepItem* items, int32_t n, void* stream) {
-    HFAGP_REQUIRE(items && n >= 1 && n <= kWPMax, HFAGP_EBADARG, "weight_prep_batch: 1..%d items", kWPMax);
-    WPBatch b;
-    int tiles = 0;
-    bool any_scaled = false;
-    for (int i = 0; i < n; ++i) {
-        const HfagpWeightPrepItem& a = items[i];
-        HFAGP_REQUIRE(a.weight && (a.image || a.image_t || a.wsq), HFAGP_EBADARG, "weight_prep_batch: null pointer (item %d)", i);
-        HFAGP_REQUIRE(a.Cout % 32 == 0 && a.Cin % 32 == 0 && (a.taps == 1 || a.taps == 9), HFAGP_EUNSUPPORTED,
-                      "weight_prep_batch: item %d: Cout=%d, Cin=%d must be multiples of 32, taps=%d in {1,9}", i, a.Cout, a.Cin, a.taps);
-        const int kd = a.image ? kind_of(a.precision) : 0, kd_t = a.image_t ? kind_of(a.precision_t) : 0;
-        HFAGP_REQUIRE((!a.image || kd != 0) && (!a.image_t || kd_t != 0), HFAGP_EBADARG,
-                      "weight_prep_batch: item %d: precision without a 16-bit weight image", i);
-        // (max |w| only where a float16 image of the item will be scaled by it)
-        float* amax = (kind_f16(kd) || kind_f16(kd_t)) ? a.w_absmax : nullptr;
-        any_scaled |= amax != nullptr;
-        b.it[i] = WPItem{a.weight, reinterpret_cast<uint4*>(a.image), reinterpret_cast<uint4*>(a.image_t), a.wsq, amax, a.Cout, a.Cin,
-                         a.taps, kd, kd_t, tiles};
-        tiles += (a.Cout / 32) * (a.Cin / 32);
-    }
-    b.n = n;
-    if (any_scaled) {
-        weight_absmax_clear_kernel<<<1, 64, 0, (hipStream_t)stream>>>(b);
-        weight_absmax_batch_kernel<<<(unsigned)tiles, 256, 0, (hipStream_t)stream>>>(b);
-    }
-    weight_prep_batch_kernel<<<(unsigned)tiles, 256, 0, (hipStream_t)stream>>>(b);
-    return check_launch("weight_prep_batch");
-}

@@ -37,6 +37,12 @@ constexpr bool kind_f16(int kd) { return kd == 1 || kd == 4 || kd == 5; }
 constexpr int kind_nprod(int kd) { return kd == 1 ? 1 : kd == 5 ? 2 : kind_parts(kd) == 2 ? 3 : 6; }
 constexpr int kind_pa(int kd, int i) { return kd == 5 ? 0 : (i == 1 || i == 3) ? 1 : i == 4 ? 2 : 0; }
 constexpr int kind_pb(int kd, int i) { return kd == 5 ? i : (i == 2 || i == 3) ? 1 : i == 5 ? 2 : 0; }
+// the same as one table per kind: product i of the nprod is (A part pa[i]) x (B part pb[i])
+struct PartOrder { int nprod, pa[6], pb[6]; };
+constexpr PartOrder kind_order(int kd) {
+    return PartOrder{kind_nprod(kd), {kind_pa(kd, 0), kind_pa(kd, 1), kind_pa(kd, 2), kind_pa(kd, 3), kind_pa(kd, 4), kind_pa(kd, 5)},
+                     {kind_pb(kd, 0), kind_pb(kd, 1), kind_pb(kd, 2), kind_pb(kd, 3), kind_pb(kd, 4), kind_pb(kd, 5)}};
+}
 
 __device__ __forceinline__ float f16_lo_back(unsigned u) {       // fp16 in bits 0-15 -> float
     return (float)__builtin_bit_cast(f16x2, u)[0];

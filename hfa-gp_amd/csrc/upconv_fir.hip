@@ -46,23 +46,20 @@ constexpr int FW_BYTES = 4 * 3 * FT_PLANE * 4;            // windows: 4 channel 
 
 template <int KD, int IO>
 __global__ void __launch_bounds__(512, 1) upconv_fir_kernel(const ConvParams p, const FirFuse ff) {
+    using namespace up_items;
     constexpr int NP = kind_parts(KD);
+    static_assert(NP == kind_parts_a(KD), "no F16X2 here: activations and weights have the same parts");
     constexpr bool F16 = kind_f16(KD);
     constexpr bool XH = (IO & 1) != 0, YH = (IO & 2) != 0;       // fp16 storage of x / y (see modconv_bf16_kernel)
     constexpr int XB = XH ? 2 : 4;
     static_assert(IO == 0 || KD == 1, "fp16 storage goes with the single-pass fp16 arithmetic");
     constexpr int NW = 8, NTH = NW * 64;
-    constexpr int TM = 2, TN = 1, WN = NW / 2, BM = 128, BNU = WN * TN * 32, PH = BM / PW, NITEM = 9, RB = NP == 1 ? 6 : 3;
+    constexpr int TM = 2, TN = 1, WN = NW / 2, BM = 128, BNU = WN * TN * 32, PH = BM / PW, RB = NP == 1 ? 6 : 3;
     static_assert(BNU == 128 && PH == 8, "tile shape");
     constexpr int LPWB = RowPitch<NP>::value;
     constexpr int APOS = (PH + 2) * LPWB;
     constexpr int A_PART = APOS * APITCH, A_BUF = NP * A_PART;
     constexpr int REGION0 = 2 * A_BUF > FT_BYTES ? 2 * A_BUF : FT_BYTES;
-    constexpr int I_GRP[NITEM] = {0, 0, 0, 0, 1, 1, 2, 2, 3};
-    constexpr int I_PHASE[NITEM] = {0, 1, 2, 3, 0, 1, 0, 2, 0};
-    constexpr int I_W[NITEM] = {0, 1, 3, 4, 6, 7, 2, 5, 8};
-    constexpr int G_FIRST[4] = {0, 4, 6, 8};
-    constexpr int G_OFF[4] = {(1 * LPWB + 1) * APITCH, (0 * LPWB + 1) * APITCH, (1 * LPWB + 0) * APITCH, 0};
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
     char* As = lds_raw;                                           // K loop: [2][NP][APOS][48 B]
     float* T = reinterpret_cast<float*>(lds_raw);                 // epilogue: [16 rows][32 cols][32 ch] (aliases As)
@@ -110,9 +107,8 @@ __global__ void __launch_bounds__(512, 1) upconv_fir_kernel(const ConvParams p, 
         const int pidx = (wm * TM + tm) * 32 + l31;
         apos[tm] = ((pidx >> 4) * LPWB + (pidx & 15)) * APITCH + 16 * h;
     }
-    constexpr int NPROD = NP == 1 ? 1 : NP == 2 ? 3 : 6;
-    constexpr int PA[6] = {0, 1, 0, 1, 2, 0};
-    constexpr int PB[6] = {0, 0, 1, 1, 0, 2};
+    constexpr PartOrder PO = kind_order(KD);
+    constexpr int NPROD = PO.nprod;
 
     const int Ho2 = 2 * p.H, Wo2 = 2 * p.W;
     const int C0 = 32 * tw;
@@ -137,37 +133,10 @@ __global__ void __launch_bounds__(512, 1) upconv_fir_kernel(const ConvParams p, 
             amask[k] = inside ? sdown : 0.f;
             soff[k] = 4 * q;
         }
-        auto load_a = [&](int chunk) __attribute__((always_inline)) {
-            const char* xc = xb + (long long)chunk * (CKB * XB);
-#pragma unroll
-            for (int k = 0; k < A_PER_T; ++k) {
-                if constexpr (XH) {
-                    const uint2 u = *reinterpret_cast<const uint2*>(xc + aoff[k]);
-                    ra[k].x = __builtin_bit_cast(float, u.x);
-                    ra[k].y = __builtin_bit_cast(float, u.y);
-                } else {
-                    ra[k] = *reinterpret_cast<const float4*>(xc + aoff[k]);
-                }
-            }
-        };
+        auto load_a = [&](int chunk) __attribute__((always_inline)) { a16_load<XH>(ra, xb, chunk, aoff); };
         auto store_a = [&](int chunk, auto buf_tag, auto k_tag) __attribute__((always_inline)) {
             constexpr int BUF = decltype(buf_tag)::value, k = decltype(k_tag)::value;
-            const float m = amask[k];
-            const float4 sv = *reinterpret_cast<const float4*>(Ss + chunk * CKB + soff[k]);
-            uint2 parts[NP];
-            if constexpr (XH) {
-                const f32x2 s01 = {sv.x * m, sv.y * m}, s23 = {sv.z * m, sv.w * m};
-                const f16x2 x01 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, ra[k].x));
-                const f16x2 x23 = __builtin_bit_cast(f16x2, __builtin_bit_cast(unsigned, ra[k].y));
-                parts[0] = make_uint2(__builtin_bit_cast(unsigned, x01 * __builtin_convertvector(s01, f16x2)),
-                                      __builtin_bit_cast(unsigned, x23 * __builtin_convertvector(s23, f16x2)));
-            } else {
-                split4<KD>(make_float4(ra[k].x * (sv.x * m), ra[k].y * (sv.y * m), ra[k].z * (sv.z * m),
-                                       ra[k].w * (sv.w * m)), parts);
-            }
-#pragma unroll
-            for (int q = 0; q < NP; ++q)
-                *reinterpret_cast<uint2*>(As + BUF * A_BUF + q * A_PART + lds_a[k]) = parts[q];
+            a16_store<KD, XH>(As + BUF * A_BUF, A_PART, lds_a[k], amask[k], *reinterpret_cast<const float4*>(Ss + chunk * CKB + soff[k]), ra[k]);
         };
 
         f32x16 acc[4][TM];
@@ -195,7 +164,7 @@ __global__ void __launch_bounds__(512, 1) upconv_fir_kernel(const ConvParams p, 
             for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
                 for (int q = 0; q < NP; ++q)
-                    af[G & 1][tm][q] = *reinterpret_cast<const u32x4*>(As + UU * A_BUF + q * A_PART + G_OFF[G] + apos[tm]);
+                    af[G & 1][tm][q] = *reinterpret_cast<const u32x4*>(As + UU * A_BUF + q * A_PART + group_pos(G, LPWB) * APITCH + apos[tm]);
         };
         auto item = [&](int c, auto u_tag, auto i_tag) __attribute__((always_inline)) {
             constexpr int I = decltype(i_tag)::value, G = I_GRP[I], F = I_PHASE[I];
@@ -206,7 +175,7 @@ __global__ void __launch_bounds__(512, 1) upconv_fir_kernel(const ConvParams p, 
             for (int pr = 0; pr < NPROD; ++pr)
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
-                    acc[F][tm] = mfma16<F16>(af[G & 1][tm][PA[pr]], bq[SL][PB[pr]], acc[F][tm]);
+                    acc[F][tm] = mfma16<F16>(af[G & 1][tm][PO.pa[pr]], bq[SL][PO.pb[pr]], acc[F][tm]);
             if constexpr (I >= NITEM - A_PER_T)
                 store_a(min(c + 1, c_end - 1), std::integral_constant<int, 1 - decltype(u_tag)::value>{},
                         std::integral_constant<int, I - (NITEM - A_PER_T)>{});

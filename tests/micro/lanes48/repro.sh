@@ -29,7 +29,7 @@ declare -A flags=(
   [slp_snop0]="-mllvm -amdgpu-snop-padding=1"
   [slp_snop3]="-mllvm -amdgpu-snop-padding=4"
 )
-objs=(); for u in elementwise modconv modconv_bf16 smallconv upconv_fir raymarch backward raymarch_bwd wgrad wgrad_bf16 qr loss collective; do objs+=("$src/$u.o"); done
+objs=(); for u in elementwise modconv modconv_bf16 weight_prep smallconv upconv_fir raymarch backward raymarch_bwd wgrad wgrad_bf16 qr loss collective; do objs+=("$src/$u.o"); done
 log="$R/gpurun_out/lanes48_repro.txt"; : > "$log"
 for v in ${VARIANTS:-noslp slp slp_mfmapad slp_waitzero slp_loadzero slp_snop0 slp_snop3}; do
   /opt/rocm/bin/hipcc "${base[@]}" ${flags[$v]} -c "$src/torgb_skip.hip" -o "$out/torgb_$v.o" 2>/dev/null || { echo "variant $v: compile failed" | tee -a "$log"; continue; }

@@ -106,16 +106,23 @@ def test_planes_query_kernel_has_no_scratch(tmp_path):
     assert len(seen) == 8, seen          # {split fp16, fp32 decoder} x {rgb, sigma only} x {explicit, grid}
 
 
+# units appended to build.sh's list since ABI 13 that this file holds to the packed-fp32 rule, with a kernel each must contain
+# (test_kernel_resources.py pins the list before them)
+APPENDED_UNITS = [("planes_query", "planes_query_kernel"), ("weight_prep", "weight_prep_batch_kernel")]
+
+
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
-def test_planes_query_has_no_packed_fp32_arithmetic(tmp_path):
+@pytest.mark.parametrize("unit,kernel", APPENDED_UNITS, ids=[u for u, _ in APPENDED_UNITS])
+def test_appended_unit_has_no_packed_fp32_arithmetic(tmp_path, unit, kernel):
     """test_kernel_resources.py's rule for every unit (build.sh's note on the lost low half of packed fp32 ops): compiled with build.sh's
-    flags, planes_query.hip contains no v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32."""
+    flags, the unit contains no v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32."""
     build = open(os.path.join(ROOT, "hfa-gp_amd", "csrc", "build.sh")).read()
+    assert re.search(r"^units\+=\(.*\b%s\b" % unit, build, re.M), f"{unit}.hip is not in build.sh's unit list"
     flags = re.search(r"^FLAGS=\((.*)\)", build, re.M).group(1).split()
-    asm = tmp_path / "pq.s"
-    out = subprocess.run([HIPCC, *flags, "-S", "--cuda-device-only", os.path.join(ROOT, "hfa-gp_amd", "csrc", "planes_query.hip"),
+    asm = tmp_path / "unit.s"
+    out = subprocess.run([HIPCC, *flags, "-S", "--cuda-device-only", os.path.join(ROOT, "hfa-gp_amd", "csrc", unit + ".hip"),
                           "-o", str(asm)], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     text = asm.read_text()
-    assert "planes_query_kernel" in text
+    assert kernel in text
     assert not re.findall(r"v_pk_(fma|mul|add)_f32", text)

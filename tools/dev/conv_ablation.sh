@@ -1,10 +1,10 @@
 #!/usr/bin/env bash
-# Developer: ablation builds of the 16-bit conv kernel (what bounds it?).  Run HERE to build (cross-compile), the
-# variants travel to the GPU box with gpurun; there:  bash tools/dev/conv_ablation.sh run
+# Developer: ablation builds of the 16-bit conv kernel (what bounds it?).  Build where hipcc is (cross-compiles); on the
+# machine with the GPU:  bash tools/dev/conv_ablation.sh run
 set -euo pipefail
 here="$(cd "$(dirname "${BASH_SOURCE[0]}")/../.." && pwd)"
 csrc="${CSRC:-$here/hfa-gp_amd/csrc}"   # ablation variants: see tools/dev/patches/README.md
-variants=(base "nostore:-DHFAGP_ABL_NOSTORE" "old:-DHFAGP_LOADA_EARLY=0 -DHFAGP_B_EARLY=0" "aearly:-DHFAGP_LOADA_EARLY=1 -DHFAGP_B_EARLY=0" "bearly:-DHFAGP_LOADA_EARLY=0 -DHFAGP_B_EARLY=1"
+variants=(base "nostore:-DHFAGP_ABL_NOSTORE"
           "nob:-DHFAGP_ABL_NOB" "noa:-DHFAGP_ABL_NOA" "nostage:-DHFAGP_ABL_NOSTAGE"
           "mfmaonly:-DHFAGP_ABL_NOB -DHFAGP_ABL_NOA -DHFAGP_ABL_NOSTAGE -DHFAGP_ABL_NOBAR" "presplit:-DHFAGP_ABL_PRESPLIT")
 [[ -n "${ABL_VARIANTS:-}" ]] && read -r -a variants <<< "$ABL_VARIANTS"
@@ -18,7 +18,7 @@ if [[ "${1:-build}" == "build" ]]; then
     wait
     for v in "${variants[@]}"; do
         name="${v%%:*}"; [[ "$name" == base ]] && continue
-        objs=(); for s in elementwise modconv torgb_skip raymarch backward raymarch_bwd wgrad wgrad_bf16 qr loss; do objs+=("$csrc/$s.o"); done
+        objs=(); for s in elementwise modconv weight_prep torgb_skip raymarch backward raymarch_bwd wgrad wgrad_bf16 qr loss; do objs+=("$csrc/$s.o"); done
         /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC "${objs[@]}" "/tmp/mcb_$name.o" -o "$here/hfa-gp_amd/libhfagp_abl_$name.so"
     done
     ls -la "$here"/hfa-gp_amd/libhfagp_abl_*.so
