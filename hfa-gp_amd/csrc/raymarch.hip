@@ -49,7 +49,10 @@ struct WaveLds {
 // FROM_STATE (GRADS only): the per-sample colours, densities, depths and sort order of every ray are READ from
 // HfagpRaymarchArgs::state, where the forward call of the same step left them (13.4 KB per ray), instead of being recomputed
 // — no gather, no decoder: the compositing adjoint alone.
-template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false>
+// LEGACY_TAPS: every lane of a gather quad computes the taps of all three planes (sample_taps) instead of one plane per lane
+// exchanged by DPP (raymarch_common.h sample_taps_quad) — the form before the exchange, kept selectable for A/B timing and the
+// bit-identity tests (developer switch HFAGP_DEV_RAY_TAPS_LEGACY=1, launch_raymarch).
+template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false>
 __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
     static_assert(!FROM_STATE || GRADS, "the saved state is consumed by the backward pass");
     using L = WaveLds<NC, NF>;
@@ -78,6 +81,7 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
         load_decoder(a, j, g, dec);
     }
     constexpr int kStateFloats = S * 35;        // per ray: col [S][32] | ts [S] | ss [S] | sid [S]
+    const QuadPlaneSel qsel = quad_plane_sel(a, lane & 3);      // the plane this lane computes the taps of (sample_taps_quad)
 
     const RaySchedule sch = ray_schedule(p.total_rays, wave);
     // The set-up of a ray — position in the sequence -> (frame, pixel) with five integer divisions, the camera ray with seven
@@ -177,10 +181,15 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
                     *reinterpret_cast<float4*>(&lds.col[s * CS + 16 * ot + 4 * g]) = cv;
                 }
             };
+            // the taps of sample (lane >> 2) of a tile: one plane per quad lane + DPP exchange (all 64 lanes are active here)
+            auto tile_taps = [&](float tz, PlaneTaps taps[3]) {
+                if constexpr (LEGACY_TAPS) sample_taps(p, o3, d3, tz, taps);
+                else sample_taps_quad(p, qsel, o3, d3, tz, taps);
+            };
             auto eval_tile = [&](int s0) {
                 float f[8];
                 PlaneTaps taps[3];
-                sample_taps(p, o3, d3, lds.t[s0 + (lane >> 2)], taps);
+                tile_taps(lds.t[s0 + (lane >> 2)], taps);
                 gather8(a, b, lane & 3, taps, f);
                 decode_tile(s0, f);
             };
@@ -199,7 +208,7 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
                             // (priority: this wave's tap arithmetic and load issue go ahead of the other wave's decoder
                             // arithmetic on the SIMD, so its loads are in flight under that decoder: -1.7 %)
                             __builtin_amdgcn_s_setprio(3);
-                            sample_taps(p, o3, d3, lds.t[first + 16 * tile + (lane >> 2)], taps);
+                            tile_taps(lds.t[first + 16 * tile + (lane >> 2)], taps);
                             tile_issue(a, b, lane & 3, taps, tl);
                             __builtin_amdgcn_s_setprio(0);
                             tile_reduce(tl, f);
@@ -462,36 +471,45 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
     }
 }
 
-template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false>
+template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false>
 static int launch(const RayParams& p, hipStream_t s) {
     const size_t lds = 4 * sizeof(WaveLds<NC, NF>) + ((DEC16 && !FROM_STATE) ? kDecL1Floats * sizeof(float) : 0);
     int blocks = (p.total_rays + 3) / 4;
     const int cap = kNumCU * 2 * 4;          // 2 resident workgroups per CU, a few rounds each
     if (blocks > cap) blocks = cap;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&raymarch_kernel<NC, NF, GRADS, DEC16, FROM_STATE>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&raymarch_kernel<NC, NF, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             set_error("raymarch: cannot raise dynamic LDS to %zu bytes: %s", lds, hipGetErrorString(e));
             return HFAGP_ELAUNCH;
         }
     }
-    raymarch_kernel<NC, NF, GRADS, DEC16, FROM_STATE><<<blocks, 256, lds, s>>>(p);
+    raymarch_kernel<NC, NF, GRADS, DEC16, FROM_STATE, LEGACY_TAPS><<<blocks, 256, lds, s>>>(p);
     return check_launch(GRADS ? "raymarch_bwd/samples" : "raymarch_fwd");
 }
 
-template <bool GRADS, bool DEC16, bool FROM_STATE = false>
+template <bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false>
 static int launch_n(const RayParams& p, hipStream_t s) {
     const int n = p.a.Sc / 16;
-    return n == 3 ? launch<3, 3, GRADS, DEC16, FROM_STATE>(p, s) : n == 2 ? launch<2, 2, GRADS, DEC16, FROM_STATE>(p, s)
-                                                                          : launch<1, 1, GRADS, DEC16, FROM_STATE>(p, s);
+    return n == 3   ? launch<3, 3, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>(p, s)
+           : n == 2 ? launch<2, 2, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>(p, s)
+                    : launch<1, 1, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>(p, s);
+}
+
+template <bool LEGACY_TAPS>
+static int launch_gather(const RayParams& p, bool grads, bool dec16, hipStream_t s) {
+    if (grads) return dec16 ? launch_n<true, true, false, LEGACY_TAPS>(p, s) : launch_n<true, false, false, LEGACY_TAPS>(p, s);
+    return dec16 ? launch_n<false, true, false, LEGACY_TAPS>(p, s) : launch_n<false, false, false, LEGACY_TAPS>(p, s);
 }
 
 int launch_raymarch(const RayParams& p, bool grads, hipStream_t s) {
     const bool dec16 = p.a.planes_absmax != nullptr;
-    if (grads && p.a.state) return launch_n<true, false, true>(p, s);        // (no decoder in this variant)
-    if (grads) return dec16 ? launch_n<true, true>(p, s) : launch_n<true, false>(p, s);
-    return dec16 ? launch_n<false, true>(p, s) : launch_n<false, false>(p, s);
+    if (grads && p.a.state) return launch_n<true, false, true>(p, s);        // (no gather and no decoder in this variant)
+    // Developer switch HFAGP_DEV_RAY_TAPS_LEGACY=1: all three planes' taps on every lane of a gather quad (read at every call, so one
+    // process can time and compare both forms).
+    const char* dev = getenv("HFAGP_DEV_RAY_TAPS_LEGACY");
+    return dev && atoi(dev) == 1 ? launch_gather<true>(p, grads, dec16, s) : launch_gather<false>(p, grads, dec16, s);
 }
 
 }  // namespace hfagp

@@ -223,6 +223,45 @@ __device__ __forceinline__ void sample_taps(const RayParams& p, const float o3[3
     plane_taps(p.a, q[2], p.a.plane_axes == 0 ? q[0] : q[1], taps[2]);
 }
 
+// The same taps in the QUAD layout of the forward gather (raymarch.hip: lanes 4q..4q+3 hold the SAME sample q and differ only in
+// the channel group they load).  With sample_taps each of the four lanes computes all three planes' taps — three plane_taps of
+// ~50 vector instructions each, every one of them repeated by the three neighbours.  Here lane 4q + r computes plane min(r, 2) alone
+// and the quad exchanges the results with quad-permute DPP moves (v_mov_b32_dpp quad_perm:[pl,pl,pl,pl]: vector-ALU rate, no LDS):
+// one plane_taps + 24 moves instead of three plane_taps.  Every tap is produced by the same instruction sequence on the same inputs
+// as in sample_taps — only the lane that executes it differs — so the results are bit-identical.
+// The DPP moves read the neighbouring lanes' registers: callers run this with all 64 lanes active.
+struct QuadPlaneSel {         // which coordinates of the sample point this lane's plane projects (lane-constant: hoisted out of the ray loop)
+    bool x_is_z;              // gx = q[2] (plane 2), else q[0]
+    bool y_is_y;              // gy = q[1] (plane 0; plane 2 with plane_axes != 0), else whichever of q[0], q[2] gx is not
+};
+__device__ __forceinline__ QuadPlaneSel quad_plane_sel(const HfagpRaymarchArgs& a, int r) {      // r = lane & 3
+    QuadPlaneSel s;
+    s.x_is_z = r >= 2;
+    s.y_is_y = r == 0 || (r >= 2 && a.plane_axes != 0);
+    return s;
+}
+__device__ __forceinline__ void quad_bcast3(int v, int& v0, int& v1, int& v2) {      // v of the quad's lanes 0, 1, 2 -> all four lanes
+    v0 = __builtin_amdgcn_mov_dpp(v, 0x00, 0xf, 0xf, true);
+    v1 = __builtin_amdgcn_mov_dpp(v, 0x55, 0xf, 0xf, true);
+    v2 = __builtin_amdgcn_mov_dpp(v, 0xaa, 0xf, 0xf, true);
+}
+__device__ __forceinline__ void sample_taps_quad(const RayParams& p, const QuadPlaneSel& sel, const float o3[3], const float d3[3],
+                                                 float tz, PlaneTaps taps[3]) {
+    float q[3];
+    sample_point(p, o3, d3, tz, q);
+    const float gx = sel.x_is_z ? q[2] : q[0];                        // planes (x,y), (x,z), (z,x) [plane_axes 0] or (z,y): sample_taps
+    const float gy = sel.y_is_y ? q[1] : sel.x_is_z ? q[0] : q[2];
+    PlaneTaps mine;
+    plane_taps(p.a, gx, gy, mine);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        quad_bcast3(mine.idx[k], taps[0].idx[k], taps[1].idx[k], taps[2].idx[k]);
+        int w0, w1, w2;
+        quad_bcast3(__float_as_int(mine.w[k]), w0, w1, w2);
+        taps[0].w[k] = __int_as_float(w0); taps[1].w[k] = __int_as_float(w1); taps[2].w[k] = __int_as_float(w2);
+    }
+}
+
 // lane (j, g) accumulates channels 8g..8g+7 of the mean over the 3 planes of the bilinear samples
 __device__ __forceinline__ void gather8(const HfagpRaymarchArgs& a, int b, int g, const PlaneTaps taps[3], float f[8]) {
 #pragma unroll

@@ -1,5 +1,7 @@
 """Static instruction mix of every loop of one kernel in a hipcc -S listing (developer tool).
-usage: isa_mix.py listing.s mangled_kernel_name"""
+usage: isa_mix.py listing.s mangled_kernel_name [resource_remarks.txt]
+"dpp" counts the vector instructions that carry a DPP modifier (they are part of "valu" as well).  With the stderr of
+hipcc -Rpass-analysis=kernel-resource-usage as the third argument, the kernel's register / scratch / LDS lines are printed too."""
 import re
 import sys
 from collections import Counter
@@ -34,6 +36,8 @@ def mix(lines):
             c["trans"] += 1
         elif op.startswith("v_"):
             c["valu"] += 1
+            if "_dpp" in op or "quad_perm:" in l or "row_shr:" in l or "row_bcast:" in l:
+                c["dpp"] += 1
         elif op.startswith("s_"):
             c["salu"] += 1
         elif op.startswith("ds_"):
@@ -50,3 +54,12 @@ def mix(lines):
 print("whole kernel:", len(body), mix(body))
 for st, en in loops:
     print(f"loop lines {st}..{en} ({en - st}):", mix(body[st:en]))
+if len(sys.argv) > 3:
+    on = False
+    for l in open(sys.argv[3]):
+        m = re.search(r"Function Name: (\S+)", l)
+        if m:
+            on = m.group(1) == name
+        m = re.search(r"remark:\s+((?:TotalSGPRs|VGPRs|AGPRs|ScratchSize|Occupancy|SGPRs Spill|VGPRs Spill|LDS Size)[^:]*: \d+)", l)
+        if on and m:
+            print("resources:", m.group(1))
