@@ -215,6 +215,7 @@ SYMBOLS = {
     "hfagp_raymarch_bwd": (C.c_int, [C.POINTER(RaymarchBwdArgs), C.c_void_p]),
     "hfagp_raymarch_bwd_geom": (C.c_int, [C.POINTER(RaymarchBwdArgs), C.POINTER(RaymarchGeomGrads), C.c_void_p]),
     "hfagp_raymarch_bwd_rows_bytes": (C.c_size_t, [C.POINTER(RaymarchArgs)]),
+    "hfagp_raymarch_bwd_camera": (C.c_int, [C.POINTER(RaymarchBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hfagp_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "hfagp_adam_chunk": (C.c_int32, []),
     "hfagp_weight_prep_batch": (C.c_int, [C.POINTER(WeightPrepItem), C.c_int32, C.c_void_p]),

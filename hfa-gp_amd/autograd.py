@@ -344,6 +344,7 @@ class SynthesisFn(torch.autograd.Function):
         ctx.params = params
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape = ws.shape
+        ctx.c_dtype = c.dtype
         if geometry:
             ctx.set_materialize_grads(False)         # an output the loss does not use hands backward None, not a zero image
             return img, rgb_raw, depth, mask[0]
@@ -396,11 +397,19 @@ class SynthesisFn(torch.autograd.Function):
         # per workgroup (an LDS reduction over its eight waves: no change either way) — it is WHERE they land, not how many.
         # HFAGP_DEV_DEC_DIRECT=1 re-enables it for A/B timing)
         dec_direct = ctx.pg and os.environ.get("HFAGP_DEV_DEC_DIRECT", "0") == "1" and all(bw._direct(p) for p in dec_prm)
+        need_c = ctx.needs_input_grad[1]
+        rec_out = [] if need_c else None
         rb = gen._timed("raymarch_bwd", float(b), ops.raymarch_bwd, g_feat.view(b, res * res, 32), tape["planes"],
                         u_strat=tape["u_strat"], u_imp=tape["u_imp"], decoder_grads=ctx.pg,
                         planes_absmax=tape.get("planes_absmax"), state=tape.get("ray_state"),
-                        dec_out=tuple(p.grad for p in dec_prm) if dec_direct else None,
+                        dec_out=tuple(p.grad for p in dec_prm) if dec_direct else None, rec_out=rec_out,
                         **geom, **gen._render_args(tape["c"]))
+        d_c = None
+        if need_c:      # the camera label: positional derivative of the gather along every ray, then the adjoint of the ray generation
+            d_c2w, d_intr, _ = gen._timed("raymarch_bwd_camera", float(b), ops.raymarch_bwd_camera, g_feat.view(b, res * res, 32),
+                                          tape["planes"], rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
+                                          planes_absmax=tape.get("planes_absmax"), **gen._render_args(tape["c"]))
+            d_c = torch.cat((d_c2w, d_intr), 1).to(ctx.c_dtype)
         if ctx.pg:
             d_planes, dec = rb
             for prm, g in zip(dec_prm, dec):
@@ -430,7 +439,7 @@ class SynthesisFn(torch.autograd.Function):
         bw.release_ready()
         ctx.tape = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return (d_ws, None, None, None, None) + pgrads
+        return (d_ws, d_c, None, None, None) + pgrads
 
 
 class SynthesisGeomFn(SynthesisFn):

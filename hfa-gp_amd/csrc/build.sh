@@ -32,6 +32,7 @@ for src in elementwise modconv modconv_bf16 smallconv upconv_fir upfir_lean torg
 units+=(planes_query)
 units+=(marching_cubes)
 units+=(weight_prep)
+units+=(raymarch_camera)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

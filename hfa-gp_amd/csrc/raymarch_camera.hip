@@ -1,0 +1,328 @@
+// Camera gradient of the ray marcher: dL/d(cam2world, intrinsics) from the per-sample records pass 1 of the backward leaves
+// in `rec` (depth, omega, d sigma per sample: raymarch.hip) and the upstream feature gradient.
+//
+//   raymarch_bwd_camera_kernel   per 16-sample tile: gather -> decoder forward -> decoder adjoint = dL/dF (the arithmetic of
+//                                raymarch_bwd_df_kernel, same shared device functions), then the POSITIONAL derivative of the
+//                                bilinear gather,  dL/dp = (2 / box_warp) sum_planes (dL/dix, dL/diy) routed to the two
+//                                coordinates the plane projects, summed along the ray:  dL/do = sum_s dL/dp_s,
+//                                dL/dd = sum_s t_s dL/dp_s  ->  ray_grad[ray][6].  One writer per ray, plain stores.
+//   camera_reduce_kernel         adjoint of ray_setup (raymarch_common.h) summed over a frame's rays in a fixed order
+//                                -> d_cam2world[b][16], d_intrinsics[b][9].
+// The sample depths carry no gradient (stratified: uniforms and constants; importance: detached as in EG3D), so the camera
+// reaches the loss through the sample POSITIONS alone.  A pass of its own, not a flag on the dL/dF producers: it is the same
+// whichever pass-2 form ran, and the producers' instantiations stay what they are.
+#include "raymarch_common.h"
+
+namespace hfagp {
+
+constexpr int kCamWaves = 4;
+constexpr int kCamReduceThreads = 256;
+
+// plane_taps with what the derivative needs next to the texel indices: the fractional parts and each tap's validity (the
+// weights of plane_taps are products of these; a tap outside the plane is a zero texel)
+struct PlaneTapsD {
+    int idx[4];          // nw, ne, sw, se (clamped into the plane: always loadable)
+    bool ok[4];
+    float fx, fy;
+};
+__device__ __forceinline__ void plane_taps_d(const HfagpRaymarchArgs& a, float gx, float gy, PlaneTapsD& t) {
+    const float fW = (float)a.W, fH = (float)a.H;
+    float ix, iy;
+    plane_pixel(a, gx, gy, ix, iy);
+    const float fx0 = floorf(ix), fy0 = floorf(iy);
+    t.fx = __fsub_rn(ix, fx0);
+    t.fy = __fsub_rn(iy, fy0);
+    const int x0 = (int)fminf(fmaxf(fx0, -2.f), fW + 1.f), y0 = (int)fminf(fmaxf(fy0, -2.f), fH + 1.f);
+    const int x1 = x0 + 1, y1 = y0 + 1;
+    const bool vx0 = x0 >= 0 && x0 < a.W, vx1 = x1 >= 0 && x1 < a.W;
+    const bool vy0 = y0 >= 0 && y0 < a.H, vy1 = y1 >= 0 && y1 < a.H;
+    const int cx0 = min(max(x0, 0), a.W - 1), cx1 = min(max(x1, 0), a.W - 1);
+    const int cy0 = min(max(y0, 0), a.H - 1), cy1 = min(max(y1, 0), a.H - 1);
+    t.ok[0] = vx0 && vy0; t.ok[1] = vx1 && vy0; t.ok[2] = vx0 && vy1; t.ok[3] = vx1 && vy1;
+    t.idx[0] = cy0 * a.W + cx0; t.idx[1] = cy0 * a.W + cx1;
+    t.idx[2] = cy1 * a.W + cx0; t.idx[3] = cy1 * a.W + cx1;
+}
+
+template <int S, bool DEC16>
+__global__ void __launch_bounds__(kCamWaves * 64, 2)
+raymarch_bwd_camera_kernel(const RayParams p, float* __restrict__ ray_grad) {
+    __shared__ float w1t[4 * 8 * 64];
+    __shared__ float w0t[2 * 16 * 64];
+    __shared__ float wfwd[kDecLdsRows * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const HfagpRaymarchArgs& a = p.a;
+    const int j = lane & 15, g = lane >> 4;
+    const int R = a.res * a.res;
+    constexpr int NT = S / 16;
+    if (wave == 0) {
+        DecoderRegs dec;
+        load_decoder(a, j, g, dec);
+        if constexpr (DEC16) {
+            Dec16Regs d16;
+            make_dec16(dec, a.planes_absmax, lane, d16);
+            store_dec16_lds(d16, wfwd, lane);
+        } else {
+            store_decoder_lds(dec, wfwd, lane);
+        }
+    }
+    if constexpr (DEC16) {
+        build_grad16_lds(a, w1t, w0t, lane, wave, kCamWaves);
+    } else {
+        const float g0 = a.decoder_lr_mul * 0.17677669529663687f, g1 = a.decoder_lr_mul * 0.125f;
+        for (int i = threadIdx.x; i < 4 * 8 * 64; i += kCamWaves * 64) {
+            const int l = i & 63, st = (i >> 6) & 7, mt = i >> 9, jj = l & 15, gg = l >> 4;
+            w1t[i] = a.dec_w1[(1 + 16 * (st >> 2) + 4 * gg + (st & 3)) * 64 + 16 * mt + jj] * g1;
+        }
+        for (int i = threadIdx.x; i < 2 * 16 * 64; i += kCamWaves * 64) {
+            const int l = i & 63, st = (i >> 6) & 15, ft = i >> 10, jj = l & 15, gg = l >> 4;
+            w0t[i] = a.dec_w0[(16 * (st >> 2) + 4 * gg + (st & 3)) * 32 + 16 * ft + jj] * g0;
+        }
+    }
+    __syncthreads();
+    // d pixel / d grid coordinate (plane_pixel) times the mean over the planes
+    const float sx = (float)a.W * 0.5f * 0.3333333333333333f, sy = (float)a.H * 0.5f * 0.3333333333333333f;
+    const RaySchedule sch = ray_schedule((long long)p.total_rays, wave, kCamWaves);
+    for (long long rp = sch.begin; rp < sch.end; rp += sch.stride) {
+        int b, pi, pj;
+        ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
+        const int ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+        float o3[3], d3[3];
+        ray_setup(a, b, pi, pj, o3, d3);
+        float4 gfeat[2];
+#pragma unroll
+        for (int ot = 0; ot < 2; ++ot) gfeat[ot] = load_g_feat4(p, (size_t)ray * 32 + 16 * ot + 4 * g);
+        // this lane's share (its 8 channels of its samples) of dL/dq summed along the ray, plain and depth-weighted
+        float acc_o[3] = {0.f, 0.f, 0.f}, acc_d[3] = {0.f, 0.f, 0.f};
+        float zq = p.rec[((size_t)ray * S + (lane >> 2)) * 4];
+#pragma unroll 1
+        for (int tt = 0; tt < NT; ++tt) {
+            const int s = 16 * tt + j;
+            int ln = lane;
+            asm volatile("" : "+v"(ln));       // the weight images are read per tile, not hoisted into registers
+            const float zq_cur = zq;
+            zq = p.rec[((size_t)ray * S + 16 * min(tt + 1, NT - 1) + (lane >> 2)) * 4];
+            const float4 rec = *reinterpret_cast<const float4*>(p.rec + ((size_t)ray * S + s) * 4);   // depth, omega, dsigma
+            float f[8];
+            {
+                PlaneTaps tq[3];
+                sample_taps(p, o3, d3, zq_cur, tq);
+                gather8(a, b, lane & 3, tq, f);
+                const int src = 4 * j + g;
+#pragma unroll
+                for (int cc = 0; cc < 8; ++cc) f[cc] = __shfl(f[cc], src);
+            }
+            f32x4 hp[4], h[4], o[2];
+            float sigma;
+            if constexpr (DEC16) decoder_fwd16_lds<true>(wfwd, ln, f, hp, h, sigma, o);
+            else decoder_fwd_lds<true>(wfwd, lane, f, hp, h, sigma, o);
+            f32x4 dO[2];
+#pragma unroll
+            for (int ot = 0; ot < 2; ++ot) {
+                const float4 gf = gfeat[ot];
+                const float gv[4] = {gf.x, gf.y, gf.z, gf.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float sg = sigmoid_f(o[ot][r]);
+                    dO[ot][r] = rec.y * 2.f * gv[r] * 1.002f * sg * (1.f - sg);
+                }
+            }
+            f32x4 dH[4];
+            f32x4 dF2[2];
+            if constexpr (DEC16) decoder_bwd16_lds(wfwd, w1t, w0t, ln, dO, rec.z, hp, dH, dF2);
+#pragma unroll
+            for (int mt = 0; mt < (DEC16 ? 0 : 4); ++mt) {
+                const float* ws_ = wfwd + (48 + mt * 4) * 64 + lane;
+                dH[mt] = f32x4{ws_[0] * rec.z, ws_[64] * rec.z, ws_[128] * rec.z, ws_[192] * rec.z};
+#pragma unroll
+                for (int ot = 0; ot < 2; ++ot)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float wA = w1t[(mt * 8 + ot * 4 + r) * 64 + lane];
+                        dH[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dO[ot][r], dH[mt], 0, 0, 0);
+                    }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dH[mt][r] *= sigmoid_f(hp[mt][r]);
+            }
+            if constexpr (!DEC16) {
+#pragma unroll
+                for (int ft = 0; ft < 2; ++ft) {
+                    dF2[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float wA = w0t[(ft * 16 + mt * 4 + r) * 64 + lane];
+                            dF2[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dH[mt][r], dF2[ft], 0, 0, 0);
+                        }
+                }
+            }
+            // ---- positional derivative: lane (j, g) holds dL/dF of channels 16 ft + 4 g + r of sample j (depth rec.x) and forms
+            // its share of P_k = <dL/dF, texel_k> for the twelve taps (lines the gather above has just pulled in)
+            float q[3];
+            sample_point(p, o3, d3, rec.x, q);
+            float dq[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl) {
+                float gx, gy;
+                plane_coords(a, q, pl, gx, gy);
+                PlaneTapsD t;
+                plane_taps_d(a, gx, gy, t);
+                const char* base = reinterpret_cast<const char*>(a.planes + ((size_t)(b * 3 + pl) * a.H * a.W) * 32);
+                float4 v0[4], v1[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned off = ((unsigned)t.idx[k] * 32u + 4u * g) * 4u;      // < 2^32: one plane
+                    v0[k] = *reinterpret_cast<const float4*>(base + off);
+                    v1[k] = *reinterpret_cast<const float4*>(base + off + 64);
+                }
+                float P[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    float acc = dF2[0][0] * v0[k].x;
+                    acc = fmaf(dF2[0][1], v0[k].y, acc);
+                    acc = fmaf(dF2[0][2], v0[k].z, acc);
+                    acc = fmaf(dF2[0][3], v0[k].w, acc);
+                    acc = fmaf(dF2[1][0], v1[k].x, acc);
+                    acc = fmaf(dF2[1][1], v1[k].y, acc);
+                    acc = fmaf(dF2[1][2], v1[k].z, acc);
+                    acc = fmaf(dF2[1][3], v1[k].w, acc);
+                    P[k] = t.ok[k] ? acc : 0.f;
+                }
+                const float dix = ((P[1] - P[0]) * (1.f - t.fy) + (P[3] - P[2]) * t.fy) * sx;
+                const float diy = ((P[2] - P[0]) * (1.f - t.fx) + (P[3] - P[1]) * t.fx) * sy;
+                // planes (x,y), (x,z), (z,x) [plane_axes 0] or (z,y): plane_coords
+                if (pl == 0) { dq[0] += dix; dq[1] += diy; }
+                else if (pl == 1) { dq[0] += dix; dq[2] += diy; }
+                else {
+                    dq[2] += dix;
+                    if (a.plane_axes == 0) dq[0] += diy; else dq[1] += diy;
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                acc_o[k] += dq[k];
+                acc_d[k] = fmaf(rec.x, dq[k], acc_d[k]);
+            }
+        }
+        // the ray's 64 lane shares (16 samples per tile x 4 channel groups) in a fixed butterfly order; q = coord_scale * p
+        float out[6];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            out[k] = wave_sum(acc_o[k]) * p.coord_scale;
+            out[3 + k] = wave_sum(acc_d[k]) * p.coord_scale;
+        }
+        if (lane == 0) {
+            float* dst = ray_grad + (size_t)ray * 6;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) dst[k] = out[k];
+        }
+    }
+}
+
+// One workgroup per frame.  Thread t walks rays t, t + 256, ...; 17 partial sums (12 of cam2world rows 0-2, fx, skew, cx, fy, cy),
+// then a fixed-order tree over the threads: two calls give the same bits.
+__global__ void __launch_bounds__(kCamReduceThreads)
+camera_reduce_kernel(const HfagpRaymarchArgs a, const float* __restrict__ ray_grad, float* __restrict__ d_cam2world,
+                     float* __restrict__ d_intrinsics) {
+    __shared__ float red[17][kCamReduceThreads];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int R = a.res * a.res;
+    const float* M = a.cam2world + b * 16;
+    const float* K = a.intrinsics + b * 9;
+    const float fx = K[0], sk = K[1], cx = K[2], fy = K[4], cy = K[5];
+    const float inv_res = 1.0f / (float)a.res, half_res = 0.5f / (float)a.res;
+    float acc[17];
+#pragma unroll
+    for (int k = 0; k < 17; ++k) acc[k] = 0.f;
+    for (int i = tid; i < R; i += kCamReduceThreads) {
+        const int pi = i / a.res, pj = i % a.res;
+        // ray_setup's arithmetic
+        const float xc = __fadd_rn(__fmul_rn((float)pj, inv_res), half_res);
+        const float yc = __fadd_rn(__fmul_rn((float)pi, inv_res), half_res);
+        const float xl = __fdiv_rn(__fsub_rn(__fadd_rn(__fsub_rn(xc, cx), __fdiv_rn(__fmul_rn(cy, sk), fy)),
+                                             __fdiv_rn(__fmul_rn(sk, yc), fy)), fx);
+        const float yl = __fdiv_rn(__fsub_rn(yc, cy), fy);
+        float v[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float wv = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(M[4 * k], xl), __fmul_rn(M[4 * k + 1], yl)),
+                                                 M[4 * k + 2]), M[4 * k + 3]);
+            v[k] = __fsub_rn(wv, M[4 * k + 3]);
+        }
+        const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(v[0], v[0]), __fmul_rn(v[1], v[1])),
+                                                     __fmul_rn(v[2], v[2]))), 1e-12f);
+        const float d0 = __fdiv_rn(v[0], nrm), d1 = __fdiv_rn(v[1], nrm), d2 = __fdiv_rn(v[2], nrm);
+        const float* rg = ray_grad + ((size_t)b * R + i) * 6;
+        const float go[3] = {rg[0], rg[1], rg[2]};
+        const float gd[3] = {rg[3], rg[4], rg[5]};
+        // d = v / |v|:  gv = (g_d - d (d . g_d)) / |v|
+        const float dot = d0 * gd[0] + d1 * gd[1] + d2 * gd[2];
+        const float inv = 1.f / nrm;
+        const float gv[3] = {(gd[0] - d0 * dot) * inv, (gd[1] - d1 * dot) * inv, (gd[2] - d2 * dot) * inv};
+        float dxl = 0.f, dyl = 0.f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            acc[4 * k] += gv[k] * xl;
+            acc[4 * k + 1] += gv[k] * yl;
+            acc[4 * k + 2] += gv[k];
+            acc[4 * k + 3] += go[k];            // (column 3 enters v as w - o: its two contributions cancel)
+            dxl = fmaf(gv[k], M[4 * k], dxl);
+            dyl = fmaf(gv[k], M[4 * k + 1], dyl);
+        }
+        // xl = (xc - cx - sk yl) / fx,  yl = (yc - cy) / fy
+        const float dn = dxl / fx;
+        const float dyl_t = dyl - sk * dn;
+        acc[12] -= dn * xl;                     // fx
+        acc[13] -= dn * yl;                     // skew
+        acc[14] -= dn;                          // cx
+        acc[15] -= dyl_t * yl / fy;             // fy
+        acc[16] -= dyl_t / fy;                  // cy
+    }
+#pragma unroll
+    for (int k = 0; k < 17; ++k) red[k][tid] = acc[k];
+    __syncthreads();
+    for (int half = kCamReduceThreads / 2; half > 0; half >>= 1) {
+        if (tid < half) {
+#pragma unroll
+            for (int k = 0; k < 17; ++k) red[k][tid] += red[k][tid + half];
+        }
+        __syncthreads();
+    }
+    if (tid < 16) d_cam2world[b * 16 + tid] = tid < 12 ? red[tid][0] : 0.f;
+    if (tid < 9) {
+        const int src = tid == 0 ? 12 : tid == 1 ? 13 : tid == 2 ? 14 : tid == 4 ? 15 : tid == 5 ? 16 : -1;
+        d_intrinsics[b * 9 + tid] = src >= 0 ? red[src][0] : 0.f;
+    }
+}
+
+template <int S>
+static void launch_camera(const RayParams& p, float* ray_grad, hipStream_t s) {
+    const long long ntiles = (long long)p.total_rays * (S / 16);
+    const unsigned blocks = (unsigned)std::min<long long>((ntiles + kCamWaves - 1) / kCamWaves, (long long)kNumCU * 6);
+    if (p.a.planes_absmax) raymarch_bwd_camera_kernel<S, true><<<blocks, kCamWaves * 64, 0, s>>>(p, ray_grad);
+    else raymarch_bwd_camera_kernel<S, false><<<blocks, kCamWaves * 64, 0, s>>>(p, ray_grad);
+}
+
+}  // namespace hfagp
+
+using namespace hfagp;
+
+extern "C" int hfagp_raymarch_bwd_camera(const HfagpRaymarchBwdArgs* a, float* ray_grad, float* d_cam2world, float* d_intrinsics,
+                                         void* stream) {
+    HFAGP_REQUIRE(a && a->rec && ray_grad, HFAGP_EBADARG, "raymarch_bwd_camera: null pointer");
+    HFAGP_REQUIRE((d_cam2world != nullptr) == (d_intrinsics != nullptr), HFAGP_EBADARG,
+                  "raymarch_bwd_camera: d_cam2world and d_intrinsics go together (both or neither)");
+    RayParams p;
+    int rc = fill_ray_params(&a->fwd, p, "raymarch_bwd_camera");
+    if (rc != HFAGP_OK) return rc;
+    p.g_feat = a->g_feat;
+    p.rec = a->rec;
+    hipStream_t s = (hipStream_t)stream;
+    const int S = a->fwd.Sc + a->fwd.Sf;
+    if (S == 96) launch_camera<96>(p, ray_grad, s);
+    else if (S == 64) launch_camera<64>(p, ray_grad, s);
+    else launch_camera<32>(p, ray_grad, s);
+    if (d_cam2world)
+        camera_reduce_kernel<<<(unsigned)a->fwd.B, kCamReduceThreads, 0, s>>>(p.a, ray_grad, d_cam2world, d_intrinsics);
+    return check_launch("raymarch_bwd_camera");
+}

@@ -708,10 +708,6 @@ class TriPlaneGenerator(nn.Module):
             raise RuntimeError(f"TriPlaneGenerator.synthesis: tensors live on {ws.device} but the current device is "
                                f"cuda:{torch.cuda.current_device()}; the kernels are enqueued on the CURRENT device's "
                                f"stream — wrap the call in `with torch.cuda.device(ws.device):`")
-        if c.requires_grad and torch.is_grad_enabled():
-            raise RuntimeError("TriPlaneGenerator.synthesis: the camera label `c` requires grad, but the renderer "
-                               "has no camera gradient (HFA-GP never optimises the pose through the generator); "
-                               "detach it explicitly")
         if ws.shape[1:] != (cfg.num_ws, cfg.w_dim) or c.shape[1] != cfg.c_dim:
             raise ValueError(f"expected ws [B,{cfg.num_ws},{cfg.w_dim}] and c [B,{cfg.c_dim}], got "
                              f"{tuple(ws.shape)} and {tuple(c.shape)}")
@@ -760,7 +756,8 @@ class TriPlaneGenerator(nn.Module):
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                   return_planes: bool = False, geometry: bool = False, **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
-        HFA-GP) and w.r.t. the generator parameters that require grad (after `tune_generator()`).
+        HFA-GP), w.r.t. the generator parameters that require grad (after `tune_generator()`) and w.r.t. the camera label `c`
+        when it requires grad (pose refinement; the importance depths are detached as in EG3D).
         `geometry=True`: the dict also has 'image_mask' [B,1,r,r] (the per-ray opacity, sum of the compositing weights), and
         'image_depth' and 'image_mask' are differentiable — silhouette / matting losses and depth priors reach `ws` and the
         generator.  Off (the default), 'image_depth' carries no gradient and the dict has EG3D's three keys."""
@@ -772,18 +769,20 @@ class TriPlaneGenerator(nn.Module):
                    "image_raw": torch.zeros(0, 3, r, r, device=dev), "image_depth": torch.zeros(0, 1, r, r, device=dev)}
             if geometry:
                 out["image_mask"] = torch.zeros(0, 1, r, r, device=dev)
-            out["image"] = out["image"] + 0.0 * ws.sum()          # keeps the autograd edge to ws
+            out["image"] = out["image"] + 0.0 * ws.sum() + 0.0 * c.sum()      # keeps the autograd edges to ws and c
             return out
         params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
-        need_grad = torch.is_grad_enabled() and (ws.requires_grad or any(p.requires_grad for p in params))
+        cam_grad = torch.is_grad_enabled() and c.requires_grad
+        need_grad = torch.is_grad_enabled() and (ws.requires_grad or cam_grad or any(p.requires_grad for p in params))
+        c_in = c if cam_grad else c.detach()
         if need_grad:
             from .autograd import SynthesisFn
             if geometry:
                 from .autograd import SynthesisGeomFn
-                img, rgb_raw, depth, mask = SynthesisGeomFn.apply(ws, c.detach(), u_strat, u_imp, self, *params)
+                img, rgb_raw, depth, mask = SynthesisGeomFn.apply(ws, c_in, u_strat, u_imp, self, *params)
                 out = {"image": img, "image_raw": rgb_raw, "image_depth": depth, "image_mask": mask}
             else:
-                img, rgb_raw, depth = SynthesisFn.apply(ws, c.detach(), u_strat, u_imp, self, *params)
+                img, rgb_raw, depth = SynthesisFn.apply(ws, c_in, u_strat, u_imp, self, *params)
                 out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
             if return_planes:
                 out["planes"], out["feature_image"] = self._last_extras

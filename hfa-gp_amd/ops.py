@@ -1211,7 +1211,7 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
                  planes_absmax: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
                  two_kernel: bool = False, rows: Optional[bool] = None, dec_out=None, _out=None,
                  g_depth: Optional[torch.Tensor] = None, g_wsum: Optional[torch.Tensor] = None,
-                 depth_range: Optional[torch.Tensor] = None):
+                 depth_range: Optional[torch.Tensor] = None, rec_out: Optional[list] = None):
     """g_feat [B,R,32] → d planes [B,3,H,W,32].  ``g_depth`` / ``g_wsum`` [B,R]: gradients w.r.t. the CLAMPED expected depth and
     the opacity `raymarch` returns, added to the compositing adjoint (hfagp.h HfagpRaymarchGeomGrads); ``depth_range``
     (`ops.depth_range(tminmax)`, required with g_depth) is the forward's batch-global clamp range; g_feat may be None when one of
@@ -1221,7 +1221,8 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
     timing), False = the scatter kernels.  The sort's scratch (~0.9 GB per frame at 128^2 rays x 96 samples) is bounded by
     `rows_scratch_cap()`: a batch that needs more is processed in frame chunks (round 6; rounds 5 fell back to the 2 x slower scatter
     kernels above 16 GiB, i.e. from B = 19 on, without a word); where the sort does not apply at all (more than 8192 bins per frame)
-    or its scratch cannot be allocated, the scatter kernels run and say so once."""
+    or its scratch cannot be allocated, the scatter kernels run and say so once.  ``rec_out``: a list that receives pass 1's
+    per-sample records [B,R,Sc+Sf,4] whatever the return form is (`raymarch_bwd_camera` reads them)."""
     _chk(planes, "planes")
     b, _, h, w, _ = planes.shape
     r = res * res
@@ -1239,6 +1240,8 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
     else:
         d_planes = torch.zeros_like(planes)
         rec = torch.empty(b, r, sc + sf, 4, device=planes.device, dtype=torch.float32)
+    if rec_out is not None:
+        rec_out.append(rec)
     planes_absmax = _decoder_bound(planes, decoder_precision, planes_absmax)      # (one bound for every chunk of the batch)
     a = L.RaymarchBwdArgs()
     f = a.fwd
@@ -1317,6 +1320,43 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
     if decoder_grads:
         return d_planes, dec
     return (d_planes, rec) if return_rec else d_planes
+
+
+def raymarch_bwd_camera(g_feat: Optional[torch.Tensor], planes: torch.Tensor, rec: torch.Tensor, cam2world, intrinsics, u_strat,
+                        u_imp, dec_w0, dec_b0, dec_w1, dec_b1, res: int, ray_start: float, ray_end: float, box_warp: float,
+                        decoder_lr_mul: float = 1.0, plane_axes: int = 0, white_back: bool = False,
+                        decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None):
+    """The camera gradient of the renderer (hfagp_raymarch_bwd_camera) → (d cam2world [B,16], d intrinsics [B,9], ray_grad [B,R,6]:
+    d origin, d direction per ray).  ``g_feat`` and the other arguments as in the `raymarch_bwd` call that wrote ``rec`` (its
+    ``rec_out=`` / ``return_rec=True``): the depth, opacity and white_back terms are already in the records.  Independent of which
+    pass-2 form that call ran; no atomics, two calls return the same bits."""
+    _chk(planes, "planes")
+    b, _, h, w, _ = planes.shape
+    r = res * res
+    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    dev = planes.device
+    if _chk(rec, "rec").shape != (b, r, sc + sf, 4):
+        raise RuntimeError(f"raymarch_bwd_camera: rec must be [B, R, Sc + Sf, 4] = [{b}, {r}, {sc + sf}, 4], got {tuple(rec.shape)}")
+    if g_feat is not None and _chk(g_feat, "g_feat").shape != (b, r, 32):
+        raise RuntimeError(f"raymarch_bwd_camera: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
+    d_c2w = torch.empty(b, 16, device=dev, dtype=torch.float32)
+    d_intr = torch.empty(b, 9, device=dev, dtype=torch.float32)
+    ray_grad = torch.empty(b, r, 6, device=dev, dtype=torch.float32)
+    if b == 0:
+        return d_c2w, d_intr, ray_grad
+    a = L.RaymarchBwdArgs()
+    f = a.fwd
+    f.planes, f.cam2world, f.intrinsics = _ptr(planes), _ptr(_chk(cam2world, "cam2world")), _ptr(_chk(intrinsics, "intrinsics"))
+    f.u_strat, f.u_imp = _ptr(_chk(u_strat, "u_strat")), _ptr(_chk(u_imp, "u_imp"))
+    f.dec_w0, f.dec_b0, f.dec_w1, f.dec_b1 = _ptr(dec_w0), _ptr(dec_b0), _ptr(dec_w1), _ptr(dec_b1)
+    f.B, f.H, f.W, f.res, f.Sc, f.Sf = b, h, w, res, sc, sf
+    f.plane_axes, f.white_back = plane_axes, int(white_back)
+    f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
+    f.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
+    a.g_feat, a.rec = _ptr(g_feat), _ptr(rec)
+    L.check(L.lib().hfagp_raymarch_bwd_camera(C.byref(a), _ptr(ray_grad), _ptr(d_c2w), _ptr(d_intr), _stream()),
+            "raymarch_bwd_camera")
+    return d_c2w, d_intr, ray_grad
 
 
 # ----------------------------------------------------------------------------- loss side of the fitting step

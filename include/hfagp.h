@@ -38,6 +38,7 @@
  * backward (the reference gets these from torch.autograd through EG3D's custom ops; g_loss.backward(), code/trainer_rgb.py:93):
  *   hfagp_raymarch_bwd      <- autograd of the renderer: grid_sample / decoder / compositing adjoints
  *   hfagp_raymarch_bwd_geom <- the same with gradients of the expected depth and the opacity (silhouette / depth losses)
+ *   hfagp_raymarch_bwd_camera <- autograd of RaySampler + grid_sample w.r.t. the sample positions: the gradient of the camera label
  *   hfagp_modconv_fwd modes HFAGP_CONV3X3_BWD / HFAGP_CONVS2_BWD <- conv2d_gradfix data gradients (the same GEMM kernel)
  *   hfagp_conv_wgrad (+ _workspace_bytes) <- conv2d_gradfix weight gradients
  *   hfagp_pointwise_bwd     <- bias_act backward + noise-strength / bias gradients + demodulation adjoint of a SynthesisLayer
@@ -636,6 +637,16 @@ int hfagp_raymarch_bwd_geom(const HfagpRaymarchBwdArgs* a, const HfagpRaymarchGe
  * 0 = the sort + gather form does not apply (more than 8192 bins per frame: planes beyond ~256 x 341 texels, or more than
  * 2^31 slots): leave rows_scratch NULL.  At 2 frames x 128^2 rays x 96 samples on mirrored 256^2 planes: 1.8 GB.            */
 size_t hfagp_raymarch_bwd_rows_bytes(const HfagpRaymarchArgs* fwd);
+
+/* Camera gradient (additive to ABI 15).  After hfagp_raymarch_bwd[_geom] on the same arguments and stream: a->rec holds pass 1's
+ * records (the depth, opacity and white_back terms are folded into them).  a->d_planes, rows_scratch, df_scratch and d_dec_* are
+ * ignored.  Per sample the positional derivative of the tri-plane gather (the function the forward evaluated: grid_sample
+ * bilinear, zeros padding, a tap outside the plane contributes nothing), summed along the ray:
+ * ray_grad: [B][R][6] floats, written (d origin, d direction per ray; the sample depths carry no gradient, as in EG3D).
+ * d_cam2world [B][16], d_intrinsics [B][9]: written, both or neither (NULL: only ray_grad) — the adjoint of the ray generation
+ * summed over each frame's rays; row 3 of cam2world and intrinsics entries 3, 6, 7, 8 are written as 0.  No atomics: two calls
+ * give the same bits.  HFAGP_EBADARG, nothing launched: a, a->rec or ray_grad NULL; one of the two camera outputs alone.     */
+int hfagp_raymarch_bwd_camera(const HfagpRaymarchBwdArgs* a, float* ray_grad, float* d_cam2world, float* d_intrinsics, void* stream);
 
 /* ------------------------------------------------------------------ gradients w.r.t. the generator weights
  * (needed once HFA-GP calls tune_generator(), trainer_rgb.py:69-71)                                       */
