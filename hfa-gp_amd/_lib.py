@@ -41,6 +41,14 @@ class PlanesQueryArgs(C.Structure):
         [("decoder_lr_mul", C.c_float), ("box_warp", C.c_double), ("cube_length", C.c_double)]
 
 
+class PlanesQueryBwdArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("planes", "coords", "dec_w0", "dec_b0", "dec_w1", "dec_b1", "planes_absmax",
+                                          "g_sigma", "g_rgb", "d_planes", "d_coords",
+                                          "d_dec_w0", "d_dec_b0", "d_dec_w1", "d_dec_b1")] + \
+        [("M", C.c_int64)] + [(n, C.c_int32) for n in ("B", "H", "W", "Bc", "plane_axes")] + \
+        [("decoder_lr_mul", C.c_float), ("box_warp", C.c_double)]
+
+
 class MarchingCubesArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("volume", "workspace", "counts", "verts", "faces")] + \
         [(n, C.c_int64) for n in ("workspace_bytes", "vert_capacity", "face_capacity")] + \
@@ -178,6 +186,7 @@ SYMBOLS = {
     "hfagp_last_error": (C.c_char_p, []),
     "hfagp_raymarch_fwd": (C.c_int, [C.POINTER(RaymarchArgs), C.c_void_p]),
     "hfagp_planes_query": (C.c_int, [C.POINTER(PlanesQueryArgs), C.c_void_p]),
+    "hfagp_planes_query_bwd": (C.c_int, [C.POINTER(PlanesQueryBwdArgs), C.c_void_p]),
     "hfagp_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "hfagp_marching_cubes_count": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),
     "hfagp_marching_cubes_emit": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),

@@ -324,6 +324,40 @@ class _Backward:
         self.pending = []
 
 
+def _backbone_backward(bw: _Backward, gen, backbone_tape, d_planes: torch.Tensor, b: int, dev) -> None:
+    """d planes [B,3,R,R,32] → the backbone blocks, last block first, then the style gradients of the whole pass into bw.d_ws.
+    Shared by the backward of `synthesis` (after the renderer's adjoint) and of `sample_mixed(differentiable=True)`."""
+    g_img_b = ops.planes_to_nhwc(d_planes)
+    dxs, nxt = None, None
+    walk = list(reversed(backbone_tape))
+    side = gen.side_stream(b, dev) if all(not r["rgb"]["small"] for r in walk) else None
+    ahead = bw.image_chain(walk, g_img_b, side) if side is not None else None
+    for k, rec in enumerate(walk):
+        s_next = nxt["styles"] if nxt is not None else None
+        dxs_new, c0, g_img_b = bw.block(rec, g_img_b, dxs, s_next, nxt, ahead[k] if ahead is not None else None)
+        if nxt is not None:
+            bw.finish_layer(nxt)
+        dxs, nxt = dxs_new, c0
+        bw.release_ready()
+    if side is not None:
+        torch.cuda.current_stream(dev).wait_stream(side)     # (nothing of this pass is left on the side stream)
+    bw.flush_styles()
+    bw.release_ready()
+
+
+def _query_backward(gen, planes, coords, pam, g_sigma, g_rgb, d_planes, need_coords: bool, dec):
+    """ops.planes_query_bwd of a query that rode on `planes`: the plane gradient is added INTO d_planes (None: fresh zeros) and the
+    decoder gradients into the tensors `dec` (None: the generator is frozen) → (d_planes, d coords shaped like coords or None)."""
+    b, m = planes.shape[0], coords.shape[1]
+    d_planes, d_co, _ = ops.planes_query_bwd(
+        planes, coords, None if g_sigma is None else g_sigma.float().reshape(b, m, 1).contiguous(),
+        None if g_rgb is None else g_rgb.float().contiguous(), planes_absmax=pam, d_planes=d_planes, coords_grad=need_coords,
+        decoder_grads=dec is not None, dec_out=dec, **gen._query_kwargs())
+    if d_co is not None and coords.shape[0] != b:
+        d_co = d_co.sum(0, keepdim=True)          # one point set for every identity
+    return d_planes, d_co
+
+
 class SynthesisFn(torch.autograd.Function):
     """inputs: ws, c, u_strat, u_imp, gen, *generator parameters (listed only so that autograd can hand their
     gradients back when the generator is being tuned; the forward reads them from `gen`)."""
@@ -333,18 +367,30 @@ class SynthesisFn(torch.autograd.Function):
         return SynthesisFn._forward(ctx, False, ws, c, u_strat, u_imp, gen, params)
 
     @staticmethod
-    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params):
+    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params, query=None):
         tape = {}
         ws_c = ws.detach().float().contiguous()
         with torch.no_grad():
             img, rgb_raw, depth, planes, feat_img, *mask = gen._forward_impl(ws_c, c.detach().float().contiguous(), u_strat,
                                                                              u_imp, tape, geometry)
+            if query is not None:                    # points evaluated on this call's planes (synthesis(query=))
+                tape["query"] = query.detach().float().contiguous()
+                q_sigma, q_rgb = ops.planes_query(planes, tape["query"], planes_absmax=tape.get("planes_absmax"),
+                                                  **gen._query_kwargs())
         gen._last_extras = (planes, feat_img)        # for synthesis(return_planes=True)
         ctx.gen, ctx.tape, ctx.ws_c = gen, tape, ws_c
         ctx.params = params
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape = ws.shape
         ctx.c_dtype = c.dtype
+        if query is not None:
+            ctx.set_materialize_grads(False)
+            ctx.q_dtype = query.dtype
+            if geometry:
+                return img, rgb_raw, depth, mask[0], q_sigma, q_rgb
+            no_mask = depth.new_empty(0)             # (a fixed number of outputs; without geometry=True the dict has no 'image_mask'
+            ctx.mark_non_differentiable(depth, no_mask)      # and the depth carries no gradient, as in a call without query)
+            return img, rgb_raw, depth, no_mask, q_sigma, q_rgb
         if geometry:
             ctx.set_materialize_grads(False)         # an output the loss does not use hands backward None, not a zero image
             return img, rgb_raw, depth, mask[0]
@@ -354,6 +400,11 @@ class SynthesisFn(torch.autograd.Function):
     @staticmethod
     @torch.no_grad()
     def backward(ctx, g_img, g_raw, g_depth, g_mask=None):
+        d_ws, d_c, _, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask)
+        return (d_ws, d_c, None, None, None) + pgrads
+
+    @staticmethod
+    def _backward(ctx, g_img, g_raw, g_depth, g_mask=None, g_qsigma=None, g_qrgb=None, need_coords=False):
         gen, tape = ctx.gen, ctx.tape
         if tape is None:
             raise RuntimeError("TriPlaneGenerator.synthesis: backward called a second time — the saved activations "
@@ -410,6 +461,14 @@ class SynthesisFn(torch.autograd.Function):
                                           tape["planes"], rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
                                           planes_absmax=tape.get("planes_absmax"), **gen._render_args(tape["c"]))
             d_c = torch.cat((d_c2w, d_intr), 1).to(ctx.c_dtype)
+        d_coords = None
+        if g_qsigma is not None or g_qrgb is not None:
+            # the point query of synthesis(query=): its plane gradient joins the renderer's BEFORE the one backbone pass, its decoder
+            # gradients land in the renderer's four tensors.  After raymarch_bwd has returned: that call overwrites plane 2 on
+            # mirrored planes (mirror_plane_kernel), this one adds to every plane.
+            _, d_coords = gen._timed("planes_query_bwd", float(b), _query_backward, gen, tape["planes"], tape["query"],
+                                     tape.get("planes_absmax"), g_qsigma, g_qrgb, rb[0] if ctx.pg else rb, need_coords,
+                                     rb[1] if ctx.pg else None)
         if ctx.pg:
             d_planes, dec = rb
             for prm, g in zip(dec_prm, dec):
@@ -420,26 +479,10 @@ class SynthesisFn(torch.autograd.Function):
             bw.release_ready()
         else:
             d_planes = rb
-        # ---- backbone, last block first
-        g_img_b = ops.planes_to_nhwc(d_planes)
-        dxs, nxt = None, None
-        walk = list(reversed(tape["backbone"]))
-        side = gen.side_stream(b, dev) if all(not r["rgb"]["small"] for r in walk) else None
-        ahead = bw.image_chain(walk, g_img_b, side) if side is not None else None
-        for k, rec in enumerate(walk):
-            s_next = nxt["styles"] if nxt is not None else None
-            dxs_new, c0, g_img_b = bw.block(rec, g_img_b, dxs, s_next, nxt, ahead[k] if ahead is not None else None)
-            if nxt is not None:
-                bw.finish_layer(nxt)
-            dxs, nxt = dxs_new, c0
-            bw.release_ready()
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)     # (nothing of this pass is left on the side stream)
-        bw.flush_styles()
-        bw.release_ready()
+        _backbone_backward(bw, gen, tape["backbone"], d_planes, b, dev)
         ctx.tape = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return (d_ws, d_c, None, None, None) + pgrads
+        return d_ws, d_c, d_coords, pgrads
 
 
 class SynthesisGeomFn(SynthesisFn):
@@ -448,3 +491,71 @@ class SynthesisGeomFn(SynthesisFn):
     @staticmethod
     def forward(ctx, ws, c, u_strat, u_imp, gen, *params):
         return SynthesisFn._forward(ctx, True, ws, c, u_strat, u_imp, gen, params)
+
+
+
+class SynthesisQueryFn(SynthesisFn):
+    """`synthesis(query=coords)`: inputs ws, c, u_strat, u_imp, coords, geometry, gen, *parameters; outputs image, image_raw,
+    image_depth, image_mask, query_sigma [B,M,1], query_rgb [B,M,32].  The gradients of the last two reach the planes through
+    ops.planes_query_bwd right after ops.raymarch_bwd, into its d_planes and decoder gradients: one backbone pass serves the
+    image and the point losses, and every parameter is released to the gradient sink once."""
+    @staticmethod
+    def forward(ctx, ws, c, u_strat, u_imp, coords, geometry, gen, *params):
+        return SynthesisFn._forward(ctx, bool(geometry), ws, c, u_strat, u_imp, gen, params, query=coords)
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb):
+        need_coords = ctx.needs_input_grad[4] and (g_qsigma is not None or g_qrgb is not None)
+        d_ws, d_c, d_coords, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, need_coords)
+        if d_coords is not None:
+            d_coords = d_coords.to(ctx.q_dtype)
+        return (d_ws, d_c, None, None, d_coords, None, None) + pgrads
+
+
+class SampleMixedFn(torch.autograd.Function):
+    """`sample_mixed(..., differentiable=True)` on its own: inputs ws, coords, gen, *parameters; outputs sigma, rgb.  A backbone
+    forward with a tape, the query; backward = ops.planes_query_bwd, then the backbone backward `synthesis` runs."""
+    @staticmethod
+    def forward(ctx, ws, coords, gen, *params):
+        ws_c = ws.detach().float().contiguous()
+        co = coords.detach().float().contiguous()
+        tape = []
+        with torch.no_grad():
+            planes = gen.backbone_planes(ws_c, tape)
+            pam = getattr(gen, "_planes_absmax", None)
+            sigma, rgb = ops.planes_query(planes, co, planes_absmax=pam, **gen._query_kwargs())
+        ctx.gen, ctx.tape, ctx.ws_c, ctx.co, ctx.planes, ctx.pam = gen, tape, ws_c, co, planes, pam
+        ctx.params = params
+        ctx.pg = any(p.requires_grad for p in params)
+        ctx.ws_shape, ctx.q_dtype = ws.shape, coords.dtype
+        ctx.set_materialize_grads(False)
+        return sigma, rgb
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_sigma, g_rgb):
+        gen = ctx.gen
+        if ctx.tape is None:
+            raise RuntimeError("TriPlaneGenerator.sample_mixed: backward called a second time — the saved activations are released "
+                               "by the first backward pass (retain_graph is not supported)")
+        none = (None,) * (3 + len(ctx.params))
+        if g_sigma is None and g_rgb is None:
+            return none
+        planes = ctx.planes
+        b, dev = planes.shape[0], planes.device
+        d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
+        bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
+        net = gen.decoder.net
+        dec_prm = (net["0"].weight, net["0"].bias, net["2"].weight, net["2"].bias)
+        dec = tuple(torch.zeros_like(p) for p in dec_prm) if ctx.pg else None
+        d_planes, d_coords = _query_backward(gen, planes, ctx.co, ctx.pam, g_sigma, g_rgb, None, ctx.needs_input_grad[1], dec)
+        if ctx.pg:
+            for prm, g in zip(dec_prm, dec):
+                bw._acc(prm, g)
+        _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
+        ctx.tape = ctx.planes = None
+        if d_coords is not None:
+            d_coords = d_coords.to(ctx.q_dtype)
+        pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
+        return (d_ws, d_coords, None) + pgrads

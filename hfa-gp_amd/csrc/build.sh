@@ -33,6 +33,7 @@ units+=(planes_query)
 units+=(marching_cubes)
 units+=(weight_prep)
 units+=(raymarch_camera)
+units+=(planes_query_bwd)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

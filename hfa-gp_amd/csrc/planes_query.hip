@@ -15,6 +15,7 @@
 //     its 4 MB L2 holds plane bands instead of refetching them.
 #include <type_traits>
 #include "raymarch_common.h"
+#include "planes_query_common.h"
 
 namespace hfagp {
 
@@ -33,17 +34,7 @@ struct QueryParams {
     float voxel, origin;       // grid: fp32(cube_length / (N - 1)), fp32(-cube_length / 2)
 };
 
-// Point normalisation without contraction: hipcc fuses a * b + c into one FMA (and __fmul_rn / __fadd_rn are plain operators
-// here), but torch rounds `samples * voxel_size + voxel_origin` and `(2 / box_warp) * coords` after every operation — and
-// the grid must give the bits of the explicit path fed with that lattice.
-__device__ __forceinline__ float scale_rn(float s, float v) {
-#pragma clang fp contract(off)
-    return s * v;
-}
-__device__ __forceinline__ float lattice_rn(int i, float voxel, float origin) {
-#pragma clang fp contract(off)
-    return (float)i * voxel + origin;
-}
+// (scale_rn / lattice_rn, the point normalisation: planes_query_common.h, shared with the backward)
 
 template <bool DEC16, bool RGB, bool GRID>
 __global__ void __launch_bounds__(256) planes_query_kernel(const QueryParams p) {

@@ -28,6 +28,8 @@ struct TileLds {
 };
 
 // decoder-weight gradients (PG): per-tile operand images for the sample-contracting products
+// (planes_query_bwd.hip carries a COPY of this PG code — GradLds, the operand images and MFMA products per tile, the flush at the
+// end of the kernel — for free points: a change here belongs there too)
 //   dW1c[32x64] += dO[32x16] . SP^T[16x64]      dW0[64x32] += dHpre[64x16] . F[16x32]
 struct GradLds {
     float sp[64 * 17], dp[64 * 17], dO[32 * 17], f[16 * 33];

@@ -18,30 +18,8 @@ namespace hfagp {
 constexpr int kCamWaves = 4;
 constexpr int kCamReduceThreads = 256;
 
-// plane_taps with what the derivative needs next to the texel indices: the fractional parts and each tap's validity (the
-// weights of plane_taps are products of these; a tap outside the plane is a zero texel)
-struct PlaneTapsD {
-    int idx[4];          // nw, ne, sw, se (clamped into the plane: always loadable)
-    bool ok[4];
-    float fx, fy;
-};
-__device__ __forceinline__ void plane_taps_d(const HfagpRaymarchArgs& a, float gx, float gy, PlaneTapsD& t) {
-    const float fW = (float)a.W, fH = (float)a.H;
-    float ix, iy;
-    plane_pixel(a, gx, gy, ix, iy);
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    t.fx = __fsub_rn(ix, fx0);
-    t.fy = __fsub_rn(iy, fy0);
-    const int x0 = (int)fminf(fmaxf(fx0, -2.f), fW + 1.f), y0 = (int)fminf(fmaxf(fy0, -2.f), fH + 1.f);
-    const int x1 = x0 + 1, y1 = y0 + 1;
-    const bool vx0 = x0 >= 0 && x0 < a.W, vx1 = x1 >= 0 && x1 < a.W;
-    const bool vy0 = y0 >= 0 && y0 < a.H, vy1 = y1 >= 0 && y1 < a.H;
-    const int cx0 = min(max(x0, 0), a.W - 1), cx1 = min(max(x1, 0), a.W - 1);
-    const int cy0 = min(max(y0, 0), a.H - 1), cy1 = min(max(y1, 0), a.H - 1);
-    t.ok[0] = vx0 && vy0; t.ok[1] = vx1 && vy0; t.ok[2] = vx0 && vy1; t.ok[3] = vx1 && vy1;
-    t.idx[0] = cy0 * a.W + cx0; t.idx[1] = cy0 * a.W + cx1;
-    t.idx[2] = cy1 * a.W + cx0; t.idx[3] = cy1 * a.W + cx1;
-}
+// (PlaneTapsD / plane_taps_d, the taps with what the positional derivative needs: raymarch_common.h, shared with
+// planes_query_bwd.hip)
 
 template <int S, bool DEC16>
 __global__ void __launch_bounds__(kCamWaves * 64, 2)

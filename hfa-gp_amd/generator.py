@@ -754,14 +754,31 @@ class TriPlaneGenerator(nn.Module):
 
     def synthesis(self, ws: torch.Tensor, c: torch.Tensor, noise_mode: str = "const",
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
-                  return_planes: bool = False, geometry: bool = False, **_unused) -> Dict[str, torch.Tensor]:
+                  return_planes: bool = False, geometry: bool = False, query: Optional[torch.Tensor] = None,
+                  **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
         HFA-GP), w.r.t. the generator parameters that require grad (after `tune_generator()`) and w.r.t. the camera label `c`
         when it requires grad (pose refinement; the importance depths are detached as in EG3D).
         `geometry=True`: the dict also has 'image_mask' [B,1,r,r] (the per-ray opacity, sum of the compositing weights), and
         'image_depth' and 'image_mask' are differentiable — silhouette / matting losses and depth priors reach `ws` and the
-        generator.  Off (the default), 'image_depth' carries no gradient and the dict has EG3D's three keys."""
+        generator.  Off (the default), 'image_depth' carries no gradient and the dict has EG3D's three keys.
+        `query=coords` [B or 1, M, 3] (world units): the dict also has 'query_sigma' [B,M,1] and 'query_rgb' [B,M,32], the raw
+        decoder outputs at the points on THIS call's planes — the bits of `sample_mixed` under `no_grad` — differentiable w.r.t.
+        `ws`, the generator parameters that require grad and `coords` when it requires grad.  Their gradient joins the
+        renderer's before the one backbone backward pass: a point loss (EG3D's density regularisation, an occupancy prior) next
+        to an image loss costs one launch, not a second backbone pass.  A loss on the points ALONE still runs the image's whole
+        backward here (on a zero image gradient): `sample_mixed(..., differentiable=True)` is the cheaper form for that."""
         self._check_inputs(ws, c, noise_mode)
+        if query is not None:
+            if query.dim() != 3 or query.shape[-1] != 3 or query.shape[0] not in (1, ws.shape[0]) or not query.is_cuda:
+                raise ValueError(f"expected query [B or 1, M, 3] on the device for ws of batch {ws.shape[0]}, got "
+                                 f"{tuple(query.shape)} on {query.device}")
+            if query.shape[1] == 0 or ws.shape[0] == 0:       # nothing to evaluate: the keys, with the autograd edge of the points
+                out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry)
+                zero = 0.0 * query.sum() if query.requires_grad else 0.0
+                out["query_sigma"] = torch.zeros(ws.shape[0], query.shape[1], 1, device=ws.device) + zero
+                out["query_rgb"] = torch.zeros(ws.shape[0], query.shape[1], 32, device=ws.device) + zero
+                return out
         if ws.shape[0] == 0:          # empty batch (ragged last batch of a frame shard): nothing to launch
             cfg, dev = self.cfg, ws.device
             r = cfg.neural_rendering_resolution
@@ -773,11 +790,20 @@ class TriPlaneGenerator(nn.Module):
             return out
         params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
         cam_grad = torch.is_grad_enabled() and c.requires_grad
-        need_grad = torch.is_grad_enabled() and (ws.requires_grad or cam_grad or any(p.requires_grad for p in params))
+        need_grad = torch.is_grad_enabled() and (ws.requires_grad or cam_grad or any(p.requires_grad for p in params) or
+                                                 (query is not None and query.requires_grad))
         c_in = c if cam_grad else c.detach()
         if need_grad:
             from .autograd import SynthesisFn
-            if geometry:
+            if query is not None:
+                from .autograd import SynthesisQueryFn
+                img, rgb_raw, depth, mask, q_sigma, q_rgb = SynthesisQueryFn.apply(ws, c_in, u_strat, u_imp, query, geometry, self,
+                                                                                   *params)
+                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
+                if geometry:
+                    out["image_mask"] = mask
+                out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
+            elif geometry:
                 from .autograd import SynthesisGeomFn
                 img, rgb_raw, depth, mask = SynthesisGeomFn.apply(ws, c_in, u_strat, u_imp, self, *params)
                 out = {"image": img, "image_raw": rgb_raw, "image_depth": depth, "image_mask": mask}
@@ -791,9 +817,14 @@ class TriPlaneGenerator(nn.Module):
         with torch.no_grad():
             img, rgb_raw, depth, planes, feat_img, *mask = self._forward_impl(
                 ws.detach().float().contiguous(), c.detach().float().contiguous(), u_strat, u_imp, None, geometry)
+            if query is not None:
+                q_sigma, q_rgb = ops.planes_query(planes, query.detach().float().contiguous(),
+                                                  planes_absmax=getattr(self, "_planes_absmax", None), **self._query_kwargs())
         out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
         if geometry:
             out["image_mask"] = mask[0]
+        if query is not None:
+            out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
         if return_planes:
             out["planes"] = planes
             out["feature_image"] = feat_img
@@ -820,7 +851,7 @@ class TriPlaneGenerator(nn.Module):
         return ws
 
     # ------------------------------------------------------------------ point queries (EG3D TriPlaneGenerator.sample*)
-    def _query_guard(self, who: str, ws: torch.Tensor, *tensors) -> None:
+    def _query_guard(self, who: str, ws: torch.Tensor, *tensors, differentiable: bool = False) -> None:
         if not ws.is_cuda:
             raise RuntimeError(f"TriPlaneGenerator.{who}: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
         if ws.device.index != torch.cuda.current_device():
@@ -828,13 +859,16 @@ class TriPlaneGenerator(nn.Module):
                                f"cuda:{torch.cuda.current_device()}; wrap the call in `with torch.cuda.device(ws.device):`")
         if ws.dim() != 3 or ws.shape[1:] != (self.cfg.num_ws, self.cfg.w_dim):
             raise ValueError(f"expected ws [B,{self.cfg.num_ws},{self.cfg.w_dim}], got {tuple(ws.shape)}")
-        self._no_backward(who, ws, *tensors)
+        if not differentiable:
+            self._no_backward(who, ws, *tensors)
 
     def _no_backward(self, who: str, *tensors) -> None:
         if torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors) or
                                         any(p.requires_grad for p in self.parameters())):
+            hint = " — or pass `differentiable=True`, or ride on an image pass with `synthesis(query=)`" if who == "sample_mixed" \
+                else ""
             raise RuntimeError(f"TriPlaneGenerator.{who}: wrap in `torch.no_grad()`; the query has no backward "
-                               f"(an input or a generator parameter requires grad)")
+                               f"(an input or a generator parameter requires grad){hint}")
 
     def _query_planes(self, ws: torch.Tensor):
         """One backbone pass → (planes [B,3,R,R,32], the |planes| bound `synthesis` hands the renderer)."""
@@ -849,11 +883,17 @@ class TriPlaneGenerator(nn.Module):
                     decoder_lr_mul=cfg.decoder_lr_mul, decoder_precision=cfg.decoder_precision)
 
     def sample_mixed(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], ws: torch.Tensor,
-                     truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:
+                     truncation_psi=1, truncation_cutoff=None, update_emas=False, *, differentiable: bool = False,
+                     **synthesis_kwargs) -> Dict[str, torch.Tensor]:
         """EG3D TriPlaneGenerator.sample_mixed: the raw decoder outputs at `coordinates` [B or 1, M, 3] (world units) of the
         tri-planes of `ws` → {'rgb': [B,M,32], 'sigma': [B,M,1]} (sigma before the renderer's softplus).  `directions` is
         shape-checked and ignored (OSGDecoder does not read it); the truncation arguments are EG3D's and unused here, as
-        there.  One backbone pass, one launch (ops.planes_query), the decoder precision the renderer runs.  Forward only."""
+        there.  One backbone pass, one launch (ops.planes_query), the decoder precision the renderer runs.
+        Forward only unless `differentiable=True`: then, under grad, the outputs are differentiable w.r.t. `ws`, the generator
+        parameters that require grad and `coordinates` when it requires grad, at the price of a backbone backward pass of its
+        own — a loss that also renders should use `synthesis(query=)`, which shares the image's pass.  Inside a trainer step
+        scope (a gradient sink, or gradients accumulated in place) the stand-alone form raises: a second pass would hand every
+        parameter to the sink twice."""
         noise_mode = synthesis_kwargs.get("noise_mode", "const")
         if noise_mode != "const":
             raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
@@ -861,10 +901,24 @@ class TriPlaneGenerator(nn.Module):
             raise ValueError(f"expected coordinates [B or 1, M, 3] for ws of batch {ws.shape[0]}, got {tuple(coordinates.shape)}")
         if directions is not None and directions.shape != coordinates.shape:
             raise ValueError(f"directions {tuple(directions.shape)} must match coordinates {tuple(coordinates.shape)}")
-        self._query_guard("sample_mixed", ws, coordinates)
+        params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
+        grad = differentiable and torch.is_grad_enabled() and (ws.requires_grad or coordinates.requires_grad or
+                                                               any(p.requires_grad for p in params))
+        self._query_guard("sample_mixed", ws, *(() if differentiable else (coordinates,)), differentiable=differentiable)
         b, m = ws.shape[0], coordinates.shape[1]
         if b == 0 or m == 0:
-            return {"rgb": torch.zeros(b, m, 32, device=ws.device), "sigma": torch.zeros(b, m, 1, device=ws.device)}
+            zero = 0.0 * ws.sum() + 0.0 * coordinates.sum() if grad else 0.0       # keeps the autograd edges
+            return {"rgb": torch.zeros(b, m, 32, device=ws.device) + zero, "sigma": torch.zeros(b, m, 1, device=ws.device) + zero}
+        if grad:
+            if getattr(self, "_grad_sink", None) is not None or getattr(self, "_grad_inplace", False):
+                raise RuntimeError("TriPlaneGenerator.sample_mixed(differentiable=True) inside a trainer step scope: its backward is "
+                                   "a second backbone pass and would release every parameter to the gradient sink twice — "
+                                   "evaluate the points with `synthesis(..., query=coordinates)` instead")
+            if not coordinates.is_cuda:
+                raise RuntimeError("TriPlaneGenerator.sample_mixed: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
+            from .autograd import SampleMixedFn
+            sigma, rgb = SampleMixedFn.apply(ws, coordinates, self, *params)
+            return {"rgb": rgb, "sigma": sigma}
         with torch.no_grad():
             planes, pam = self._query_planes(ws)
             sigma, rgb = ops.planes_query(planes, coordinates.detach().float().contiguous(), planes_absmax=pam,

@@ -730,6 +730,73 @@ def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *,
     return sigma, rgb
 
 
+def planes_query_bwd(planes: torch.Tensor, coords: torch.Tensor, g_sigma: Optional[torch.Tensor], g_rgb: Optional[torch.Tensor], *,
+                     dec_w0: torch.Tensor, dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, box_warp: float,
+                     plane_axes, decoder_lr_mul: float, decoder_precision: str, planes_absmax: Optional[torch.Tensor] = None,
+                     d_planes=None, coords_grad: bool = False, decoder_grads: bool = False, dec_out=None):
+    """Backward of `planes_query(planes, coords, ...)` (hfagp_planes_query_bwd; explicit points only) → ``(d_planes, d_coords,
+    dec)``.  ``g_sigma`` [B,M,1] or [B,M] and ``g_rgb`` [B,M,32]: the upstream gradients, either may be None.
+
+      * ``d_planes``: a [B,3,H,W,32] tensor the plane gradient is ACCUMULATED into (returned), None = fresh zeros, False = not
+        wanted (None is returned).  A tensor shared with `raymarch_bwd` must have been through that call FIRST: on mirrored
+        planes it overwrites plane 2, and this kernel adds to all three planes at their true texels.
+      * ``coords_grad``: also return d_coords [B,M,3] (one row per identity; for broadcast coords [1,M,3] the gradient of the
+        shared points is ``d_coords.sum(0, keepdim=True)``), else None.  Points outside the box get exact zeros.
+      * ``decoder_grads`` / ``dec_out``: as `raymarch_bwd` — four decoder-parameter gradients, accumulated into ``dec_out``
+        when given, else into fresh zeros; ``dec`` is None without them.
+    The other keywords are the forward's; pass the ``planes_absmax`` the forward call got, so that the recomputed decoder is
+    the one that ran."""
+    _chk(planes, "planes")
+    if planes.dim() != 5 or planes.shape[1] != 3 or planes.shape[4] != 32:
+        raise RuntimeError("planes_query_bwd: planes must be [B, 3, H, W, 32]")
+    b, _, h, w, _ = planes.shape
+    dev = planes.device
+    if isinstance(plane_axes, str):
+        plane_axes = 0 if plane_axes == "eg3d_original" else 1
+    if coords is None:
+        raise ValueError("planes_query_bwd: explicit coords only (grid mode has no backward)")
+    _chk(coords, "coords")
+    if coords.dim() != 3 or coords.shape[2] != 3 or coords.shape[0] not in (1, b):
+        raise RuntimeError(f"planes_query_bwd: coords must be [1 or B={b}, M, 3], got {tuple(coords.shape)}")
+    m = coords.shape[1]
+    if g_sigma is None and g_rgb is None:
+        raise ValueError("planes_query_bwd: pass g_sigma, g_rgb or both")
+    if g_sigma is not None and (_chk(g_sigma, "g_sigma").numel() != b * m or g_sigma.shape[:2] != (b, m)):
+        raise RuntimeError(f"planes_query_bwd: g_sigma must be [B, M, 1] = [{b}, {m}, 1], got {tuple(g_sigma.shape)}")
+    if g_rgb is not None and _chk(g_rgb, "g_rgb").shape != (b, m, 32):
+        raise RuntimeError(f"planes_query_bwd: g_rgb must be [B, M, 32] = [{b}, {m}, 32], got {tuple(g_rgb.shape)}")
+    if d_planes is False:
+        d_planes = None
+        if not (coords_grad or decoder_grads):
+            raise ValueError("planes_query_bwd: nothing to compute (d_planes=False without coords_grad or decoder_grads)")
+    elif d_planes is None:
+        d_planes = torch.zeros_like(planes)
+    elif _chk(d_planes, "d_planes").shape != planes.shape:
+        raise RuntimeError(f"planes_query_bwd: d_planes must be shaped like planes {tuple(planes.shape)}, got {tuple(d_planes.shape)}")
+    d_coords = torch.empty(b, m, 3, device=dev, dtype=torch.float32) if coords_grad else None     # (every point has one writer)
+    dec = None
+    if decoder_grads:
+        dec = tuple(dec_out) if dec_out is not None else tuple(torch.zeros_like(t) for t in (dec_w0, dec_b0, dec_w1, dec_b1))
+        for t, like in zip(dec, (dec_w0, dec_b0, dec_w1, dec_b1)):
+            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+                raise RuntimeError("planes_query_bwd: dec_out must be four contiguous fp32 device tensors shaped like the decoder parameters")
+    if b == 0 or m == 0:
+        return d_planes, d_coords, dec
+    a = L.PlanesQueryBwdArgs()
+    a.planes, a.coords, a.Bc, a.M = _ptr(planes), _ptr(coords), coords.shape[0], m
+    a.dec_w0, a.dec_b0 = _ptr(_chk(dec_w0, "dec_w0")), _ptr(_chk(dec_b0, "dec_b0"))
+    a.dec_w1, a.dec_b1 = _ptr(_chk(dec_w1, "dec_w1")), _ptr(_chk(dec_b1, "dec_b1"))
+    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
+    a.g_sigma, a.g_rgb = _ptr(g_sigma), _ptr(g_rgb)
+    a.d_planes, a.d_coords = _ptr(d_planes), _ptr(d_coords)
+    if dec is not None:
+        a.d_dec_w0, a.d_dec_b0, a.d_dec_w1, a.d_dec_b1 = (_ptr(t) for t in dec)
+    a.B, a.H, a.W, a.plane_axes = b, h, w, plane_axes
+    a.box_warp, a.decoder_lr_mul = box_warp, decoder_lr_mul
+    L.check(L.lib().hfagp_planes_query_bwd(C.byref(a), _stream()), "planes_query_bwd")
+    return d_planes, d_coords, dec
+
+
 def marching_cubes(volume: torch.Tensor, level: float, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     """Iso-surface ``volume > level`` of a float32 [n0, n1, n2] volume (hfagp_marching_cubes_count / _emit) → ``(verts [V, 3]
     float32, faces [F, 3] int32)`` on the volume's device.  Vertices ``origin + spacing * p`` at the crossed lattice edges,

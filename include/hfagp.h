@@ -39,6 +39,7 @@
  *   hfagp_raymarch_bwd      <- autograd of the renderer: grid_sample / decoder / compositing adjoints
  *   hfagp_raymarch_bwd_geom <- the same with gradients of the expected depth and the opacity (silhouette / depth losses)
  *   hfagp_raymarch_bwd_camera <- autograd of RaySampler + grid_sample w.r.t. the sample positions: the gradient of the camera label
+ *   hfagp_planes_query_bwd  <- autograd of sample_mixed (grid_sample + OSGDecoder at given points) w.r.t. planes, decoder and points
  *   hfagp_modconv_fwd modes HFAGP_CONV3X3_BWD / HFAGP_CONVS2_BWD <- conv2d_gradfix data gradients (the same GEMM kernel)
  *   hfagp_conv_wgrad (+ _workspace_bytes) <- conv2d_gradfix weight gradients
  *   hfagp_pointwise_bwd     <- bias_act backward + noise-strength / bias gradients + demodulation adjoint of a SynthesisLayer
@@ -152,6 +153,45 @@ typedef struct {
 } HfagpPlanesQueryArgs;
 
 int hfagp_planes_query(const HfagpPlanesQueryArgs* a, void* stream);
+
+/* Backward of hfagp_planes_query for explicit points (additive to ABI 15; grid mode has no backward: HFAGP_EUNSUPPORTED).
+ * Given dL/dsigma [B][M] and / or dL/drgb [B][M][32] (at least one), recomputes gather and decoder per point in the precision
+ * the forward ran (planes_absmax given: split fp16 forward, split bf16 adjoint; NULL: exact fp32) and writes, each optional
+ * (at least one):
+ *   d_planes  [B][3][H][W][32]  ACCUMULATED INTO with fp32 atomics (the caller zeroes it, or hands over a gradient to add
+ *             to).  Every plane is scattered at its true texels.  hfagp_raymarch_bwd OVERWRITES plane 2 of its d_planes
+ *             with plane 1 transposed on square planes with plane_axes 0, so a caller sharing one d_planes between the two
+ *             must call this entry AFTER hfagp_raymarch_bwd on the same stream.
+ *   d_coords  [B][M][3]  plain stores, one writer per point, in world units (the 2 / box_warp scale included).  With Bc = 1
+ *             the gradient of the shared point set is the caller's sum over B.  Points outside the box get exact zeros.
+ *   d_dec_*   the decoder-parameter gradients (all four or none), ACCUMULATED INTO with one set of atomics per wavefront.
+ * The bilinear gather is not differentiable where a pixel coordinate is an integer; there the one-sided derivative of the
+ * cell the forward's floor() picked is returned.                                                                        */
+typedef struct {
+    const float* planes;      /* [B][3][H][W][32] fp32                                                                    */
+    const float* coords;      /* [Bc][M][3] points in world units (required)                                              */
+    const float* dec_w0;      /* decoder.net.0.weight [64][32]  (raw parameter)                                           */
+    const float* dec_b0;      /* decoder.net.0.bias   [64]                                                                */
+    const float* dec_w1;      /* decoder.net.2.weight [33][64]                                                            */
+    const float* dec_b1;      /* decoder.net.2.bias   [33]                                                                */
+    const float* planes_absmax; /* optional, as HfagpPlanesQueryArgs::planes_absmax: pass what the forward call passed    */
+    const float* g_sigma;     /* optional [B][M]     dL/d sigma (the raw density)                                         */
+    const float* g_rgb;       /* optional [B][M][32] dL/d rgb                                                             */
+    float*       d_planes;    /* optional, accumulated into                                                               */
+    float*       d_coords;    /* optional out [B][M][3]                                                                   */
+    float*       d_dec_w0;    /* optional [64][32], accumulated into (the four go together)                               */
+    float*       d_dec_b0;    /* [64]                                                                                     */
+    float*       d_dec_w1;    /* [33][64]                                                                                 */
+    float*       d_dec_b1;    /* [33]                                                                                     */
+    int64_t M;                /* points per identity (> 0)                                                                */
+    int32_t B, H, W;          /* identities, plane height / width (> 1)                                                   */
+    int32_t Bc;               /* identities in coords, 1 (broadcast) or B                                                 */
+    int32_t plane_axes;       /* 0: (x,y),(x,z),(z,x) [eg3d original]; 1: third = (z,y)                                   */
+    float decoder_lr_mul;
+    double box_warp;
+} HfagpPlanesQueryBwdArgs;
+
+int hfagp_planes_query_bwd(const HfagpPlanesQueryBwdArgs* a, void* stream);
 
 /* ------------------------------------------------------------------ marching cubes (ABI 14)
  * The iso-surface of a fp32 volume V[n0][n1][n2] (last axis fastest, each extent >= 2) as a welded triangle mesh.
