@@ -34,6 +34,7 @@ units+=(marching_cubes)
 units+=(weight_prep)
 units+=(raymarch_camera)
 units+=(planes_query_bwd)
+units+=(raymarch_normals)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

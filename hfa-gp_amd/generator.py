@@ -77,6 +77,11 @@ class _FC(nn.Module):
         self.bias = nn.Parameter(torch.full([fout], float(bias_init)))
 
 
+# Above this many bytes of per-sample ray-marcher state (140 per sample: `ops.raymarch_state`) a differentiable step does not keep
+# the state (the backward marches again) and `synthesis(normals=True)` renders in frame chunks.
+RAY_STATE_CAP_BYTES = 8 << 30
+
+
 def _fir(taps) -> torch.Tensor:
     k = torch.tensor(list(taps), dtype=torch.float32)
     k = torch.outer(k, k)
@@ -166,6 +171,8 @@ class TriPlaneGenerator(nn.Module):
         self._absmax = None                      # (slot buffers, layer names) of the last pass: f16_range_report()
         self._rgb_part = None                    # partial toRGB sums of the conv just run (fused toRGB, ops.modconv)
         self._planes_absmax = None               # [64] slots with max |planes| of the pass in flight (16-bit decoder)
+        self._want_normals = False               # synthesis(normals=True) in flight: _forward_body takes the normal pass too ...
+        self._last_normal = None                 # ... and leaves 'image_normal' here for synthesis to pick up
         self._scalars: Dict[int, tuple] = {}     # id(param) -> (version, data_ptr, python float)
         self._const_nhwc: Optional[tuple] = None
         self.timing: Optional[Dict[str, list]] = None   # bench.py: {'raymarch': [(ev0, ev1, units)], 'modconv': [...]}
@@ -667,6 +674,24 @@ class TriPlaneGenerator(nn.Module):
         return self._timed("raymarch", nbytes, ops.raymarch, planes, u_strat=u_strat, u_imp=u_imp,
                            planes_absmax=planes_absmax, state=state, **self._render_args(c))
 
+    def _render_normals_chunked(self, planes, c, u_strat, u_imp, planes_absmax, frames: int):
+        """`render` + `ops.raymarch_normals` over chunks of `frames` frames through one state buffer of that size: the per-sample
+        state of the whole batch would exceed RAY_STATE_CAP_BYTES.  Every ray is computed as in the whole-batch launch (the
+        decoder's bound on |planes| is the batch's, taken once), so the five results equal the unchunked ones bit for bit."""
+        cfg = self.cfg
+        b, res = planes.shape[0], cfg.neural_rendering_resolution
+        planes_absmax = ops._decoder_bound(planes, cfg.decoder_precision, planes_absmax)
+        u_imp = u_imp.view(b, res * res, -1)
+        state = ops.raymarch_state(min(frames, b), res, cfg.depth_resolution, cfg.depth_resolution_importance, planes.device)
+        parts = []
+        for i in range(0, b, frames):
+            n = min(frames, b - i)
+            pl, ci, us, ui = planes[i:i + n], c[i:i + n], u_strat[i:i + n], u_imp[i:i + n].reshape(n * res * res, -1)
+            out = self.render(pl, ci, us, ui, planes_absmax=planes_absmax, state=state[:n])
+            parts.append(out + (ops.raymarch_normals(pl, state[:n], u_strat=us, u_imp=ui, planes_absmax=planes_absmax,
+                                                     **self._render_args(ci)),))
+        return tuple(torch.cat(t) for t in zip(*parts))
+
     def superres(self, rgb_raw: torch.Tensor, feat_img: torch.Tensor, ws: torch.Tensor, tape=None) -> torch.Tensor:
         if not getattr(self, "_in_forward", False):     # called directly: see backbone_planes
             self._refresh_tuned(tape is not None)
@@ -735,9 +760,22 @@ class TriPlaneGenerator(nn.Module):
         # a step that will be differentiated keeps the ray marcher's per-sample results (220 MB per frame at 128^2 rays x 96
         # samples; skipped above 8 GB): the compositing adjoint then reads them instead of marching every ray again
         ray_state = None
-        if tape is not None and b * res * res * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140 <= (8 << 30):
+        normals = getattr(self, "_want_normals", False)       # synthesis(normals=True): the same per-sample results feed the normal pass
+        frame_bytes = res * res * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
+        if (tape is not None or normals) and b * frame_bytes <= RAY_STATE_CAP_BYTES:
             ray_state = ops.raymarch_state(b, res, cfg.depth_resolution, cfg.depth_resolution_importance, ws.device)
-        feat, depth, wsum, tmm = self.render(planes, c, u_strat, u_imp, planes_absmax=pam, state=ray_state)
+        if normals and ray_state is None:         # above the cap: render and take the normals in frame chunks
+            feat, depth, wsum, tmm, normal = self._render_normals_chunked(planes, c, u_strat, u_imp, pam,
+                                                                          max(1, RAY_STATE_CAP_BYTES // frame_bytes))
+        else:
+            feat, depth, wsum, tmm = self.render(planes, c, u_strat, u_imp, planes_absmax=pam, state=ray_state)
+            if normals:
+                normal = ops.raymarch_normals(planes, ray_state, u_strat=u_strat, u_imp=u_imp, planes_absmax=pam,
+                                              **self._render_args(c))
+        if normals:
+            self._last_normal = normal.view(b, res, res, 3).permute(0, 3, 1, 2).contiguous()      # NCHW, 'image_normal'
+            if tape is None:
+                ray_state = None                  # (not needed again: released before the super-resolution allocates)
         # MipRayMarcher2 clamps the expected depth to the GLOBAL min/max sample depth of the batch
         depth = ops.depth_clamp_(depth, tmm)
         feat_img = feat.view(b, res, res, 32)                             # channels-last
@@ -755,7 +793,7 @@ class TriPlaneGenerator(nn.Module):
     def synthesis(self, ws: torch.Tensor, c: torch.Tensor, noise_mode: str = "const",
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                   return_planes: bool = False, geometry: bool = False, query: Optional[torch.Tensor] = None,
-                  **_unused) -> Dict[str, torch.Tensor]:
+                  normals: bool = False, **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
         HFA-GP), w.r.t. the generator parameters that require grad (after `tune_generator()`) and w.r.t. the camera label `c`
         when it requires grad (pose refinement; the importance depths are detached as in EG3D).
@@ -767,8 +805,23 @@ class TriPlaneGenerator(nn.Module):
         `ws`, the generator parameters that require grad and `coords` when it requires grad.  Their gradient joins the
         renderer's before the one backbone backward pass: a point loss (EG3D's density regularisation, an occupancy prior) next
         to an image loss costs one launch, not a second backbone pass.  A loss on the points ALONE still runs the image's whole
-        backward here (on a zero image gradient): `sample_mixed(..., differentiable=True)` is the cheaper form for that."""
+        backward here (on a zero image gradient): `sample_mixed(..., differentiable=True)` is the cheaper form for that.
+        `normals=True`: the dict also has 'image_normal' [B,3,r,r], the per-ray surface normal in WORLD space, pixel-aligned with
+        'image_raw' / 'image_depth': N = Σ_s ω_s n_s with n = −∇σ·rsqrt(‖∇σ‖² + 1e-12) the unit normal of the raw density (from
+        dense to empty) at every sample and ω the renderer's colour weights, so ‖N‖ ≤ 'image_mask'; not normalised
+        (`render.normal_map` turns it into a picture).  It is detached — forward only, inside a differentiable step too: its
+        gradient would be a second derivative of the tri-plane gather.  The other outputs and their gradients are unchanged."""
         self._check_inputs(ws, c, noise_mode)
+        if normals:                   # one pass of the body below with the request set (the state of the ray marcher is shared)
+            self._want_normals, self._last_normal = True, None
+            try:
+                out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query)
+            finally:
+                self._want_normals = False
+            r = self.cfg.neural_rendering_resolution
+            out["image_normal"] = self._last_normal if ws.shape[0] else torch.zeros(0, 3, r, r, device=ws.device)
+            self._last_normal = None
+            return out
         if query is not None:
             if query.dim() != 3 or query.shape[-1] != 3 or query.shape[0] not in (1, ws.shape[0]) or not query.is_cuda:
                 raise ValueError(f"expected query [B or 1, M, 3] on the device for ws of batch {ws.shape[0]}, got "

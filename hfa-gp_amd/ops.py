@@ -662,6 +662,42 @@ def raymarch(planes: torch.Tensor, cam2world: torch.Tensor, intrinsics: torch.Te
     return feat, depth, wsum, tmm
 
 
+def raymarch_normals(planes: torch.Tensor, state: torch.Tensor, *, cam2world: torch.Tensor, intrinsics: torch.Tensor,
+                     u_strat: torch.Tensor, u_imp: torch.Tensor, dec_w0: torch.Tensor, dec_b0: torch.Tensor,
+                     dec_w1: torch.Tensor, dec_b1: torch.Tensor, res: int, ray_start: float, ray_end: float, box_warp: float,
+                     decoder_lr_mul: float, plane_axes: int, white_back: bool, decoder_precision: str,
+                     planes_absmax: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-ray surface normals [B,R,3] (hfagp_raymarch_normals) of the `raymarch(..., state=state)` call with the same arguments:
+    N = Σ_s ω_s n_s over the Sc + Sf depth-sorted samples, n = −g·rsqrt(g·g + 1e-12) with g = ∇ₓσ the WORLD-space gradient of the
+    raw decoder density (before softplus(σ − 1)), ω the colour weights of the forward.  ‖N‖ ≤ wsum; not normalised; `white_back`
+    does not enter.  Forward only: the result carries no gradient.  No atomics: two calls return the same bits."""
+    _chk(planes, "planes")
+    b, three, h, w, ch = planes.shape
+    if three != 3 or ch != 32:
+        raise RuntimeError("raymarch_normals: planes must be [B, 3, H, W, 32]")
+    r = res * res
+    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    if u_strat.numel() != b * r * sc or u_imp.numel() != b * r * sf:
+        raise RuntimeError("raymarch_normals: u_strat / u_imp have the wrong number of elements")
+    if _chk(state, "state").shape != (b, r, (sc + sf) * 35):
+        raise RuntimeError(f"raymarch_normals: state must be [B, R, {(sc + sf) * 35}] (raymarch_state), got {tuple(state.shape)}")
+    normal = torch.empty(b, r, 3, device=planes.device, dtype=torch.float32)
+    if b == 0:
+        return normal
+    a = L.RaymarchArgs()
+    a.planes, a.cam2world, a.intrinsics = _ptr(planes), _ptr(_chk(cam2world, "cam2world")), _ptr(_chk(intrinsics, "intrinsics"))
+    a.u_strat, a.u_imp = _ptr(_chk(u_strat, "u_strat")), _ptr(_chk(u_imp, "u_imp"))
+    a.dec_w0, a.dec_b0 = _ptr(_chk(dec_w0, "dec_w0")), _ptr(_chk(dec_b0, "dec_b0"))
+    a.dec_w1, a.dec_b1 = _ptr(_chk(dec_w1, "dec_w1")), _ptr(_chk(dec_b1, "dec_b1"))
+    a.B, a.H, a.W, a.res, a.Sc, a.Sf = b, h, w, res, sc, sf
+    a.plane_axes, a.white_back = plane_axes, int(white_back)
+    a.ray_start, a.ray_end, a.box_warp, a.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
+    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
+    a.state = _ptr(state)
+    L.check(L.lib().hfagp_raymarch_normals(C.byref(a), _ptr(normal), _stream()), "raymarch_normals")
+    return normal
+
+
 def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *, grid=None, dec_w0: torch.Tensor,
                  dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, box_warp: float, plane_axes,
                  decoder_lr_mul: float, decoder_precision: str, planes_absmax: Optional[torch.Tensor] = None,

@@ -63,6 +63,25 @@ def render_frames(gen, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], per
         yield pending[0]
 
 
+def normal_map(image_normal: torch.Tensor, c: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """'image_normal' [B,3,r,r] of `synthesis(normals=True)` (world space, not normalised) → uint8 [B,3,r,r] in the conventional
+    colouring n·0.5 + 0.5 of the per-pixel UNIT normal (zero, i.e. mid-grey, where ‖N‖ is 0).
+    `c` [B,25], the label the synthesis call received: the normals are rotated into that camera's space first (the transpose of
+    the label's cam2world rotation block).  `mask` [B,1,r,r] ('image_mask'): the unit normal is premultiplied by it, so that
+    empty rays fade to mid-grey.  Plain torch, on whatever device the inputs live."""
+    n = image_normal.detach().float()
+    if n.dim() != 4 or n.shape[1] != 3:
+        raise ValueError(f"normal_map: expected image_normal [B, 3, r, r], got {tuple(image_normal.shape)}")
+    norm = n.norm(dim=1, keepdim=True)
+    n = torch.where(norm > 0, n / norm.clamp_min(torch.finfo(torch.float32).tiny), torch.zeros_like(n))
+    if c is not None:
+        rot = c.detach().float()[:, :16].reshape(-1, 4, 4)[:, :3, :3].to(n.device)        # cam2world: n_cam = rotᵀ n_world
+        n = torch.einsum("bji,bjhw->bihw", rot, n)
+    if mask is not None:
+        n = n * mask.detach().float().to(n.device)
+    return to_uint8(n)
+
+
 # ----------------------------------------------------------------------------- shape export (EG3D gen_samples.py --shapes)
 def shape_volume_eg3d(sigma_grid) -> np.ndarray:
     """EG3D's post-processing of a density grid [N, N, N] (TriPlaneGenerator.density_grid of one identity, indexed (ix, iy, iz)):

@@ -28,6 +28,8 @@
  *                              density volume of gen_samples.py --shapes (create_samples lattice), one launch (ABI 13)
  *   hfagp_marching_cubes_count / _emit (+ _workspace_bytes) <- the .ply mesh of gen_samples.py --shapes
  *                              (skimage.measure.marching_cubes + plyfile in EG3D's shape_utils), on the GPU (ABI 14)
+ *   hfagp_raymarch_normals  <- (no reference counterpart: the per-ray surface normal map of EG3D-family geometry renders — the
+ *                              density gradient of every sample composited with MipRayMarcher2's weights)
  *   hfagp_depth_clamp       <- MipRayMarcher2's torch.clamp(depth, min sample depth, max sample depth) over the batch, one launch (ABI 10)
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
@@ -116,6 +118,21 @@ typedef struct {
 } HfagpRaymarchArgs;
 
 int hfagp_raymarch_fwd(const HfagpRaymarchArgs* a, void* stream);
+
+/* Per-ray surface normals (additive to ABI 15).  After hfagp_raymarch_fwd on the same arguments and stream with fwd->state given:
+ * the sorted sample depths and densities are read from the state (the output pointers of `fwd` are not touched).  Per sample
+ *   g = d sigma / d x   the WORLD-space gradient of the raw decoder density (channel 0 of the decoder, before softplus(sigma - 1))
+ *                       of the function the forward evaluated: plane mean of the three bilinear gathers, zeros padding,
+ *                       align_corners = False; the 2 / box_warp factor and the routing of plane_axes included
+ *   n = -g * rsqrt(g.g + 1e-12)   the unit normal from dense to empty; exactly 0 where g is exactly 0 (outside every plane)
+ * and per ray  normal[b][r][0..2] = sum_s omega_s n_s  over the Sc + Sf samples of the final depth-sorted pass with the colour
+ * weights of the forward, omega = (w_{r-1} + w_r) / 2 at sorted position r (MipRayMarcher2's midpoint rule with the normals as
+ * colours, before its * 2 - 1).  |normal| <= wsum; not normalised; white_back does not enter.  Decoder arithmetic as the forward:
+ * split 16-bit operands given planes_absmax (gradient products: bf16 parts), exact fp32 without it.  One writer per ray, no
+ * atomics: two calls give the same bits.  Forward only (its gradient would be a second derivative of the gather).
+ * HFAGP_EBADARG, nothing launched: fwd, normal, fwd->state or fwd->planes NULL (then the checks of hfagp_raymarch_fwd on the
+ * inputs); HFAGP_EUNSUPPORTED: sample counts the forward does not support.                                                    */
+int hfagp_raymarch_normals(const HfagpRaymarchArgs* fwd, float* normal /* [B][R][3] */, void* stream);
 
 /* ------------------------------------------------------------------ point queries (ABI 13)
  * The decoder at arbitrary points, no compositing: per point the same tri-plane gather and OSGDecoder the ray marcher runs,
