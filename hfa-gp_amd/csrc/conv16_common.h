@@ -69,6 +69,29 @@ __device__ __forceinline__ void a16_store(char* buf, int a_part, int lds_a, floa
     for (int q = 0; q < NP; ++q) *reinterpret_cast<uint2*>(buf + q * a_part + lds_a) = parts[q];
 }
 
+// ---- epilogue operands of the conv GEMM loops (modconv_bf16.hip).  A lane's noise, dcoef, bias and rgb_w values are fetched as ONE
+// batch in front of its first store, and neither the batch nor the store nest holds a branch: an operand that is absent is read
+// through a resource of zero bytes (the load returns 0 without touching memory), a load of a row or column past the image is
+// clamped into it, and the store of an element outside the image gets the offset EPI_OOB, beyond any resource (dropped by the range
+// check).  Loads that sit between the stores are each waited for with vmcnt(0), which on this target drains the store in front as
+// well: 64 L2 round trips in series per lane in the previous form of these epilogues.
+// Only the vector offset and the instruction's immediate take part in the range check, the scalar offset does not: whatever can be
+// out of range goes into the vector offset.
+constexpr unsigned EPI_OOB = 0x80000000u;
+// resource over `bytes` bytes at p (wave-uniform arguments); none at all for p == nullptr
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t epi_rsrc(const void* p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, p ? bytes : 0u, 0x00020000);
+}
+__device__ __forceinline__ float epi_load(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
+}
+__device__ __forceinline__ void epi_store(__amdgpu_buffer_rsrc_t r, unsigned byte_off, float v) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, byte_off, 0, 0);
+}
+// the loaded value x is in its register from here on: the wait for the batch stands here, in front of the stores, and not where
+// the compiler sinks the first use to (behind the stores, a wait for x is a wait for them: vmcnt retires in order)
+__device__ __forceinline__ void epi_landed(float& x) { asm volatile("" : "+v"(x)); }
+
 // the streaming up-sampling layer for Cin = 32 (upfir_lean.hip), planned and launched from upconv_fir.hip's entry points
 struct LeanParams {
     const float* x; const void* wt; const float* styles; const float* dcoef; const float* noise; const float* bias;

@@ -31,7 +31,11 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
     constexpr bool F16 = kind_f16(KD);
     constexpr bool XH = (IO & 1) != 0, YH = (IO & 2) != 0;
     constexpr int XB = XH ? 2 : 4;                       // bytes per input element
-    static_assert(IO == 0 || KD == 1, "fp16 storage goes with the single-pass fp16 arithmetic");
+    static_assert((IO & 3) == 0 || KD == 1, "fp16 storage goes with the single-pass fp16 arithmetic");
+    // IO bit 2: the epilogue this kernel had before its loads were batched (developer switch HFAGP_DEV_CONV_EPILOGUE_LEGACY=1,
+    // instantiated for the F16X3 forward 3x3 conv only: launch_modconv_bf16)
+    constexpr bool ELEG = (IO & 4) != 0;
+    static_assert(!ELEG || (KD == 4 && NTAPS == 9 && IO == 4), "the legacy epilogue is kept for one instantiation");
     // wave grid WM x WN over the 128 x 128 block tile; TM here is the M tiles per wave for WN = 2
     constexpr int WN = 2, WM = 4 / WN, TN = 4 / WN, TMW = 4 / WM, BM = 128, PH = BM / PW;
     static_assert(TM == 2, "block tile is 128 positions");
@@ -305,6 +309,125 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
 #pragma unroll
         for (int i = 0; i < TMW * 16 * 3; ++i) rgbp[i] = 0.f;
     }
+    if constexpr (!ELEG) {
+        // The batched form (conv16_common.h; the 32-channel loop below has the same): a lane's 32 noise values (position (tm, rw, q);
+        // rows and columns past the phase's grid clamped) and, per N tile, dcoef, bias and the three rgb_w in ONE batch in front of
+        // the first store; then, M tile by M tile (its accumulators are free once stored: with all 64 outputs held beside the 96
+        // toRGB sums the fp16 kinds spilled), the outputs in place of their accumulators and their stores, branch-free.  The
+        // arithmetic of an output and the order of the toRGB sums are the previous epilogue's: the same bits.
+        constexpr int EB = YH ? 2 : 4;                                    // bytes per stored element
+        unsigned co_b[TN];                                                // byte offset of the lane's channel in an fp32 vector
+        bool co_ok[TN];                                                   // (Cout = 96: the last 32 columns of the tile do not exist)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+            const int co = co0 + (wn * TN + tn) * 32 + l31;
+            co_b[tn] = (unsigned)co * 4u;
+            co_ok[tn] = co < p.Cout;
+        }
+        float nz[TMW * 16], dv[TN], bv[TN], rw3[TN][RGB ? 3 : 1];
+        if (p.fused) {
+            const __amdgpu_buffer_rsrc_t r_nz = epi_rsrc(p.noise, (unsigned)(p.Ho * p.Wo) * 4u);
+            const __amdgpu_buffer_rsrc_t r_d = epi_rsrc(p.dcoef ? p.dcoef + (size_t)b * p.Cout : nullptr, (unsigned)p.Cout * 4u);
+            const __amdgpu_buffer_rsrc_t r_b = epi_rsrc(p.bias, (unsigned)p.Cout * 4u);
+            const __amdgpu_buffer_rsrc_t r_w = epi_rsrc(do_rgb ? p.rgb_w + (size_t)b * 3 * p.Cout : nullptr, (unsigned)(3 * p.Cout) * 4u);
+#pragma unroll
+            for (int tm = 0; tm < TMW; ++tm)
+#pragma unroll
+                for (int rw = 0; rw < 2; ++rw) {
+                    const int oy = ph.sy * min(m0 + 2 * (wm * TMW + tm) + rw, ph.mh - 1) + ph.oy0;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const int n = min(n0 + 8 * (q >> 2) + 4 * h + (q & 3), ph.mw - 1);
+                        nz[(tm * 2 + rw) * 8 + q] = epi_load(r_nz, (unsigned)(oy * p.Wo + ph.ox0 + ph.sx * n) * 4u);
+                    }
+                }
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) {                             // (a channel past Cout is past these resources: 0)
+                dv[tn] = epi_load(r_d, co_b[tn]);
+                bv[tn] = epi_load(r_b, co_b[tn]);
+                if constexpr (RGB) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) rw3[tn][c] = epi_load(r_w, (unsigned)(c * p.Cout) * 4u + co_b[tn]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < TMW * 16; ++i) epi_landed(nz[i]);
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) {
+                epi_landed(dv[tn]);
+                epi_landed(bv[tn]);
+                if constexpr (RGB) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) epi_landed(rw3[tn][c]);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < TMW * 16; ++i) nz[i] = p.noise ? nz[i] * p.noise_strength : 0.f;
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) dv[tn] = p.dcoef ? dv[tn] * sback : sback;
+        }
+        // the stores go through a resource that starts at the tile's first output element (row sy m0 + oy0, column ox0 of sample b)
+        // and ends with the tile's rows or with the image: an element outside the grid or past Cout gets EPI_OOB
+        const int oyb = ph.sy * m0 + ph.oy0;
+        const unsigned pix_b = (unsigned)p.Cout * EB, row_b = (unsigned)p.Wo * pix_b;
+        char* base = (YH ? reinterpret_cast<char*>(p.out) : reinterpret_cast<char*>(out)) + (((size_t)b * p.Ho + oyb) * p.Wo + ph.ox0) * pix_b;
+        const __amdgpu_buffer_rsrc_t r_y = epi_rsrc(p.out ? base : nullptr, (unsigned)min((p.Ho - oyb) * p.Wo - ph.ox0, ph.sy * PH * p.Wo) * pix_b);
+#pragma unroll
+        for (int tm = 0; tm < TMW; ++tm) {
+            if (p.fused) {
+                // an element outside the grid or past Cout counts for nothing in vmax; a channel past Cout adds nothing to the toRGB
+                // sums (the sums of a position outside the grid are never written)
+#pragma unroll
+                for (int rw = 0; rw < 2; ++rw) {
+                    const bool row_ok = m0 + 2 * (wm * TMW + tm) + rw < ph.mh;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const bool ok = row_ok && n0 + 8 * (q >> 2) + 4 * h + (q & 3) < ph.mw;
+#pragma unroll
+                        for (int tn = 0; tn < TN; ++tn) {
+                            const float v = lrelu_gain_clamp(acc[tm][tn][8 * rw + q] * dv[tn] + bv[tn] + nz[(tm * 2 + rw) * 8 + q], p.act,
+                                                             p.alpha, p.gain, p.clamp);
+                            acc[tm][tn][8 * rw + q] = v;
+                            vmax = fmaxf(vmax, ok && co_ok[tn] ? fabsf(v) : 0.f);
+                            if constexpr (RGB) {
+                                const float vc = co_ok[tn] ? v : 0.f;
+#pragma unroll
+                                for (int c = 0; c < 3; ++c)
+                                    rgbp[((tm * 2 + rw) * 8 + q) * 3 + c] = fmaf(vc, rw3[tn][c], rgbp[((tm * 2 + rw) * 8 + q) * 3 + c]);
+                            }
+                        }
+                    }
+                }
+            } else if constexpr (F16) {
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[tm][tn][r] *= sback;      // (element by element: no packed fp32, build.sh)
+            }
+            if (p.out) {                     // (NULL: the caller only wants the fused toRGB sums — last SR layer, forward only)
+#pragma unroll
+                for (int rw = 0; rw < 2; ++rw) {
+                    const int mr = 2 * (wm * TMW + tm) + rw;                 // row of the tile
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        const int n = n0 + 8 * (q >> 2) + 4 * h + (q & 3);
+                        const bool ok = m0 + mr < ph.mh && n < ph.mw;
+                        const unsigned pos_b = (unsigned)(ph.sy * mr) * row_b + (unsigned)(ph.sx * n) * pix_b;
+#pragma unroll
+                        for (int tn = 0; tn < TN; ++tn) {
+                            const unsigned off = ok && co_ok[tn] ? pos_b + (co_b[tn] >> 2) * EB : EPI_OOB;
+                            if constexpr (YH)
+                                __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(short, (_Float16)acc[tm][tn][8 * rw + q]), r_y, off, 0, 0);
+                            else
+                                epi_store(r_y, off, acc[tm][tn][8 * rw + q]);
+                        }
+                    }
+                }
+            }
+        }
+        if (p.fused && p.y_absmax) publish_absmax(p.y_absmax, vmax, blockIdx.x * 4 + wave);
+    }
+    if constexpr (ELEG) {
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn) {
         const int co = co0 + (wn * TN + tn) * 32 + l31;
@@ -358,6 +481,7 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
             }
     }
     if (p.fused && p.y_absmax) publish_absmax(p.y_absmax, vmax, blockIdx.x * 4 + wave);
+    }   // ELEG
     if constexpr (RGB) {
         if (do_rgb) {
             // reduce-scatter over the 32 channel lanes: at the step with lane bit m the lane keeps one half of its values
@@ -703,7 +827,10 @@ constexpr size_t lds_bytes(int cin) { return (size_t)2 * A_BUF + (size_t)(cin + 
 
 template <int KD, int TM, int NTAPS, int IO, int LOOP>
 __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p, const int) {
-    static_assert(KD == 4 && TM == 2 && NTAPS == 9 && IO == 0 && LOOP == 1, "the 32-channel loop is the F16X3 forward 3x3 conv");
+    static_assert(KD == 4 && TM == 2 && NTAPS == 9 && IO == 0 && (LOOP == 1 || LOOP == 3), "the 32-channel loop is the F16X3 forward 3x3 conv");
+    // LOOP = 3: the same kernel with the epilogue it had before its loads were batched (developer switch
+    // HFAGP_DEV_CONV_EPILOGUE_LEGACY=1, launch_modconv_bf16): each output's operands fetched between the stores
+    constexpr bool LEGACY = LOOP == 3;
     using namespace c9;
     typedef float f32x4v __attribute__((ext_vector_type(4)));
     extern __shared__ __attribute__((aligned(16))) char lds_raw[];
@@ -876,6 +1003,87 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
     float rgbp[16 * 3];                                                // [position 4 tm + r][rgb]
 #pragma unroll
     for (int i = 0; i < 16 * 3; ++i) rgbp[i] = 0.f;
+    if constexpr (!LEGACY) {
+        if (p.fused) {
+            // The lane's operands in ONE batch (conv16_common.h): 16 noise values (row 4 wm + tm, column 4 g + r; rows and columns
+            // past the image clamped) and, per N tile, dcoef, bias and the three rgb_w: 52 loads, one wait, in front of the first
+            // store.  The arithmetic of an output and the order of the toRGB sums are the previous epilogue's: the same bits.
+            const __amdgpu_buffer_rsrc_t r_nz = epi_rsrc(p.noise, (unsigned)(p.Ho * p.Wo) * 4u);
+            const __amdgpu_buffer_rsrc_t r_d = epi_rsrc(p.dcoef ? p.dcoef + (size_t)b * p.Cout : nullptr, (unsigned)p.Cout * 4u);
+            const __amdgpu_buffer_rsrc_t r_b = epi_rsrc(p.bias, (unsigned)p.Cout * 4u);
+            const __amdgpu_buffer_rsrc_t r_w = epi_rsrc(do_rgb ? p.rgb_w + (size_t)b * 3 * p.Cout : nullptr, (unsigned)(3 * p.Cout) * 4u);
+            const unsigned co_b = (unsigned)(co0 + wn * 64 + i16) * 4u;   // byte offset of the lane's channel in N tile 0; tile tn: + 64 tn
+            float nz[16], dv[4], bv[4], rw3[4][3];
+#pragma unroll
+            for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    nz[tm * 4 + r] = epi_load(r_nz, (unsigned)(min(m0 + 4 * wm + tm, p.Ho - 1) * p.Wo + min(n0 + 4 * g + r, p.Wo - 1)) * 4u);
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn) {
+                dv[tn] = epi_load(r_d, co_b + 64u * tn);
+                bv[tn] = epi_load(r_b, co_b + 64u * tn);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rw3[tn][c] = epi_load(r_w, (unsigned)(c * p.Cout) * 4u + co_b + 64u * tn);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) epi_landed(nz[i]);
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn) {
+                epi_landed(dv[tn]);
+                epi_landed(bv[tn]);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) epi_landed(rw3[tn][c]);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; ++i) nz[i] = p.noise ? nz[i] * p.noise_strength : 0.f;
+#pragma unroll
+            for (int tn = 0; tn < 4; ++tn) dv[tn] = p.dcoef ? dv[tn] * sback : sback;      // (no bias, no toRGB: those loads returned 0)
+            // the outputs, in place of their accumulators; an element outside the image counts for nothing in vmax (and its toRGB
+            // sums belong to a position that is never written)
+#pragma unroll
+            for (int tm = 0; tm < 4; ++tm) {
+                const bool row_ok = m0 + 4 * wm + tm < p.Ho;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const bool ok = row_ok && n0 + 4 * g + r < p.Wo;
+#pragma unroll
+                    for (int tn = 0; tn < 4; ++tn) {
+                        const float v = lrelu_gain_clamp(acc[tm][tn][r] * dv[tn] + bv[tn] + nz[tm * 4 + r], p.act, p.alpha, p.gain, p.clamp);
+                        acc[tm][tn][r] = v;
+                        vmax = fmaxf(vmax, ok ? fabsf(v) : 0.f);
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) rgbp[(tm * 4 + r) * 3 + c] = fmaf(v, rw3[tn][c], rgbp[(tm * 4 + r) * 3 + c]);
+                    }
+                }
+            }
+            // (in front of the stores: its look at the slot is a load, and the wait for it would wait for every store as well)
+            if (p.y_absmax) publish_absmax(p.y_absmax, vmax, blockIdx.x * 4 + wave);
+        } else {
+#pragma unroll
+            for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < 4; ++tn)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[tm][tn][r] *= sback;       // (element by element: no packed fp32, build.sh)
+        }
+        // the stores, branch-free, through a resource over the rows of this tile that the image has (a row past the image is past
+        // the resource); a column past the image gets EPI_OOB.  (No y wanted — the last layer in front of a fused toRGB: no stores.)
+        if (p.out) {
+            const unsigned row_b = (unsigned)(p.Wo * p.Cout) * 4u, col_b = (unsigned)p.Cout * 4u;
+            const __amdgpu_buffer_rsrc_t r_y = epi_rsrc(out + ((size_t)b * p.Ho + m0) * p.Wo * p.Cout, (unsigned)min(8, p.Ho - m0) * row_b);
+            const unsigned y_b = (unsigned)(4 * wm) * row_b + (unsigned)(n0 + 4 * g) * col_b + (unsigned)(co0 + wn * 64 + i16) * 4u;
+#pragma unroll
+            for (int tm = 0; tm < 4; ++tm)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const unsigned off = n0 + 4 * g + r < p.Wo ? y_b + tm * row_b + r * col_b : EPI_OOB;
+#pragma unroll
+                    for (int tn = 0; tn < 4; ++tn) epi_store(r_y, off + 64u * tn, acc[tm][tn][r]);
+                }
+        }
+    }
+    if constexpr (LEGACY) {
 #pragma unroll
     for (int tn = 0; tn < 4; ++tn) {
         const int co = co0 + wn * 64 + tn * 16 + i16;
@@ -911,6 +1119,7 @@ __global__ void __launch_bounds__(256, 2) modconv_bf16_kernel(const ConvParams p
         }
     }
     if (p.fused && p.y_absmax) publish_absmax(p.y_absmax, vmax, blockIdx.x * 4 + wave);
+    }   // LEGACY
     if (do_rgb) {
         // reduce-scatter over the 16 channel lanes (as in the 16-channel loop): afterwards lane i16 owns position i16 = 4 tm + r
         int n = 16 * 3;
@@ -1219,9 +1428,15 @@ static size_t bf16_lds_bytes(int cin) {
 }
 
 template <int KD>
-static void launch_group(const Plan& pl, int phase0, int nphase, int ntaps, int cin, hipStream_t s) {
+static void launch_group(const Plan& pl, int phase0, int nphase, int ntaps, int cin, bool epi_legacy, hipStream_t s) {
     const dim3 grid(pl.grid.x, (unsigned)nphase, 1);
     const size_t lds = bf16_lds_bytes<kind_parts_a(KD), 2>(cin);
+    if constexpr (KD == 4) {            // developer A/B of the epilogue (modconv_plan.h)
+        if (ntaps == 9 && epi_legacy) {
+            modconv_bf16_kernel<4, 2, 9, 4><<<grid, 256, lds, s>>>(pl.p, phase0);
+            return;
+        }
+    }
     switch (ntaps) {
         case 9: modconv_bf16_kernel<KD, 2, 9><<<grid, 256, lds, s>>>(pl.p, phase0); break;
         case 4: modconv_bf16_kernel<KD, 2, 4><<<grid, 256, lds, s>>>(pl.p, phase0); break;
@@ -1313,6 +1528,10 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
                   "up-conv: of 64)", a->Cin, CKB, a->Cout, BNB);
     HFAGP_REQUIRE(pl.bn == BNB && pl.bm == 128, HFAGP_EUNSUPPORTED, "modconv (16-bit MFMA): unexpected plan");
     HFAGP_REQUIRE(a->Cin <= 512, HFAGP_EUNSUPPORTED, "modconv (16-bit MFMA): Cin=%d > 512 (style image in LDS)", a->Cin);
+    // (modconv_bf16_kernel's epilogues store through a buffer resource over the up to 16 output rows of a tile: 32-bit byte offsets
+    // below EPI_OOB; the merged up-conv kernels address y_t with pointers)
+    HFAGP_REQUIRE(pl.merged_up || (long long)pl.p.Wo * pl.p.Cout < (1ll << 25), HFAGP_EUNSUPPORTED,
+                  "modconv (16-bit MFMA): an output row of %d x %d elements exceeds the 32-bit tile offsets", pl.p.Wo, pl.p.Cout);
     const int kd = kind_of(a->precision);
     HFAGP_REQUIRE(kd != 0, HFAGP_EBADARG, "modconv: unknown precision %d", a->precision);
     const int io = (a->x_f16 ? 1 : 0) | (a->y_f16 ? 2 : 0);
@@ -1358,7 +1577,8 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
         return check_launch("modconv_fwd (16-bit MFMA, merged adjoint of the up-conv)");
     }
     if (conv9_mfma16_takes(a)) {        // the forward 3x3 conv at F16X3: the 32-channel 16x16x32 loop
-        modconv_bf16_kernel<4, 2, 9, 0, 1><<<pl.grid, 256, c9::lds_bytes(a->Cin), s>>>(p, 0);
+        if (conv_epilogue_legacy()) modconv_bf16_kernel<4, 2, 9, 0, 3><<<pl.grid, 256, c9::lds_bytes(a->Cin), s>>>(p, 0);
+        else modconv_bf16_kernel<4, 2, 9, 0, 1><<<pl.grid, 256, c9::lds_bytes(a->Cin), s>>>(p, 0);
         return check_launch("modconv_fwd (16-bit MFMA, 32-channel loop)");
     }
     for (int p0 = 0; p0 < p.nphase;) {
@@ -1366,7 +1586,8 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
         while (p0 + n < p.nphase && p.phase[p0 + n].ntaps == p.phase[p0].ntaps) ++n;
         const int nt = p.phase[p0].ntaps;
         HFAGP_REQUIRE(nt == 9 || nt == 4 || nt == 2 || nt == 1, HFAGP_EUNSUPPORTED, "modconv (16-bit MFMA): %d taps", nt);
-        with_kind(kd, [&](auto k) { launch_group<decltype(k)::value>(pl, p0, n, nt, a->Cin, s); });
+        const bool epi_legacy = a->mode == HFAGP_CONV3X3 && conv_epilogue_legacy();
+        with_kind(kd, [&](auto k) { launch_group<decltype(k)::value>(pl, p0, n, nt, a->Cin, epi_legacy, s); });
         p0 += n;
     }
     return check_launch("modconv_fwd (16-bit MFMA)");

@@ -255,6 +255,14 @@ static inline bool conv9_mfma16_takes(const HfagpModconvArgs* a) {
            a->Cin % 32 == 0 && a->Cin <= 512 && a->Cout % 128 == 0;
 }
 
+// Developer switch HFAGP_DEV_CONV_EPILOGUE_LEGACY=1 (read at every call, so one process can time both): the forward 3x3 conv at
+// F16X3 with the epilogue it had before its loads were batched — modconv_bf16_kernel<4, 2, 9, 0, 3> for the
+// 32-channel loop, <4, 2, 9, 4> for the 16-channel one (HFAGP_DEV_CONV9_LEGACY=1).  Every other instantiation has the batched form only.
+static inline bool conv_epilogue_legacy() {
+    const char* dev = getenv("HFAGP_DEV_CONV_EPILOGUE_LEGACY");
+    return dev && atoi(dev) == 1;
+}
+
 // The merged up-conv at F16X3 with fp32 storage runs the 32-channel 16x16x32 loop of upconv_bf16_kernel<4, 4, 0, 2> in its
 // 4-wave block (launch_modconv_bf16 checks the block and the staged span); f16, f16x2, the bf16 kinds, fp16 storage, Cin = 16 and
 // the 8-wave developer variant stay on the 16-channel loop.  No shape is excluded: at B = 32 all seven flagship layers, 4^2 to
