@@ -17,25 +17,9 @@
 //   The importance depths carry no gradient (EG3D: no_grad + detach), neither do the camera / depths.
 #include <algorithm>
 #include <cstdlib>
-#include "raymarch_common.h"
+#include "decoder_adjoint.h"
 
 namespace hfagp {
-
-struct TileLds {
-    float df[16 * 32];        // dL/dfeature of the 16 samples, [sample][channel]
-    __attribute__((aligned(16))) int   idx[12 * 16];       // texel index of every tap, [plane*4 + tap][sample]
-    __attribute__((aligned(16))) float wgt[12 * 16];       // bilinear weight / 3
-};
-
-// decoder-weight gradients (PG): per-tile operand images for the sample-contracting products
-// (planes_query_bwd.hip carries a COPY of this PG code — GradLds, the operand images and MFMA products per tile, the flush at the
-// end of the kernel — for free points: a change here belongs there too)
-//   dW1c[32x64] += dO[32x16] . SP^T[16x64]      dW0[64x32] += dHpre[64x16] . F[16x32]
-struct GradLds {
-    float sp[64 * 17], dp[64 * 17], dO[32 * 17], f[16 * 33];
-};
-
-struct DecGrads { float *w0, *b0, *w1, *b1; };   // [64][32], [64], [33][64], [33]; accumulated with atomics
 
 // MIRROR: the projections of planes 1 and 2 are (x,z) and (z,x) on square planes (EG3D's original axes): their taps
 // are the same texels with row/column swapped and bitwise the same weights, and dL/dfeature is shared by the three
@@ -80,50 +64,14 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
     const int R = a.res * a.res;
     constexpr int NT = S / 16;
 
-    if (wave == 0) {
-        DecoderRegs dec;
-        load_decoder(a, j, g, dec);
-        if constexpr (DEC16) {
-            Dec16Regs d16;
-            make_dec16(dec, a.planes_absmax, lane, d16);
-            store_dec16_lds(d16, wfwd, lane);
-        } else {
-            store_decoder_lds(dec, wfwd, lane);
-        }
-    }
-    if constexpr (DEC16) {
-        build_grad16_lds(a, w1t, w0t, lane, wave, NWB);
-        __syncthreads();
-    } else {
-        const float g0 = a.decoder_lr_mul * 0.17677669529663687f, g1 = a.decoder_lr_mul * 0.125f;
-        for (int i = threadIdx.x; i < 4 * 8 * 64; i += NTHB) {
-            const int l = i & 63, st = (i >> 6) & 7, mt = i >> 9, jj = l & 15, gg = l >> 4;
-            w1t[i] = a.dec_w1[(1 + 16 * (st >> 2) + 4 * gg + (st & 3)) * 64 + 16 * mt + jj] * g1;
-        }
-        for (int i = threadIdx.x; i < 2 * 16 * 64; i += NTHB) {
-            const int l = i & 63, st = (i >> 6) & 15, ft = i >> 10, jj = l & 15, gg = l >> 4;
-            w0t[i] = a.dec_w0[(16 * (st >> 2) + 4 * gg + (st & 3)) * 32 + 16 * ft + jj] * g0;
-        }
-        __syncthreads();
-    }
+    if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
+    if constexpr (DEC16) build_grad16_lds(a, w1t, w0t, lane, wave, NWB);
+    else build_grad_lds(a, w1t, w0t, threadIdx.x, NTHB);
+    __syncthreads();
 
     GradLds& gl = reinterpret_cast<GradLds*>(glds_raw)[PG ? wave : 0];      // never dereferenced unless PG
-    f32x4 aw1[2][4], aw0[4][2];                      // PG: dW1c tiles [ct][kt], dW0 tiles [kt][ft]
-    float s_dO[2][4], s_dp[4][4], s_sw[4][4], s_ds = 0.f;
-    if constexpr (PG) {
-#pragma unroll
-        for (int x = 0; x < 2; ++x)
-#pragma unroll
-            for (int y = 0; y < 4; ++y) {
-                aw1[x][y] = f32x4{0.f, 0.f, 0.f, 0.f};
-                aw0[y][x] = f32x4{0.f, 0.f, 0.f, 0.f};
-                s_dO[x][y] = 0.f;
-            }
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-#pragma unroll
-            for (int y = 0; y < 4; ++y) { s_dp[x][y] = 0.f; s_sw[x][y] = 0.f; }
-    }
+    DecGradAcc acc;                                  // PG: a wave's sums over its tiles
+    if constexpr (PG) dec_grad_zero(acc);
 
     // XCD-local schedule over (ray in column-strip order, tile of the ray): raymarch_common.h ray_schedule
     // (WIDE: the schedule runs over RAYS and a wave walks the tiles of its ray in sequence — ray generation and the ray's dL/dfeat
@@ -221,9 +169,7 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
             rec = r_cur.rec; gfeat[0] = r_cur.gf[0]; gfeat[1] = r_cur.gf[1];
             ray = r_cur.ray; tt = r_cur.tt; slots = r_cur.slots;
             finish_gather(g_cur, f);
-            const int src = 4 * j + g;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) f[c] = __shfl(f[c], src);
+            quad_to_mfma(f, lane);
             r_cur = r_nxt; r_nxt = r_nn; g_cur = g_nxt;
         } else {
         tt = WIDE ? tw : __builtin_amdgcn_readfirstlane((int)(tile % NT));        // wave-uniform -> scalar registers
@@ -241,17 +187,9 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
         const int s = 16 * tt + j;
         rec = *reinterpret_cast<const float4*>(p.rec + ((size_t)ray * S + s) * 4);   // depth, omega, dsigma
         if constexpr (SCATTER) sample_taps(p, o3, d3, rec.x, taps);          // taps of sample j: the scatter below publishes them
-        {
-            // gather in the quad layout of raymarch_kernel (4 adjacent lanes per texel line), then to the MFMA layout
-            PlaneTaps tq[3];
-            const float zq_cur = zqw;
-            if constexpr (WIDE) zqw = p.rec[((size_t)ray * S + 16 * min(tt + 1, NT - 1) + (lane >> 2)) * 4];
-            sample_taps(p, o3, d3, zq_cur, tq);
-            gather8(a, b, lane & 3, tq, f);
-            const int src = 4 * j + g;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) f[c] = __shfl(f[c], src);
-        }
+        const float zq_cur = zqw;
+        if constexpr (WIDE) zqw = p.rec[((size_t)ray * S + 16 * min(tt + 1, NT - 1) + (lane >> 2)) * 4];
+        gather8_mfma(p, b, o3, d3, zq_cur, lane, f);
         gfeat[0] = gfw[0]; gfeat[1] = gfw[1];
         if constexpr (!SCATTER) {
             if (ro.dfs) slots = load_df_slots(ro, (size_t)ray * S + s);
@@ -264,213 +202,32 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
         if constexpr (DEC16) decoder_fwd16_lds<true>(wfwd, ln, f, hp, h, sigma, o);
         else decoder_fwd_lds<true>(wfwd, ln, f, hp, h, sigma, o);
 
-        // dL/do (colour logits) in the C layout: lane (j, g), register r of tile ot -> channel 16ot + 4g + r
-        //   colour = sigmoid(o) * 1.002 - 0.001,  dL/dcolour = omega * 2 dL/dfeat
+        // decoder adjoint: dL/dcolour = omega * 2 dL/dfeat, dL/dsigma = rec.z  ->  dH, dF
         f32x4 dO[2];
-#pragma unroll
-        for (int ot = 0; ot < 2; ++ot) {
-            const float4 gf = gfeat[ot];
-            const float gv[4] = {gf.x, gf.y, gf.z, gf.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float sg = sigmoid_f(o[ot][r]);
-                dO[ot][r] = rec.y * 2.f * gv[r] * 1.002f * sg * (1.f - sg);
-            }
-        }
-        // dH^T = W1c^T . dO^T + wsig (x) dsigma:  A[i][k] = W1[1 + c(k)][16mt + i],  c(k) = 16ot + 4g + r
+        ray_colour_logit_grad(o, rec.y, gfeat, dO);
         f32x4 dH[4];
         f32x4 dF[2];
         if constexpr (DEC16) decoder_bwd16_lds(wfwd, w1t, w0t, ln, dO, rec.z, hp, dH, dF);
-#pragma unroll
-        for (int mt = 0; mt < (DEC16 ? 0 : 4); ++mt) {
-            const float* ws_ = wfwd + (48 + mt * 4) * 64 + ln;
-            dH[mt] = f32x4{ws_[0] * rec.z, ws_[64] * rec.z, ws_[128] * rec.z, ws_[192] * rec.z};
-#pragma unroll
-            for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float wA = w1t[(mt * 8 + ot * 4 + r) * 64 + ln];
-                    dH[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dO[ot][r], dH[mt], 0, 0, 0);
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dH[mt][r] *= sigmoid_f(hp[mt][r]);      // softplus' = sigmoid
-        }
-        // dF^T = W0^T . dHpre^T:  A[i][k] = W0[16mt + 4g + r][16ft + i]
-#pragma unroll
-        for (int ft = 0; ft < 2; ++ft) {
-            if constexpr (!DEC16) {
-                dF[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float wA = w0t[(ft * 16 + mt * 4 + r) * 64 + ln];
-                        dF[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dH[mt][r], dF[ft], 0, 0, 0);
-                    }
-            }
-            // lane (j, g), register r -> feature channel 16ft + 4g + r of sample j
-            if constexpr (SCATTER)
-                *reinterpret_cast<float4*>(&lds.df[j * 32 + 16 * ft + 4 * g]) =
-                    make_float4(dF[ft][0], dF[ft][1], dF[ft][2], dF[ft][3]);
-        }
-        if constexpr (!SCATTER) {           // sort + gather form of d planes (raymarch_rows.hip): dL/dF to the sample's slots
-            if (ro.dfs) store_df_sorted(ro, slots, g, dF);
-        }
-        if constexpr (PG) {
-            // operand images for the weight-gradient products + running bias / sigma-row sums
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    gl.sp[(16 * mt + 4 * g + r) * 17 + j] = h[mt][r];
-                    gl.dp[(16 * mt + 4 * g + r) * 17 + j] = dH[mt][r];
-                    s_dp[mt][r] += dH[mt][r];
-                    s_sw[mt][r] += rec.z * h[mt][r];
-                }
-#pragma unroll
-            for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    gl.dO[(16 * ot + 4 * g + r) * 17 + j] = dO[ot][r];
-                    s_dO[ot][r] += dO[ot][r];
-                }
-#pragma unroll
-            for (int t = 0; t < 8; ++t) gl.f[j * 33 + 8 * g + t] = f[t];
-            if (g == 0) s_ds += rec.z;
-            WAVE_SYNC();
-            // MFMA operands: A[i][k] -> lane (i = j, k = g); B[k][n] -> lane (k = g, n = j); 4 samples per step
-#pragma unroll
-            for (int st = 0; st < 4; ++st) {
-                const int smp = 4 * st + g;
-                float a1[2], bsp[4], a0[4], bf[2];
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) a1[ct] = gl.dO[(16 * ct + j) * 17 + smp];
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt) {
-                    bsp[kt] = gl.sp[(16 * kt + j) * 17 + smp];
-                    a0[kt] = gl.dp[(16 * kt + j) * 17 + smp];
-                }
-#pragma unroll
-                for (int ft = 0; ft < 2; ++ft) bf[ft] = gl.f[smp * 33 + 16 * ft + j];
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-                    for (int kt = 0; kt < 4; ++kt)
-                        aw1[ct][kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[ct], bsp[kt], aw1[ct][kt], 0, 0, 0);
-#pragma unroll
-                for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                    for (int ft = 0; ft < 2; ++ft)
-                        aw0[kt][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[kt], bf[ft], aw0[kt][ft], 0, 0, 0);
-            }
-        }
+        else decoder_bwd_lds(wfwd, w1t, w0t, ln, dO, rec.z, hp, dH, dF);
         if constexpr (SCATTER) {
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl)                 // lane (j, g = pl) publishes plane pl's taps of sample j
-            if (g == pl) {                             // tap-major [plane*4 + tap][sample]: the scatter reads 16 samples as b128
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    lds.idx[(pl * 4 + k) * 16 + j] = taps[pl].idx[k];
-                    lds.wgt[(pl * 4 + k) * 16 + j] = taps[pl].w[k] * 0.3333333333333333f;
-                }
-            }
-        WAVE_SYNC();
-        // ---- scatter: lane = channel, half-wave hf walks tap (2kp + hf) of one plane through the 16 depth-sorted
-        // samples and MERGES RUNS: consecutive samples whose tap lands on the same texel (the plane the ray is steep
-        // to moves < 1 texel per sample; the importance samples cluster) are summed in a register and leave as one
-        // 128-byte atomic: 96 -> ~67 atomics per tile on the bench workload (plane (x,y): 3.0 taps per run, the two
-        // depth planes: 1.1).  Measured 9.3 -> 8.8 ms per 4 frames; without any atomics the call takes 2.7 ms, i.e.
-        // the cost follows the number of DISTINCT lines touched more than the number of atomic instructions.
-        {
-            const int c = lane & 31, hf = lane >> 5;
-            float* base = d_planes + (size_t)b * 3 * a.H * a.W * 32 + c;
-            float dfc[16];                             // dL/dfeature[sample][c] of the tile: read once, used by every tap
-#pragma unroll
-            for (int sm = 0; sm < 16; ++sm) dfc[sm] = lds.df[sm * 32 + c];
-#pragma unroll 1
-            for (int pk = 0; pk < (MIRROR ? 4 : 6); ++pk) {
-                const int pl = pk >> 1, k = 2 * (pk & 1) + hf;
-                float* pbase = base + (size_t)pl * a.H * a.W * 32;
-                float wv[16];
-                int tv[16];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {          // the 16 samples of this tap: 4 + 4 ds_read_b128 (half-wave broadcast)
-                    const float4 w4 = *reinterpret_cast<const float4*>(&lds.wgt[(pl * 4 + k) * 16 + 4 * q]);
-                    const int4 t4 = *reinterpret_cast<const int4*>(&lds.idx[(pl * 4 + k) * 16 + 4 * q]);
-                    wv[4 * q] = w4.x; wv[4 * q + 1] = w4.y; wv[4 * q + 2] = w4.z; wv[4 * q + 3] = w4.w;
-                    tv[4 * q] = t4.x; tv[4 * q + 1] = t4.y; tv[4 * q + 2] = t4.z; tv[4 * q + 3] = t4.w;
-                }
-                int cur = -1;
-                float run = 0.f;
-#pragma unroll
-                for (int sm = 0; sm < 16; ++sm) {
-                    const float wgt = wv[sm];
-                    const int t = tv[sm];
-                    const float v = dfc[sm] * wgt;
-                    if (wgt != 0.f) {
-                        if (t == cur) {
-                            run += v;
-                        } else {
-#ifndef HFAGP_NO_ATOMICS
-                            if (cur >= 0) unsafeAtomicAdd(pbase + (size_t)cur * 32, run);
-#endif
-                            cur = t;
-                            run = v;
-                        }
-                    }
-                }
-#ifndef HFAGP_NO_ATOMICS
-                if (cur >= 0) unsafeAtomicAdd(pbase + (size_t)cur * 32, run);
-#endif
-            }
+            for (int ft = 0; ft < 2; ++ft) publish_df(lds, j, g, ft, dF[ft]);
+        } else {                            // sort + gather form of d planes (raymarch_rows.hip): dL/dF to the sample's slots
+            if (ro.dfs) store_df_sorted(ro, slots, g, dF);
         }
-        }   // SCATTER
+        if constexpr (PG) dec_grad_tile(acc, gl, j, g, f, h, dH, dO, rec.z);
+        if constexpr (SCATTER) {
+            // taps of sample j + dL/dF through LDS, then run-merged 128-byte atomics (plane 2 is left to the mirror under MIRROR)
+#pragma unroll
+            for (int pl = 0; pl < 3; ++pl)
+                if (g == pl) publish_taps(lds, pl, taps[pl], j, true);
+            WAVE_SYNC();
+            scatter_tile_runs<(MIRROR ? 4 : 6)>(lds, d_planes + (size_t)b * 3 * a.H * a.W * 32, (size_t)a.H * a.W * 32, lane);
+        }
         WAVE_SYNC();
     }
     }
-    if constexpr (PG) {
-        // effective weight = parameter * gain  ->  d parameter = d effective * gain
-        const float g0 = a.decoder_lr_mul * 0.17677669529663687f, g1 = a.decoder_lr_mul * 0.125f, gb = a.decoder_lr_mul;
-        // C layout: lane (col = j, rows 4g + r)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-            for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    unsafeAtomicAdd(dg.w1 + (1 + 16 * ct + 4 * g + r) * 64 + 16 * kt + j, aw1[ct][kt][r] * g1);
-#pragma unroll
-        for (int kt = 0; kt < 4; ++kt)
-#pragma unroll
-            for (int ft = 0; ft < 2; ++ft)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    unsafeAtomicAdd(dg.w0 + (16 * kt + 4 * g + r) * 32 + 16 * ft + j, aw0[kt][ft][r] * g0);
-        // per-lane running sums: reduce over the 16 sample lanes (j), lane j == 0 commits
-        auto red16 = [](float v) {
-            v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
-            return v;
-        };
-#pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float vb = red16(s_dp[mt][r]), vw = red16(s_sw[mt][r]);
-                if (j == 0) {
-                    unsafeAtomicAdd(dg.b0 + 16 * mt + 4 * g + r, vb * gb);
-                    unsafeAtomicAdd(dg.w1 + 16 * mt + 4 * g + r, vw * g1);          // sigma row of W1
-                }
-            }
-#pragma unroll
-        for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float v = red16(s_dO[ot][r]);
-                if (j == 0) unsafeAtomicAdd(dg.b1 + 1 + 16 * ot + 4 * g + r, v * gb);
-            }
-        const float vs = red16(s_ds);
-        if (lane == 0) unsafeAtomicAdd(dg.b1, vs * gb);
-    }
+    if constexpr (PG) dec_grad_flush(acc, dg, a.decoder_lr_mul, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -522,30 +279,9 @@ raymarch_bwd_cols_kernel(const RayParams p, float* __restrict__ d_planes, const 
     const int R = a.res * a.res;
     const int nslots = a.H * kColSlots;
 
-    if (wave == 0) {
-        DecoderRegs dec;
-        load_decoder(a, j, g, dec);
-        if constexpr (DEC16) {
-            Dec16Regs d16;
-            make_dec16(dec, a.planes_absmax, lane, d16);
-            store_dec16_lds(d16, wfwd, lane);
-        } else {
-            store_decoder_lds(dec, wfwd, lane);
-        }
-    }
-    if constexpr (DEC16) {
-        build_grad16_lds(a, w1t, w0t, lane, wave, kColWaves);
-    } else {
-        const float g0 = a.decoder_lr_mul * 0.17677669529663687f, g1 = a.decoder_lr_mul * 0.125f;
-        for (int i = threadIdx.x; i < 4 * 8 * 64; i += kColWaves * 64) {
-            const int l = i & 63, st = (i >> 6) & 7, mt = i >> 9, jj = l & 15, gg = l >> 4;
-            w1t[i] = a.dec_w1[(1 + 16 * (st >> 2) + 4 * gg + (st & 3)) * 64 + 16 * mt + jj] * g1;
-        }
-        for (int i = threadIdx.x; i < 2 * 16 * 64; i += kColWaves * 64) {
-            const int l = i & 63, st = (i >> 6) & 15, ft = i >> 10, jj = l & 15, gg = l >> 4;
-            w0t[i] = a.dec_w0[(16 * (st >> 2) + 4 * gg + (st & 3)) * 32 + 16 * ft + jj] * g0;
-        }
-    }
+    if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
+    if constexpr (DEC16) build_grad16_lds(a, w1t, w0t, lane, wave, kColWaves);
+    else build_grad_lds(a, w1t, w0t, threadIdx.x, kColWaves * 64);
     const int c = lane & 31, hf = lane >> 5;
     for (int i = threadIdx.x; i < nslots; i += kColWaves * 64) tag[i] = -1;
     __syncthreads();
@@ -570,62 +306,21 @@ raymarch_bwd_cols_kernel(const RayParams p, float* __restrict__ d_planes, const 
                 PlaneTaps taps[3];
                 sample_taps(p, o3, d3, rec.x, taps);
                 float f[8];
-                {
-                    PlaneTaps tq[3];
-                    sample_taps(p, o3, d3, p.rec[((size_t)ray * S + 16 * tt + (lane >> 2)) * 4], tq);
-                    gather8(a, b, lane & 3, tq, f);
-                    const int src = 4 * j + g;
-#pragma unroll
-                    for (int cc = 0; cc < 8; ++cc) f[cc] = __shfl(f[cc], src);
-                }
+                gather8_mfma(p, b, o3, d3, p.rec[((size_t)ray * S + 16 * tt + (lane >> 2)) * 4], lane, f);
                 f32x4 hp[4], h[4], o[2];
                 float sigma;
                 if constexpr (DEC16) decoder_fwd16_lds<true>(wfwd, lane, f, hp, h, sigma, o);
                 else decoder_fwd_lds<true>(wfwd, lane, f, hp, h, sigma, o);
+                const float4 gfeat[2] = {load_g_feat4(p, (size_t)ray * 32 + 4 * g),
+                                         load_g_feat4(p, (size_t)ray * 32 + 16 + 4 * g)};
                 f32x4 dO[2];
-#pragma unroll
-                for (int ot = 0; ot < 2; ++ot) {
-                    const float4 gf = load_g_feat4(p, (size_t)ray * 32 + 16 * ot + 4 * g);
-                    const float gv[4] = {gf.x, gf.y, gf.z, gf.w};
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float sg = sigmoid_f(o[ot][r]);
-                        dO[ot][r] = rec.y * 2.f * gv[r] * 1.002f * sg * (1.f - sg);
-                    }
-                }
+                ray_colour_logit_grad(o, rec.y, gfeat, dO);
                 f32x4 dH[4];
-                f32x4 dF2[2];
-                if constexpr (DEC16) decoder_bwd16_lds(wfwd, w1t, w0t, lane, dO, rec.z, hp, dH, dF2);
+                f32x4 dF[2];
+                if constexpr (DEC16) decoder_bwd16_lds(wfwd, w1t, w0t, lane, dO, rec.z, hp, dH, dF);
+                else decoder_bwd_lds(wfwd, w1t, w0t, lane, dO, rec.z, hp, dH, dF);
 #pragma unroll
-                for (int mt = 0; mt < (DEC16 ? 0 : 4); ++mt) {
-                    const float* ws_ = wfwd + (48 + mt * 4) * 64 + lane;
-                    dH[mt] = f32x4{ws_[0] * rec.z, ws_[64] * rec.z, ws_[128] * rec.z, ws_[192] * rec.z};
-#pragma unroll
-                    for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float wA = w1t[(mt * 8 + ot * 4 + r) * 64 + lane];
-                            dH[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dO[ot][r], dH[mt], 0, 0, 0);
-                        }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dH[mt][r] *= sigmoid_f(hp[mt][r]);
-                }
-#pragma unroll
-                for (int ft = 0; ft < 2; ++ft) {
-                    f32x4 dF = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if constexpr (DEC16) {
-                        dF = dF2[ft];
-                    } else {
-#pragma unroll
-                        for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const float wA = w0t[(ft * 16 + mt * 4 + r) * 64 + lane];
-                                dF = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dH[mt][r], dF, 0, 0, 0);
-                            }
-                    }
-                    *reinterpret_cast<float4*>(&lds.df[j * 32 + 16 * ft + 4 * g]) = make_float4(dF[0], dF[1], dF[2], dF[3]);
-                }
+                for (int ft = 0; ft < 2; ++ft) publish_df(lds, j, g, ft, dF[ft]);
                 if (g == 0) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
@@ -802,30 +497,9 @@ raymarch_bwd_df_kernel(const RayParams p, float* __restrict__ df_out, const Rows
     const int j = lane & 15, g = lane >> 4;
     const int R = a.res * a.res;
     constexpr int NT = S / 16;
-    if (wave == 0) {
-        DecoderRegs dec;
-        load_decoder(a, j, g, dec);
-        if constexpr (DEC16) {
-            Dec16Regs d16;
-            make_dec16(dec, a.planes_absmax, lane, d16);
-            store_dec16_lds(d16, wfwd, lane);
-        } else {
-            store_decoder_lds(dec, wfwd, lane);
-        }
-    }
-    if constexpr (DEC16) {
-        build_grad16_lds(a, w1t, w0t, lane, wave, kDfWaves);
-    } else {
-        const float g0 = a.decoder_lr_mul * 0.17677669529663687f, g1 = a.decoder_lr_mul * 0.125f;
-        for (int i = threadIdx.x; i < 4 * 8 * 64; i += kDfWaves * 64) {
-            const int l = i & 63, st = (i >> 6) & 7, mt = i >> 9, jj = l & 15, gg = l >> 4;
-            w1t[i] = a.dec_w1[(1 + 16 * (st >> 2) + 4 * gg + (st & 3)) * 64 + 16 * mt + jj] * g1;
-        }
-        for (int i = threadIdx.x; i < 2 * 16 * 64; i += kDfWaves * 64) {
-            const int l = i & 63, st = (i >> 6) & 15, ft = i >> 10, jj = l & 15, gg = l >> 4;
-            w0t[i] = a.dec_w0[(16 * (st >> 2) + 4 * gg + (st & 3)) * 32 + 16 * ft + jj] * g0;
-        }
-    }
+    if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
+    if constexpr (DEC16) build_grad16_lds(a, w1t, w0t, lane, wave, kDfWaves);
+    else build_grad_lds(a, w1t, w0t, threadIdx.x, kDfWaves * 64);
     __syncthreads();
     // a wave walks the tiles of ONE ray in sequence: ray generation (six divisions and a square root), the position -> pixel
     // arithmetic and the ray's dL/dfeat once per ray instead of once per tile (~100 of ~800 vector instructions of a tile)
@@ -853,61 +527,23 @@ raymarch_bwd_df_kernel(const RayParams p, float* __restrict__ df_out, const Rows
         DfSlots slots;
         if constexpr (SORTED) slots = load_df_slots(ro, (size_t)ray * S + s);      // lands while the tile runs its decoder
         float f[8];
-        {
-            PlaneTaps tq[3];
-            sample_taps(p, o3, d3, zq_cur, tq);
-            gather8(a, b, lane & 3, tq, f);
-            const int src = 4 * j + g;
-#pragma unroll
-            for (int cc = 0; cc < 8; ++cc) f[cc] = __shfl(f[cc], src);
-        }
+        gather8_mfma(p, b, o3, d3, zq_cur, lane, f);
         f32x4 hp[4], h[4], o[2];
         float sigma;
         if constexpr (DEC16) decoder_fwd16_lds<true>(wfwd, ln, f, hp, h, sigma, o);
         else decoder_fwd_lds<true>(wfwd, lane, f, hp, h, sigma, o);
         f32x4 dO[2];
-#pragma unroll
-        for (int ot = 0; ot < 2; ++ot) {
-            const float4 gf = gfeat[ot];
-            const float gv[4] = {gf.x, gf.y, gf.z, gf.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float sg = sigmoid_f(o[ot][r]);
-                dO[ot][r] = rec.y * 2.f * gv[r] * 1.002f * sg * (1.f - sg);
-            }
-        }
+        ray_colour_logit_grad(o, rec.y, gfeat, dO);
         f32x4 dH[4];
         f32x4 dF2[2];
         if constexpr (DEC16) decoder_bwd16_lds(wfwd, w1t, w0t, ln, dO, rec.z, hp, dH, dF2);
-#pragma unroll
-        for (int mt = 0; mt < (DEC16 ? 0 : 4); ++mt) {
-            const float* ws_ = wfwd + (48 + mt * 4) * 64 + lane;
-            dH[mt] = f32x4{ws_[0] * rec.z, ws_[64] * rec.z, ws_[128] * rec.z, ws_[192] * rec.z};
-#pragma unroll
-            for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float wA = w1t[(mt * 8 + ot * 4 + r) * 64 + lane];
-                    dH[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dO[ot][r], dH[mt], 0, 0, 0);
-                }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) dH[mt][r] *= sigmoid_f(hp[mt][r]);
-        }
+        else decoder_bwd_lds(wfwd, w1t, w0t, lane, dO, rec.z, hp, dH, dF2);
         // lane (j, g), register r -> feature channel 16ft + 4g + r of sample j: 16-byte stores, two per 128-byte sample line
-        float* dst = df_out + ((size_t)ray * S + s) * 32 + 4 * g;
+        if constexpr (!SORTED) {
+            float* dst = df_out + ((size_t)ray * S + s) * 32 + 4 * g;
 #pragma unroll
-        for (int ft = 0; ft < 2; ++ft) {
-            if constexpr (!DEC16) {
-                dF2[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float wA = w0t[(ft * 16 + mt * 4 + r) * 64 + lane];
-                        dF2[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dH[mt][r], dF2[ft], 0, 0, 0);
-                    }
-            }
-            if constexpr (!SORTED) *reinterpret_cast<float4*>(dst + 16 * ft) = make_float4(dF2[ft][0], dF2[ft][1], dF2[ft][2], dF2[ft][3]);
+            for (int ft = 0; ft < 2; ++ft)
+                *reinterpret_cast<float4*>(dst + 16 * ft) = make_float4(dF2[ft][0], dF2[ft][1], dF2[ft][2], dF2[ft][3]);
         }
         if constexpr (SORTED) store_df_sorted(ro, slots, g, dF2);                     // sort + gather form: raymarch_rows.hip
         }

@@ -11,15 +11,15 @@
 // The sample depths carry no gradient (stratified: uniforms and constants; importance: detached as in EG3D), so the camera
 // reaches the loss through the sample POSITIONS alone.  A pass of its own, not a flag on the dL/dF producers: it is the same
 // whichever pass-2 form ran, and the producers' instantiations stay what they are.
-#include "raymarch_common.h"
+#include "decoder_adjoint.h"
 
 namespace hfagp {
 
 constexpr int kCamWaves = 4;
 constexpr int kCamReduceThreads = 256;
 
-// (PlaneTapsD / plane_taps_d, the taps with what the positional derivative needs: raymarch_common.h, shared with
-// planes_query_bwd.hip)
+// (the decoder adjoint and the positional derivative of the gather: decoder_adjoint.h, shared with raymarch_bwd.hip,
+// planes_query_bwd.hip and raymarch_normals.hip)
 
 template <int S, bool DEC16>
 __global__ void __launch_bounds__(kCamWaves * 64, 2)
@@ -32,30 +32,9 @@ raymarch_bwd_camera_kernel(const RayParams p, float* __restrict__ ray_grad) {
     const int j = lane & 15, g = lane >> 4;
     const int R = a.res * a.res;
     constexpr int NT = S / 16;
-    if (wave == 0) {
-        DecoderRegs dec;
-        load_decoder(a, j, g, dec);
-        if constexpr (DEC16) {
-            Dec16Regs d16;
-            make_dec16(dec, a.planes_absmax, lane, d16);
-            store_dec16_lds(d16, wfwd, lane);
-        } else {
-            store_decoder_lds(dec, wfwd, lane);
-        }
-    }
-    if constexpr (DEC16) {
-        build_grad16_lds(a, w1t, w0t, lane, wave, kCamWaves);
-    } else {
-        const float g0 = a.decoder_lr_mul * 0.17677669529663687f, g1 = a.decoder_lr_mul * 0.125f;
-        for (int i = threadIdx.x; i < 4 * 8 * 64; i += kCamWaves * 64) {
-            const int l = i & 63, st = (i >> 6) & 7, mt = i >> 9, jj = l & 15, gg = l >> 4;
-            w1t[i] = a.dec_w1[(1 + 16 * (st >> 2) + 4 * gg + (st & 3)) * 64 + 16 * mt + jj] * g1;
-        }
-        for (int i = threadIdx.x; i < 2 * 16 * 64; i += kCamWaves * 64) {
-            const int l = i & 63, st = (i >> 6) & 15, ft = i >> 10, jj = l & 15, gg = l >> 4;
-            w0t[i] = a.dec_w0[(16 * (st >> 2) + 4 * gg + (st & 3)) * 32 + 16 * ft + jj] * g0;
-        }
-    }
+    if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
+    if constexpr (DEC16) build_grad16_lds(a, w1t, w0t, lane, wave, kCamWaves);
+    else build_grad_lds(a, w1t, w0t, threadIdx.x, kCamWaves * 64);
     __syncthreads();
     // d pixel / d grid coordinate (plane_pixel) times the mean over the planes
     const float sx = (float)a.W * 0.5f * 0.3333333333333333f, sy = (float)a.H * 0.5f * 0.3333333333333333f;
@@ -81,101 +60,21 @@ raymarch_bwd_camera_kernel(const RayParams p, float* __restrict__ ray_grad) {
             zq = p.rec[((size_t)ray * S + 16 * min(tt + 1, NT - 1) + (lane >> 2)) * 4];
             const float4 rec = *reinterpret_cast<const float4*>(p.rec + ((size_t)ray * S + s) * 4);   // depth, omega, dsigma
             float f[8];
-            {
-                PlaneTaps tq[3];
-                sample_taps(p, o3, d3, zq_cur, tq);
-                gather8(a, b, lane & 3, tq, f);
-                const int src = 4 * j + g;
-#pragma unroll
-                for (int cc = 0; cc < 8; ++cc) f[cc] = __shfl(f[cc], src);
-            }
+            gather8_mfma(p, b, o3, d3, zq_cur, lane, f);
             f32x4 hp[4], h[4], o[2];
             float sigma;
             if constexpr (DEC16) decoder_fwd16_lds<true>(wfwd, ln, f, hp, h, sigma, o);
             else decoder_fwd_lds<true>(wfwd, lane, f, hp, h, sigma, o);
             f32x4 dO[2];
-#pragma unroll
-            for (int ot = 0; ot < 2; ++ot) {
-                const float4 gf = gfeat[ot];
-                const float gv[4] = {gf.x, gf.y, gf.z, gf.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float sg = sigmoid_f(o[ot][r]);
-                    dO[ot][r] = rec.y * 2.f * gv[r] * 1.002f * sg * (1.f - sg);
-                }
-            }
+            ray_colour_logit_grad(o, rec.y, gfeat, dO);
             f32x4 dH[4];
             f32x4 dF2[2];
             if constexpr (DEC16) decoder_bwd16_lds(wfwd, w1t, w0t, ln, dO, rec.z, hp, dH, dF2);
-#pragma unroll
-            for (int mt = 0; mt < (DEC16 ? 0 : 4); ++mt) {
-                const float* ws_ = wfwd + (48 + mt * 4) * 64 + lane;
-                dH[mt] = f32x4{ws_[0] * rec.z, ws_[64] * rec.z, ws_[128] * rec.z, ws_[192] * rec.z};
-#pragma unroll
-                for (int ot = 0; ot < 2; ++ot)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float wA = w1t[(mt * 8 + ot * 4 + r) * 64 + lane];
-                        dH[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dO[ot][r], dH[mt], 0, 0, 0);
-                    }
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dH[mt][r] *= sigmoid_f(hp[mt][r]);
-            }
-            if constexpr (!DEC16) {
-#pragma unroll
-                for (int ft = 0; ft < 2; ++ft) {
-                    dF2[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float wA = w0t[(ft * 16 + mt * 4 + r) * 64 + lane];
-                            dF2[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dH[mt][r], dF2[ft], 0, 0, 0);
-                        }
-                }
-            }
-            // ---- positional derivative: lane (j, g) holds dL/dF of channels 16 ft + 4 g + r of sample j (depth rec.x) and forms
-            // its share of P_k = <dL/dF, texel_k> for the twelve taps (lines the gather above has just pulled in)
-            float q[3];
+            else decoder_bwd_lds(wfwd, w1t, w0t, lane, dO, rec.z, hp, dH, dF2);
+            // ---- positional derivative of the gather at the sample (depth rec.x): this lane's share
+            float q[3], dq[3];
             sample_point(p, o3, d3, rec.x, q);
-            float dq[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                float gx, gy;
-                plane_coords(a, q, pl, gx, gy);
-                PlaneTapsD t;
-                plane_taps_d(a, gx, gy, t);
-                const char* base = reinterpret_cast<const char*>(a.planes + ((size_t)(b * 3 + pl) * a.H * a.W) * 32);
-                float4 v0[4], v1[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const unsigned off = ((unsigned)t.idx[k] * 32u + 4u * g) * 4u;      // < 2^32: one plane
-                    v0[k] = *reinterpret_cast<const float4*>(base + off);
-                    v1[k] = *reinterpret_cast<const float4*>(base + off + 64);
-                }
-                float P[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float acc = dF2[0][0] * v0[k].x;
-                    acc = fmaf(dF2[0][1], v0[k].y, acc);
-                    acc = fmaf(dF2[0][2], v0[k].z, acc);
-                    acc = fmaf(dF2[0][3], v0[k].w, acc);
-                    acc = fmaf(dF2[1][0], v1[k].x, acc);
-                    acc = fmaf(dF2[1][1], v1[k].y, acc);
-                    acc = fmaf(dF2[1][2], v1[k].z, acc);
-                    acc = fmaf(dF2[1][3], v1[k].w, acc);
-                    P[k] = t.ok[k] ? acc : 0.f;
-                }
-                const float dix = ((P[1] - P[0]) * (1.f - t.fy) + (P[3] - P[2]) * t.fy) * sx;
-                const float diy = ((P[2] - P[0]) * (1.f - t.fx) + (P[3] - P[1]) * t.fx) * sy;
-                // planes (x,y), (x,z), (z,x) [plane_axes 0] or (z,y): plane_coords
-                if (pl == 0) { dq[0] += dix; dq[1] += diy; }
-                else if (pl == 1) { dq[0] += dix; dq[2] += diy; }
-                else {
-                    dq[2] += dix;
-                    if (a.plane_axes == 0) dq[0] += diy; else dq[1] += diy;
-                }
-            }
+            gather_position_grad(a, b, g, q, dF2, sx, sy, dq);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 acc_o[k] += dq[k];

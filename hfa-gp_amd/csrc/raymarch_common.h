@@ -850,82 +850,6 @@ __device__ __forceinline__ void decoder_fwd16_lds(const float* imgf, int lane, c
     }
 }
 
-// Gradient A operands (split bf16: a gradient needs fp32's exponent range; ~2^-16 per product is ample for a gradient):
-//   g1img rows mt*4+q (hi), 16+mt*4+q (lo):        A[16mt + j][k = (g, c)] = W1[1 + 16(c>>2) + 4g + (c&3)][16mt + j] * g1
-//   g0img rows (ft*2+ks)*4+q (hi), 16+... (lo):    A[16ft + j][k = (g, c)] = W0[16(2ks + (c>>2)) + 4g + (c&3)][16ft + j] * g0
-// built by whichever waves the block has (`wave` of `nwaves`).  COLOUR = false: g0img alone (a caller without colour gradients:
-// raymarch_normals.hip); g1img is not touched.
-template <bool COLOUR = true>
-__device__ __forceinline__ void build_grad16_lds(const HfagpRaymarchArgs& a, float* g1img, float* g0img, int lane, int wave,
-                                                 int nwaves) {
-    const int j = lane & 15, g = lane >> 4;
-    const float g0 = a.decoder_lr_mul * 0.17677669529663687f, g1 = a.decoder_lr_mul * 0.125f;
-    unsigned* i1 = reinterpret_cast<unsigned*>(g1img);
-    unsigned* i0 = reinterpret_cast<unsigned*>(g0img);
-    for (int t = (COLOUR ? 0 : 4) + wave; t < 8; t += nwaves) {
-        float v[8];
-        u32x4r hi, lo;
-        if (t < 4) {
-            const int mt = t;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) v[c] = a.dec_w1[(1 + 16 * (c >> 2) + 4 * g + (c & 3)) * 64 + 16 * mt + j] * g1;
-            split8_bf16(v, hi, lo);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { i1[(mt * 4 + q) * 64 + lane] = hi[q]; i1[(16 + mt * 4 + q) * 64 + lane] = lo[q]; }
-        } else {
-            const int ft = (t - 4) >> 1, ks = (t - 4) & 1;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) v[c] = a.dec_w0[(16 * (2 * ks + (c >> 2)) + 4 * g + (c & 3)) * 32 + 16 * ft + j] * g0;
-            split8_bf16(v, hi, lo);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                i0[((ft * 2 + ks) * 4 + q) * 64 + lane] = hi[q];
-                i0[(16 + (ft * 2 + ks) * 4 + q) * 64 + lane] = lo[q];
-            }
-        }
-    }
-}
-
-// decoder backward on the 16-bit pipe: dH (pre-activation gradient, C layout of the hidden tiles) and dF (C layout of the
-// two feature tiles) from dO (colour-logit gradients), d sigma, the saved pre-activations.  COLOUR = false: dO is all zeros
-// (the adjoint of sigma alone); dO and g1img are not read and the second-layer colour product is not formed.
-template <bool COLOUR = true>
-__device__ __forceinline__ void decoder_bwd16_lds(const float* dimg, const float* g1img, const float* g0img, int lane,
-                                                  const f32x4 dO[2], float dsig, const f32x4 hp[4], f32x4 dH[4], f32x4 dF[2]) {
-    u32x4r oh = {}, ol = {};
-    if constexpr (COLOUR) {
-        float v[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = dO[c >> 2][c & 3];
-        split8_bf16(v, oh, ol);
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt) {
-        const float* ws_ = dimg + (kDec16Wsig + mt * 4) * 64 + lane;
-        dH[mt] = f32x4{ws_[0] * dsig, ws_[64] * dsig, ws_[128] * dsig, ws_[192] * dsig};
-        if constexpr (COLOUR)
-            dH[mt] = mfma3_bf16(lds_row4(g1img, mt * 4, lane), lds_row4(g1img, 16 + mt * 4, lane), oh, ol, dH[mt]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dH[mt][r] *= sigmoid_f(hp[mt][r]);      // softplus' = sigmoid
-    }
-    u32x4r dh[2], dl[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-        float v[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = dH[2 * ks + (c >> 2)][c & 3];
-        split8_bf16(v, dh[ks], dl[ks]);
-    }
-#pragma unroll
-    for (int ft = 0; ft < 2; ++ft) {
-        dF[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-            dF[ft] = mfma3_bf16(lds_row4(g0img, (ft * 2 + ks) * 4, lane), lds_row4(g0img, 16 + (ft * 2 + ks) * 4, lane),
-                                dh[ks], dl[ks], dF[ft]);
-    }
-}
-
 // The same decoder with the A operands read from an LDS image [105][64] of DecoderRegs (lane-linear, so every
 // ds_read_b32 is conflict-free): used where the registers are needed for the backward products.
 constexpr int kDecLdsRows = 109;          // (109: the 16-bit image, kDec16LdsRows, shares the buffer)

@@ -16,7 +16,7 @@
 //                             positional derivative of the bilinear gather (plane_taps_d) -> the four channel groups of a sample
 //                             summed with two shuffles -> n_s -> omega_s n_s on the lanes g == 0.  One writer per ray, plain
 //                             stores, fixed butterfly order: two calls give the same bits.
-#include "raymarch_common.h"
+#include "decoder_adjoint.h"
 
 namespace hfagp {
 
@@ -33,26 +33,9 @@ raymarch_normals_kernel(const RayParams p, float* __restrict__ normal) {
     const int j = lane & 15, g = lane >> 4;
     const int R = a.res * a.res;
     constexpr int NT = S / 16;
-    if (wave == 0) {
-        DecoderRegs dec;
-        load_decoder(a, j, g, dec);
-        if constexpr (DEC16) {
-            Dec16Regs d16;
-            make_dec16(dec, a.planes_absmax, lane, d16);
-            store_dec16_lds(d16, wfwd, lane);
-        } else {
-            store_decoder_lds(dec, wfwd, lane);
-        }
-    }
-    if constexpr (DEC16) {
-        build_grad16_lds<false>(a, nullptr, w0t, lane, wave, kNrmWaves);
-    } else {
-        const float g0 = a.decoder_lr_mul * 0.17677669529663687f;
-        for (int i = threadIdx.x; i < 2 * 16 * 64; i += kNrmWaves * 64) {
-            const int l = i & 63, st = (i >> 6) & 15, ft = i >> 10, jj = l & 15, gg = l >> 4;
-            w0t[i] = a.dec_w0[(16 * (st >> 2) + 4 * gg + (st & 3)) * 32 + 16 * ft + jj] * g0;
-        }
-    }
+    if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
+    if constexpr (DEC16) build_grad16_lds<false>(a, nullptr, w0t, lane, wave, kNrmWaves);
+    else build_grad_lds<false>(a, nullptr, w0t, threadIdx.x, kNrmWaves * 64);
     __syncthreads();
     float* ts = ray_ts[wave];
     float* ss = ray_ss[wave];
@@ -118,14 +101,7 @@ raymarch_normals_kernel(const RayParams p, float* __restrict__ normal) {
             asm volatile("" : "+v"(ln));       // the weight images are read per tile, not hoisted into registers
             const float tz = ts[s], om_s = om[s];
             float f[8];
-            {
-                PlaneTaps tq[3];
-                sample_taps(p, o3, d3, ts[16 * tt + (lane >> 2)], tq);
-                gather8(a, b, lane & 3, tq, f);
-                const int src = 4 * j + g;
-#pragma unroll
-                for (int cc = 0; cc < 8; ++cc) f[cc] = __shfl(f[cc], src);
-            }
+            gather8_mfma(p, b, o3, d3, ts[16 * tt + (lane >> 2)], lane, f);
             // decoder forward: only the hidden pre-activations are used (sigma and the colour logits fall away)
             f32x4 hp[4], h[4], o[2];
             float sigma;
@@ -134,67 +110,12 @@ raymarch_normals_kernel(const RayParams p, float* __restrict__ normal) {
             // decoder adjoint of d sigma = 1, no colour gradient: dH = wsig * softplus'(hp), dF = W0^T dH
             f32x4 dH[4];
             f32x4 dF2[2];
-            if constexpr (DEC16) {
-                decoder_bwd16_lds<false>(wfwd, nullptr, w0t, ln, o, 1.f, hp, dH, dF2);
-            } else {
-#pragma unroll
-                for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) dH[mt][r] = wfwd[(kDecWsig + mt * 4 + r) * 64 + ln] * sigmoid_f(hp[mt][r]);
-#pragma unroll
-                for (int ft = 0; ft < 2; ++ft) {
-                    dF2[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float wA = w0t[(ft * 16 + mt * 4 + r) * 64 + ln];
-                            dF2[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(wA, dH[mt][r], dF2[ft], 0, 0, 0);
-                        }
-                }
-            }
-            // ---- positional derivative (as raymarch_bwd_camera_kernel): lane (j, g) holds d sigma / dF of channels 16 ft + 4 g + r
-            // of sample j and forms its share of P_k = <d sigma / dF, texel_k> for the twelve taps
-            float q[3];
+            if constexpr (DEC16) decoder_bwd16_lds<false>(wfwd, nullptr, w0t, ln, o, 1.f, hp, dH, dF2);
+            else decoder_bwd_lds<false>(wfwd, nullptr, w0t, ln, o, 1.f, hp, dH, dF2);
+            // ---- positional derivative of the gather (as raymarch_bwd_camera_kernel): this lane's share of d sigma / dq
+            float q[3], dq[3];
             sample_point(p, o3, d3, tz, q);
-            float dq[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-                float gx, gy;
-                plane_coords(a, q, pl, gx, gy);
-                PlaneTapsD t;
-                plane_taps_d(a, gx, gy, t);
-                const char* base = reinterpret_cast<const char*>(a.planes + ((size_t)(b * 3 + pl) * a.H * a.W) * 32);
-                float4 v0[4], v1[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const unsigned off = ((unsigned)t.idx[k] * 32u + 4u * g) * 4u;      // < 2^32: one plane
-                    v0[k] = *reinterpret_cast<const float4*>(base + off);
-                    v1[k] = *reinterpret_cast<const float4*>(base + off + 64);
-                }
-                float P[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    float pa = dF2[0][0] * v0[k].x;
-                    pa = fmaf(dF2[0][1], v0[k].y, pa);
-                    pa = fmaf(dF2[0][2], v0[k].z, pa);
-                    pa = fmaf(dF2[0][3], v0[k].w, pa);
-                    pa = fmaf(dF2[1][0], v1[k].x, pa);
-                    pa = fmaf(dF2[1][1], v1[k].y, pa);
-                    pa = fmaf(dF2[1][2], v1[k].z, pa);
-                    pa = fmaf(dF2[1][3], v1[k].w, pa);
-                    P[k] = t.ok[k] ? pa : 0.f;
-                }
-                const float dix = ((P[1] - P[0]) * (1.f - t.fy) + (P[3] - P[2]) * t.fy) * sx;
-                const float diy = ((P[2] - P[0]) * (1.f - t.fx) + (P[3] - P[1]) * t.fx) * sy;
-                // planes (x,y), (x,z), (z,x) [plane_axes 0] or (z,y): plane_coords
-                if (pl == 0) { dq[0] += dix; dq[1] += diy; }
-                else if (pl == 1) { dq[0] += dix; dq[2] += diy; }
-                else {
-                    dq[2] += dix;
-                    if (a.plane_axes == 0) dq[0] += diy; else dq[1] += diy;
-                }
-            }
+            gather_position_grad(a, b, g, q, dF2, sx, sy, dq);
             // the sample's four channel groups -> g = d sigma / d x in world units (q = coord_scale * x), on all four lanes
             float gw[3];
 #pragma unroll

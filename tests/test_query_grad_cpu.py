@@ -155,6 +155,29 @@ def test_unit_is_appended_to_the_build():
         assert '#include "planes_query_common.h"' in src and not re.search(r"float\s+scale_rn\s*\(", src), unit
 
 
+def test_decoder_adjoint_has_a_single_source():
+    """The pieces of the decoder adjoint that the ray-march backward, camera, point-query and normals kernels share are each
+    defined once, in decoder_adjoint.h; no unit carries its own fp32 adjoint loop or its own operand-image struct."""
+    pieces = ("decoder_images_lds", "build_grad_lds", "build_grad16_lds", "gather8_mfma", "colour_logit_grad", "decoder_bwd_lds",
+              "decoder_bwd16_lds", "dec_grad_zero", "dec_grad_tile", "dec_grad_flush", "publish_taps", "scatter_tile_runs",
+              "gather_position_grad")
+    structs = ("GradLds", "DecGrads", "DecGradAcc", "TileLds")
+    files = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hip")))
+    text = {f: open(os.path.join(CSRC, f)).read() for f in files}
+    for name in pieces:          # a definition: `void name(` at the start of a declarator (calls have no return type before them)
+        where = [f for f in files for _ in re.finditer(r"\bvoid\s+%s\s*\(" % name, text[f])]
+        assert where == ["decoder_adjoint.h"], (name, where)
+    for name in structs:
+        where = [f for f in files for _ in re.finditer(r"\bstruct\s+%s\b\s*\{" % name, text[f])]
+        assert where == ["decoder_adjoint.h"], (name, where)
+    for f in files:
+        if f.endswith(".hip"):
+            assert not re.search(r"\bstruct\s+\w*GradLds\b", text[f]), f
+            assert "mfma_f32_16x16x4f32(wA" not in text[f], f
+    for unit in ("raymarch_bwd", "raymarch_camera", "planes_query_bwd", "raymarch_normals"):
+        assert '#include "decoder_adjoint.h"' in text[unit + ".hip"], unit
+
+
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
 def test_every_instance_compiles_without_scratch_spills_or_packed_fp32(tmp_path):
     flags, _ = _flags_and_units()
