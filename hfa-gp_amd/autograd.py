@@ -441,8 +441,7 @@ class SynthesisFn(torch.autograd.Function):
                 geom.update(g_depth=g_depth.float().reshape(b, res * res).contiguous(), depth_range=tape["depth_range"])
             if g_mask is not None:
                 geom.update(g_wsum=g_mask.float().reshape(b, res * res).contiguous())
-        net = gen.decoder.net
-        dec_prm = (net["0"].weight, net["0"].bias, net["2"].weight, net["2"].bias)
+        dec_prm = gen.decoder_params()
         # (the kernel's ~9 M end-of-kernel atomics landing in the .grad slices themselves — `dec_out` — instead of four fresh zeroed
         # tensors was measured: the pass takes 1.17 - 1.20 ms instead of 0.98 - 0.99, and still does with the atomics cut to one set
         # per workgroup (an LDS reduction over its eight waves: no change either way) — it is WHERE they land, not how many.
@@ -546,8 +545,7 @@ class SampleMixedFn(torch.autograd.Function):
         b, dev = planes.shape[0], planes.device
         d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
         bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
-        net = gen.decoder.net
-        dec_prm = (net["0"].weight, net["0"].bias, net["2"].weight, net["2"].bias)
+        dec_prm = gen.decoder_params()
         dec = tuple(torch.zeros_like(p) for p in dec_prm) if ctx.pg else None
         d_planes, d_coords = _query_backward(gen, planes, ctx.co, ctx.pam, g_sigma, g_rgb, None, ctx.needs_input_grad[1], dec)
         if ctx.pg:

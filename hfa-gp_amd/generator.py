@@ -639,17 +639,20 @@ class TriPlaneGenerator(nn.Module):
         vals = am.max(dim=1).values.tolist()
         return {n: v for n, v in zip(names, vals) if not n.startswith("b4.conv0")}
 
+    def decoder_params(self):
+        """The decoder's parameters in the order of the ops' dec_w0, dec_b0, dec_w1, dec_b1."""
+        net = self.decoder.net
+        return net["0"].weight, net["0"].bias, net["2"].weight, net["2"].bias
+
     def _render_args(self, c: torch.Tensor):
         cfg = self.cfg
-        net = self.decoder.net
         hit = getattr(self, "_cam_cache", None)       # the backward pass of a step asks again with the forward's tensor
         if hit is None or hit[0] is not c or hit[1] != c._version:
             hit = self._cam_cache = (c, c._version, c[:, :16].contiguous(), c[:, 16:25].contiguous())
-        return dict(cam2world=hit[2], intrinsics=hit[3],
-                    dec_w0=net["0"].weight, dec_b0=net["0"].bias, dec_w1=net["2"].weight, dec_b1=net["2"].bias,
+        return dict(zip(ops._DEC, self.decoder_params()), cam2world=hit[2], intrinsics=hit[3],
                     res=cfg.neural_rendering_resolution, ray_start=cfg.ray_start, ray_end=cfg.ray_end,
                     box_warp=cfg.box_warp, decoder_lr_mul=cfg.decoder_lr_mul,
-                    plane_axes=0 if cfg.plane_axes == "eg3d_original" else 1, white_back=cfg.white_back,
+                    plane_axes=ops._plane_axes_id(cfg.plane_axes), white_back=cfg.white_back,
                     decoder_precision=cfg.decoder_precision)
 
     def _uniforms(self, b: int, dev, u_strat, u_imp):
@@ -930,9 +933,7 @@ class TriPlaneGenerator(nn.Module):
 
     def _query_kwargs(self) -> dict:
         cfg = self.cfg
-        net = self.decoder.net
-        return dict(dec_w0=net["0"].weight, dec_b0=net["0"].bias, dec_w1=net["2"].weight, dec_b1=net["2"].bias,
-                    box_warp=cfg.box_warp, plane_axes=0 if cfg.plane_axes == "eg3d_original" else 1,
+        return dict(zip(ops._DEC, self.decoder_params()), box_warp=cfg.box_warp, plane_axes=ops._plane_axes_id(cfg.plane_axes),
                     decoder_lr_mul=cfg.decoder_lr_mul, decoder_precision=cfg.decoder_precision)
 
     def sample_mixed(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], ws: torch.Tensor,

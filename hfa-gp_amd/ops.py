@@ -619,6 +619,79 @@ def torgb_small(x: torch.Tensor, weight: torch.Tensor, styles: torch.Tensor, bia
 
 
 # ----------------------------------------------------------------------------- renderer
+# The library sees pointers and integers, never a tensor's extent: these builders are the only guard between a mis-shaped tensor and
+# a kernel that reads past it.  Every renderer entry point fills its structures through them and raises before anything is launched.
+_DEC = ("dec_w0", "dec_b0", "dec_w1", "dec_b1")
+
+
+def _planes_dims(who: str, planes: torch.Tensor):
+    """(B, H, W) of channels-last tri-planes."""
+    _chk(planes, f"{who}: planes")
+    if planes.dim() != 5 or planes.shape[1] != 3 or planes.shape[4] != 32:
+        raise RuntimeError(f"{who}: planes must be [B, 3, H, W, 32]")
+    return planes.shape[0], planes.shape[2], planes.shape[3]
+
+
+def _plane_axes_id(plane_axes) -> int:
+    """The library's code of a plane-axes convention, given as that code or as the config's name."""
+    if isinstance(plane_axes, str):
+        return 0 if plane_axes == "eg3d_original" else 1
+    return plane_axes
+
+
+def _fill_decoder(who: str, a, planes: torch.Tensor, params, decoder_precision: str, planes_absmax) -> None:
+    """The decoder's four parameter pointers and its |planes| bound, into a RaymarchArgs / PlanesQueryArgs / PlanesQueryBwdArgs.  A
+    bound that `_decoder_bound` returned earlier passes through unchanged (`raymarch_bwd`: one for all frame chunks)."""
+    for name, t in zip(_DEC, params):
+        setattr(a, name, _ptr(_chk(t, f"{who}: {name}")))
+    # (no frames: nothing is launched that could read a bound, and there is nothing to reduce over)
+    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax)) if planes.numel() else None
+
+
+def _ray_args(who: str, f, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, res: int, ray_start: float,
+              ray_end: float, box_warp: float, decoder_lr_mul: float, plane_axes, white_back: bool, decoder_precision: str, planes_absmax,
+              state):
+    """Fills the RaymarchArgs ``f`` (a fresh one, or the `fwd` member of a RaymarchBwdArgs) with everything but the forward's output
+    pointers, and returns (B, H, W, R, Sc, Sf).  Owns the checks of planes, the uniforms' element counts, `state` and of device,
+    dtype and contiguity of every input.  The parameters after ``f`` are `raymarch`'s, in its order."""
+    b, h, w = _planes_dims(who, planes)
+    r = res * res
+    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    if u_strat.numel() != b * r * sc or u_imp.numel() != b * r * sf:
+        raise RuntimeError(f"{who}: u_strat / u_imp have the wrong number of elements")
+    if state is not None and _chk(state, f"{who}: state").shape != (b, r, (sc + sf) * 35):
+        raise RuntimeError(f"{who}: state must be [B, R, {(sc + sf) * 35}] (raymarch_state), got {tuple(state.shape)}")
+    for name, t in (("cam2world", cam2world), ("intrinsics", intrinsics), ("u_strat", u_strat), ("u_imp", u_imp)):
+        setattr(f, name, _ptr(_chk(t, f"{who}: {name}")))
+    f.planes, f.state = _ptr(planes), _ptr(state)
+    _fill_decoder(who, f, planes, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_precision, planes_absmax)
+    f.B, f.H, f.W, f.res, f.Sc, f.Sf = b, h, w, res, sc, sf
+    f.plane_axes, f.white_back = _plane_axes_id(plane_axes), int(white_back)
+    f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
+    return b, h, w, r, sc, sf
+
+
+def _dec_grad_out(who: str, a, params, decoder_grads: bool, dec_out):
+    """The four tensors the decoder-parameter gradients are ACCUMULATED into, their pointers set in the RaymarchBwdArgs /
+    PlanesQueryBwdArgs ``a``: ``dec_out`` (the parameters' .grad slices, say) or fresh zeros; None without ``decoder_grads``."""
+    if not decoder_grads:
+        return None
+    dec = tuple(dec_out) if dec_out is not None else tuple(torch.zeros_like(t) for t in params)
+    if len(dec) != 4 or any(t.shape != like.shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda
+                            for t, like in zip(dec, params)):
+        raise RuntimeError(f"{who}: dec_out must be four contiguous fp32 device tensors shaped like the decoder parameters")
+    a.d_dec_w0, a.d_dec_b0, a.d_dec_w1, a.d_dec_b1 = (_ptr(t) for t in dec)
+    return dec
+
+
+def _query_points(who: str, coords: torch.Tensor, b: int) -> int:
+    """M of explicit query points [1 or B, M, 3]."""
+    _chk(coords, f"{who}: coords")
+    if coords.dim() != 3 or coords.shape[2] != 3 or coords.shape[0] not in (1, b):
+        raise RuntimeError(f"{who}: coords must be [1 or B={b}, M, 3], got {tuple(coords.shape)}")
+    return coords.shape[1]
+
+
 def raymarch(planes: torch.Tensor, cam2world: torch.Tensor, intrinsics: torch.Tensor, u_strat: torch.Tensor,
              u_imp: torch.Tensor, dec_w0: torch.Tensor, dec_b0: torch.Tensor, dec_w1: torch.Tensor,
              dec_b1: torch.Tensor, res: int, ray_start: float, ray_end: float, box_warp: float,
@@ -631,33 +704,15 @@ def raymarch(planes: torch.Tensor, cam2world: torch.Tensor, intrinsics: torch.Te
     decoder_precision 'f16x3': the decoder MLP on the 16-bit matrix pipe with split fp16 operands (fp32-class); it needs
     a bound on |planes| — `planes_absmax` (64 slots as published by `skip_upsample_add(out_absmax=...)`), computed here
     with one reduction over the planes when the caller has none.  'fp32': the exact fp32 matrix instructions."""
-    _chk(planes, "planes")
-    b, three, h, w, ch = planes.shape
-    if three != 3 or ch != 32:
-        raise RuntimeError("raymarch: planes must be [B, 3, H, W, 32]")
-    r = res * res
-    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
-    if u_strat.numel() != b * r * sc or u_imp.numel() != b * r * sf:
-        raise RuntimeError("raymarch: u_strat / u_imp have the wrong number of elements")
+    a = L.RaymarchArgs()
+    b, _, _, r, _, _ = _ray_args("raymarch", a, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, res, ray_start,
+                                 ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision, planes_absmax, state)
     dev = planes.device
     feat = torch.empty(b, r, 32, device=dev, dtype=torch.float32)
     depth = torch.empty(b, r, device=dev, dtype=torch.float32)
     wsum = torch.empty(b, r, device=dev, dtype=torch.float32)
     tmm = torch.empty(b, r, 2, device=dev, dtype=torch.float32)
-    a = L.RaymarchArgs()
-    a.planes, a.cam2world, a.intrinsics = _ptr(planes), _ptr(_chk(cam2world, "cam2world")), _ptr(_chk(intrinsics, "intrinsics"))
-    a.u_strat, a.u_imp = _ptr(_chk(u_strat, "u_strat")), _ptr(_chk(u_imp, "u_imp"))
-    a.dec_w0, a.dec_b0 = _ptr(_chk(dec_w0, "dec_w0")), _ptr(_chk(dec_b0, "dec_b0"))
-    a.dec_w1, a.dec_b1 = _ptr(_chk(dec_w1, "dec_w1")), _ptr(_chk(dec_b1, "dec_b1"))
     a.feat, a.depth, a.wsum, a.tminmax = _ptr(feat), _ptr(depth), _ptr(wsum), _ptr(tmm)
-    a.B, a.H, a.W, a.res, a.Sc, a.Sf = b, h, w, res, sc, sf
-    a.plane_axes, a.white_back = plane_axes, int(white_back)
-    a.ray_start, a.ray_end, a.box_warp, a.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
-    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
-    if state is not None:
-        if state.shape != (b, r, (sc + sf) * 35):
-            raise RuntimeError(f"raymarch: state must be [B, R, {(sc + sf) * 35}] (raymarch_state), got {tuple(state.shape)}")
-        a.state = _ptr(_chk(state, "state"))
     L.check(L.lib().hfagp_raymarch_fwd(C.byref(a), _stream()), "raymarch_fwd")
     return feat, depth, wsum, tmm
 
@@ -671,29 +726,14 @@ def raymarch_normals(planes: torch.Tensor, state: torch.Tensor, *, cam2world: to
     N = Σ_s ω_s n_s over the Sc + Sf depth-sorted samples, n = −g·rsqrt(g·g + 1e-12) with g = ∇ₓσ the WORLD-space gradient of the
     raw decoder density (before softplus(σ − 1)), ω the colour weights of the forward.  ‖N‖ ≤ wsum; not normalised; `white_back`
     does not enter.  Forward only: the result carries no gradient.  No atomics: two calls return the same bits."""
-    _chk(planes, "planes")
-    b, three, h, w, ch = planes.shape
-    if three != 3 or ch != 32:
-        raise RuntimeError("raymarch_normals: planes must be [B, 3, H, W, 32]")
-    r = res * res
-    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
-    if u_strat.numel() != b * r * sc or u_imp.numel() != b * r * sf:
-        raise RuntimeError("raymarch_normals: u_strat / u_imp have the wrong number of elements")
-    if _chk(state, "state").shape != (b, r, (sc + sf) * 35):
-        raise RuntimeError(f"raymarch_normals: state must be [B, R, {(sc + sf) * 35}] (raymarch_state), got {tuple(state.shape)}")
+    if state is None:
+        raise RuntimeError("raymarch_normals: state must be the `raymarch_state` buffer the forward call filled, got None")
+    a = L.RaymarchArgs()
+    b, _, _, r, _, _ = _ray_args("raymarch_normals", a, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, res,
+                                 ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision, planes_absmax, state)
     normal = torch.empty(b, r, 3, device=planes.device, dtype=torch.float32)
     if b == 0:
         return normal
-    a = L.RaymarchArgs()
-    a.planes, a.cam2world, a.intrinsics = _ptr(planes), _ptr(_chk(cam2world, "cam2world")), _ptr(_chk(intrinsics, "intrinsics"))
-    a.u_strat, a.u_imp = _ptr(_chk(u_strat, "u_strat")), _ptr(_chk(u_imp, "u_imp"))
-    a.dec_w0, a.dec_b0 = _ptr(_chk(dec_w0, "dec_w0")), _ptr(_chk(dec_b0, "dec_b0"))
-    a.dec_w1, a.dec_b1 = _ptr(_chk(dec_w1, "dec_w1")), _ptr(_chk(dec_b1, "dec_b1"))
-    a.B, a.H, a.W, a.res, a.Sc, a.Sf = b, h, w, res, sc, sf
-    a.plane_axes, a.white_back = plane_axes, int(white_back)
-    a.ray_start, a.ray_end, a.box_warp, a.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
-    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
-    a.state = _ptr(state)
     L.check(L.lib().hfagp_raymarch_normals(C.byref(a), _ptr(normal), _stream()), "raymarch_normals")
     return normal
 
@@ -713,23 +753,15 @@ def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *,
         (ix - x_begin, iy, iz), rgb [B,x_count,N,N,32].  ``out`` (grid, sigma only): a [B,x_count,N,N] tensor to write into,
         contiguous inside each identity (a slab view of a whole [B,N,N,N] volume).
     Decoder arithmetic as `raymarch`: 'f16x3' (bound on |planes| from ``planes_absmax`` or one reduction here) or 'fp32'."""
-    _chk(planes, "planes")
-    if planes.dim() != 5 or planes.shape[1] != 3 or planes.shape[4] != 32:
-        raise RuntimeError("planes_query: planes must be [B, 3, H, W, 32]")
-    b, _, h, w, _ = planes.shape
+    b, h, w = _planes_dims("planes_query", planes)
     dev = planes.device
-    if isinstance(plane_axes, str):
-        plane_axes = 0 if plane_axes == "eg3d_original" else 1
     a = L.PlanesQueryArgs()
     if coords is not None:
         if grid is not None:
             raise ValueError("planes_query: pass coords or grid, not both")
-        _chk(coords, "coords")
-        if coords.dim() != 3 or coords.shape[2] != 3 or coords.shape[0] not in (1, b):
-            raise RuntimeError(f"planes_query: coords must be [1 or B={b}, M, 3], got {tuple(coords.shape)}")
+        m = _query_points("planes_query", coords, b)
         if out is not None:
             raise ValueError("planes_query: out= is for grid mode")
-        m = coords.shape[1]
         sigma = torch.empty(b, m, 1, device=dev, dtype=torch.float32)
         rgb = torch.empty(b, m, 32, device=dev, dtype=torch.float32) if want_rgb else None
         if b == 0 or m == 0:
@@ -755,12 +787,9 @@ def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *,
             return sigma, rgb
         a.N, a.x_begin, a.x_count, a.cube_length = n, x0, xc, cube
         a.out_stride = sigma.stride(0)
-    a.planes = _ptr(planes)
-    a.dec_w0, a.dec_b0 = _ptr(_chk(dec_w0, "dec_w0")), _ptr(_chk(dec_b0, "dec_b0"))
-    a.dec_w1, a.dec_b1 = _ptr(_chk(dec_w1, "dec_w1")), _ptr(_chk(dec_b1, "dec_b1"))
-    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
-    a.sigma, a.rgb = _ptr(sigma), _ptr(rgb)
-    a.B, a.H, a.W, a.plane_axes = b, h, w, plane_axes
+    _fill_decoder("planes_query", a, planes, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_precision, planes_absmax)
+    a.planes, a.sigma, a.rgb = _ptr(planes), _ptr(sigma), _ptr(rgb)
+    a.B, a.H, a.W, a.plane_axes = b, h, w, _plane_axes_id(plane_axes)
     a.box_warp, a.decoder_lr_mul = box_warp, decoder_lr_mul
     L.check(L.lib().hfagp_planes_query(C.byref(a), _stream()), "planes_query")
     return sigma, rgb
@@ -782,19 +811,11 @@ def planes_query_bwd(planes: torch.Tensor, coords: torch.Tensor, g_sigma: Option
         when given, else into fresh zeros; ``dec`` is None without them.
     The other keywords are the forward's; pass the ``planes_absmax`` the forward call got, so that the recomputed decoder is
     the one that ran."""
-    _chk(planes, "planes")
-    if planes.dim() != 5 or planes.shape[1] != 3 or planes.shape[4] != 32:
-        raise RuntimeError("planes_query_bwd: planes must be [B, 3, H, W, 32]")
-    b, _, h, w, _ = planes.shape
+    b, h, w = _planes_dims("planes_query_bwd", planes)
     dev = planes.device
-    if isinstance(plane_axes, str):
-        plane_axes = 0 if plane_axes == "eg3d_original" else 1
     if coords is None:
         raise ValueError("planes_query_bwd: explicit coords only (grid mode has no backward)")
-    _chk(coords, "coords")
-    if coords.dim() != 3 or coords.shape[2] != 3 or coords.shape[0] not in (1, b):
-        raise RuntimeError(f"planes_query_bwd: coords must be [1 or B={b}, M, 3], got {tuple(coords.shape)}")
-    m = coords.shape[1]
+    m = _query_points("planes_query_bwd", coords, b)
     if g_sigma is None and g_rgb is None:
         raise ValueError("planes_query_bwd: pass g_sigma, g_rgb or both")
     if g_sigma is not None and (_chk(g_sigma, "g_sigma").numel() != b * m or g_sigma.shape[:2] != (b, m)):
@@ -810,24 +831,16 @@ def planes_query_bwd(planes: torch.Tensor, coords: torch.Tensor, g_sigma: Option
     elif _chk(d_planes, "d_planes").shape != planes.shape:
         raise RuntimeError(f"planes_query_bwd: d_planes must be shaped like planes {tuple(planes.shape)}, got {tuple(d_planes.shape)}")
     d_coords = torch.empty(b, m, 3, device=dev, dtype=torch.float32) if coords_grad else None     # (every point has one writer)
-    dec = None
-    if decoder_grads:
-        dec = tuple(dec_out) if dec_out is not None else tuple(torch.zeros_like(t) for t in (dec_w0, dec_b0, dec_w1, dec_b1))
-        for t, like in zip(dec, (dec_w0, dec_b0, dec_w1, dec_b1)):
-            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
-                raise RuntimeError("planes_query_bwd: dec_out must be four contiguous fp32 device tensors shaped like the decoder parameters")
+    a = L.PlanesQueryBwdArgs()
+    params = (dec_w0, dec_b0, dec_w1, dec_b1)
+    dec = _dec_grad_out("planes_query_bwd", a, params, decoder_grads, dec_out)
     if b == 0 or m == 0:
         return d_planes, d_coords, dec
-    a = L.PlanesQueryBwdArgs()
+    _fill_decoder("planes_query_bwd", a, planes, params, decoder_precision, planes_absmax)
     a.planes, a.coords, a.Bc, a.M = _ptr(planes), _ptr(coords), coords.shape[0], m
-    a.dec_w0, a.dec_b0 = _ptr(_chk(dec_w0, "dec_w0")), _ptr(_chk(dec_b0, "dec_b0"))
-    a.dec_w1, a.dec_b1 = _ptr(_chk(dec_w1, "dec_w1")), _ptr(_chk(dec_b1, "dec_b1"))
-    a.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
     a.g_sigma, a.g_rgb = _ptr(g_sigma), _ptr(g_rgb)
     a.d_planes, a.d_coords = _ptr(d_planes), _ptr(d_coords)
-    if dec is not None:
-        a.d_dec_w0, a.d_dec_b0, a.d_dec_w1, a.d_dec_b1 = (_ptr(t) for t in dec)
-    a.B, a.H, a.W, a.plane_axes = b, h, w, plane_axes
+    a.B, a.H, a.W, a.plane_axes = b, h, w, _plane_axes_id(plane_axes)
     a.box_warp, a.decoder_lr_mul = box_warp, decoder_lr_mul
     L.check(L.lib().hfagp_planes_query_bwd(C.byref(a), _stream()), "planes_query_bwd")
     return d_planes, d_coords, dec
@@ -1326,50 +1339,44 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
     kernels above 16 GiB, i.e. from B = 19 on, without a word); where the sort does not apply at all (more than 8192 bins per frame)
     or its scratch cannot be allocated, the scatter kernels run and say so once.  ``rec_out``: a list that receives pass 1's
     per-sample records [B,R,Sc+Sf,4] whatever the return form is (`raymarch_bwd_camera` reads them)."""
-    _chk(planes, "planes")
-    b, _, h, w, _ = planes.shape
+    who = "raymarch_bwd"
+    b, _, _ = _planes_dims(who, planes)
     r = res * res
-    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
-    geom = g_depth is not None or g_wsum is not None or depth_range is not None
-    if g_feat is not None:
-        _chk(g_feat, "g_feat")
+    if g_feat is not None and _chk(g_feat, f"{who}: g_feat").shape != (b, r, 32):
+        raise RuntimeError(f"raymarch_bwd: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
     for t, name in ((g_depth, "g_depth"), (g_wsum, "g_wsum")):
-        if t is not None and _chk(t, name).shape != (b, r):
+        if t is not None and _chk(t, f"{who}: {name}").shape != (b, r):
             raise RuntimeError(f"raymarch_bwd: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
-    if depth_range is not None and _chk(depth_range, "depth_range").shape != (2,):
+    if depth_range is not None and _chk(depth_range, f"{who}: depth_range").shape != (2,):
         raise RuntimeError(f"raymarch_bwd: depth_range must be [2] (ops.depth_range), got {tuple(depth_range.shape)}")
-    if _out is not None:
-        d_planes, rec = _out
-    else:
-        d_planes = torch.zeros_like(planes)
-        rec = torch.empty(b, r, sc + sf, 4, device=planes.device, dtype=torch.float32)
+    d_planes, rec = _out if _out is not None else (
+        torch.zeros_like(planes), torch.empty(b, r, u_strat.shape[-1] + u_imp.shape[-1], 4, device=planes.device, dtype=torch.float32))
     if rec_out is not None:
         rec_out.append(rec)
-    planes_absmax = _decoder_bound(planes, decoder_precision, planes_absmax)      # (one bound for every chunk of the batch)
-    a = L.RaymarchBwdArgs()
-    f = a.fwd
-    f.planes, f.cam2world, f.intrinsics = _ptr(planes), _ptr(_chk(cam2world, "cam2world")), _ptr(_chk(intrinsics, "intrinsics"))
-    f.u_strat, f.u_imp = _ptr(_chk(u_strat, "u_strat")), _ptr(_chk(u_imp, "u_imp"))
-    f.dec_w0, f.dec_b0, f.dec_w1, f.dec_b1 = _ptr(dec_w0), _ptr(dec_b0), _ptr(dec_w1), _ptr(dec_b1)
-    f.B, f.H, f.W, f.res, f.Sc, f.Sf = b, h, w, res, sc, sf
-    f.plane_axes, f.white_back = plane_axes, int(white_back)
-    f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
-    f.planes_absmax = _ptr(planes_absmax)
-    if state is not None:
-        if state.shape != (b, r, (sc + sf) * 35):
-            raise RuntimeError(f"raymarch_bwd: state must be [B, R, {(sc + sf) * 35}], got {tuple(state.shape)}")
-        f.state = _ptr(_chk(state, "state"))
-    a.g_feat, a.d_planes, a.rec = _ptr(g_feat), _ptr(d_planes), _ptr(rec)
-    gg = None
-    if geom:
-        gg = L.RaymarchGeomGrads()
-        gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
-    # pass 2 as two kernels (dL/dF through a scratch buffer, then the scatter alone: hfagp.h `df_scratch`) where the column
-    # variant applies; 201 MB per frame at 128^2 rays x 96 samples.  OFF by default: measured SLOWER than the fused kernel
-    # (B = 2: dL/dF 0.51 ms + scatter 1.41 ms against 1.58 ms fused — the scatter alone is the bound, the arithmetic already
-    # hides under it; profiles/r04_raybwd_split.txt).  Kept as the vehicle for work on the scatter.
     if rows is None:
         rows = os.environ.get("HFAGP_RAYBWD_ROWS", "1") != "0" and not two_kernel
+    dec = _raymarch_bwd_frames(
+        g_feat=g_feat, planes=planes, cam2world=cam2world, intrinsics=intrinsics, u_strat=u_strat, u_imp=u_imp, state=state,
+        g_depth=g_depth, g_wsum=g_wsum, depth_range=depth_range, d_planes=d_planes, rec=rec, decoder_grads=decoder_grads, dec_out=dec_out,
+        rows=rows, two_kernel=two_kernel, dec_w0=dec_w0, dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, res=res, ray_start=ray_start,
+        ray_end=ray_end, box_warp=box_warp, decoder_lr_mul=decoder_lr_mul, plane_axes=plane_axes, white_back=white_back,
+        decoder_precision=decoder_precision,
+        planes_absmax=_decoder_bound(planes, decoder_precision, planes_absmax))       # (one bound for every chunk of the batch)
+    if decoder_grads:
+        return d_planes, dec
+    return (d_planes, rec) if return_rec else d_planes
+
+
+def _raymarch_bwd_frames(*, g_feat, planes, cam2world, intrinsics, u_strat, u_imp, state, g_depth, g_wsum, depth_range, d_planes, rec,
+                         decoder_grads, dec_out, rows, two_kernel, **scene):
+    """`raymarch_bwd` of the frames it is given: the whole batch, or — from itself — one chunk of it, which so goes through the same
+    scratch decision again (free memory may have shrunk meanwhile).  Fills ``d_planes`` and ``rec`` in place and returns the
+    decoder-gradient tuple (None without ``decoder_grads``).  ``scene``: the decoder parameters and the scalars of `_ray_args`."""
+    a = L.RaymarchBwdArgs()
+    f = a.fwd
+    b, h, w, r, sc, sf = _ray_args("raymarch_bwd", f, planes, cam2world, intrinsics, u_strat, u_imp, state=state, **scene)
+    dec = _dec_grad_out("raymarch_bwd", a, [scene[k] for k in _DEC], decoder_grads, dec_out)
+    a.g_feat, a.d_planes, a.rec = _ptr(g_feat), _ptr(d_planes), _ptr(rec)
     scratch = None
     if rows:
         need = int(L.lib().hfagp_raymarch_bwd_rows_bytes(C.byref(f)))
@@ -1377,21 +1384,17 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
         cap = rows_scratch_cap(planes.device) if need > (4 << 30) or "HFAGP_RAYBWD_SCRATCH_GIB" in os.environ else (16 << 30)
         if need > cap and b > 1:
             # frame chunks: every per-frame input / output is a contiguous slice of the batch; the decoder gradients accumulate
+            # in the one `dec`; u_imp is [B * R, Sf]; the depth range is batch-global
             nb = max(1, min(b - 1, int(b * cap // need)))
-            if decoder_grads and dec_out is None:
-                dec_out = tuple(torch.zeros_like(t) for t in (dec_w0, dec_b0, dec_w1, dec_b1))
+            per_frame = dict(g_feat=g_feat, planes=planes, cam2world=cam2world, intrinsics=intrinsics, u_strat=u_strat, state=state,
+                             g_depth=g_depth, g_wsum=g_wsum, d_planes=d_planes, rec=rec)
             for b0 in range(0, b, nb):
                 b1 = min(b, b0 + nb)
-                raymarch_bwd(None if g_feat is None else g_feat[b0:b1], planes[b0:b1], cam2world[b0:b1], intrinsics[b0:b1], u_strat[b0:b1], u_imp[b0 * r:b1 * r],
-                             dec_w0, dec_b0, dec_w1, dec_b1, res, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back,
-                             False, decoder_grads, decoder_precision, planes_absmax, None if state is None else state[b0:b1],
-                             two_kernel, rows, dec_out, _out=(d_planes[b0:b1], rec[b0:b1]),
-                             g_depth=None if g_depth is None else g_depth[b0:b1],
-                             g_wsum=None if g_wsum is None else g_wsum[b0:b1], depth_range=depth_range)   # (the range is batch-global)
+                _raymarch_bwd_frames(**{k: None if t is None else t[b0:b1] for k, t in per_frame.items()}, u_imp=u_imp[b0 * r:b1 * r],
+                                     depth_range=depth_range, decoder_grads=decoder_grads, dec_out=dec, rows=rows, two_kernel=two_kernel,
+                                     **scene)
             ROWS_STATS.update(bytes=min(need, cap), chunks=-(-b // nb), path="rows")
-            if decoder_grads:
-                return d_planes, tuple(dec_out)
-            return (d_planes, rec) if return_rec else d_planes
+            return dec
         if need > 0:
             try:
                 scratch = torch.empty(need, device=planes.device, dtype=torch.uint8)
@@ -1401,28 +1404,24 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
                 _warn_once("rows_oom", f"raymarch_bwd: {need / 2**30:.2f} GiB of sort scratch could not be allocated: this call runs the "
                                        f"(~2 x slower) scatter kernels")
         else:
-            _warn_once("rows_unsupported", f"raymarch_bwd: the sort + gather backward does not take {h} x {w} planes at {res}^2 rays "
+            _warn_once("rows_unsupported", f"raymarch_bwd: the sort + gather backward does not take {h} x {w} planes at {f.res}^2 rays "
                                            f"(more than 8192 bins per frame): the (~2 x slower) scatter kernels run")
         if scratch is None:
             ROWS_STATS.update(bytes=0, chunks=1, path="scatter")
-    if scratch is None and two_kernel and plane_axes == 0 and h == w and h <= 256 and b * r * (sc + sf) * 128 <= (4 << 30):
+    # pass 2 as two kernels (dL/dF through a scratch buffer, then the scatter alone: hfagp.h `df_scratch`) where the column
+    # variant applies; 201 MB per frame at 128^2 rays x 96 samples.  OFF by default: measured SLOWER than the fused kernel
+    # (B = 2: dL/dF 0.51 ms + scatter 1.41 ms against 1.58 ms fused — the scatter alone is the bound, the arithmetic already
+    # hides under it; profiles/r04_raybwd_split.txt).  Kept as the vehicle for work on the scatter.
+    if scratch is None and two_kernel and f.plane_axes == 0 and h == w and h <= 256 and b * r * (sc + sf) * 128 <= (4 << 30):
         df = torch.empty(b, r, sc + sf, 32, device=planes.device, dtype=torch.float32)
         a.df_scratch = _ptr(df)
-    dec = None
-    if decoder_grads:
-        # `dec_out`: four tensors the decoder gradients are ACCUMULATED into (the parameters' .grad slices) instead of new ones
-        dec = tuple(dec_out) if dec_out is not None else tuple(torch.zeros_like(t) for t in (dec_w0, dec_b0, dec_w1, dec_b1))
-        for t, like in zip(dec, (dec_w0, dec_b0, dec_w1, dec_b1)):
-            if t.shape != like.shape or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
-                raise RuntimeError("raymarch_bwd: dec_out must be four contiguous fp32 device tensors shaped like the decoder parameters")
-        a.d_dec_w0, a.d_dec_b0, a.d_dec_w1, a.d_dec_b1 = (_ptr(t) for t in dec)
-    if gg is None:
+    if g_depth is None and g_wsum is None and depth_range is None:
         L.check(L.lib().hfagp_raymarch_bwd(C.byref(a), _stream()), "raymarch_bwd")
     else:
+        gg = L.RaymarchGeomGrads()
+        gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
         L.check(L.lib().hfagp_raymarch_bwd_geom(C.byref(a), C.byref(gg), _stream()), "raymarch_bwd")
-    if decoder_grads:
-        return d_planes, dec
-    return (d_planes, rec) if return_rec else d_planes
+    return dec
 
 
 def raymarch_bwd_camera(g_feat: Optional[torch.Tensor], planes: torch.Tensor, rec: torch.Tensor, cam2world, intrinsics, u_strat,
@@ -1433,29 +1432,20 @@ def raymarch_bwd_camera(g_feat: Optional[torch.Tensor], planes: torch.Tensor, re
     d origin, d direction per ray).  ``g_feat`` and the other arguments as in the `raymarch_bwd` call that wrote ``rec`` (its
     ``rec_out=`` / ``return_rec=True``): the depth, opacity and white_back terms are already in the records.  Independent of which
     pass-2 form that call ran; no atomics, two calls return the same bits."""
-    _chk(planes, "planes")
-    b, _, h, w, _ = planes.shape
-    r = res * res
-    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    a = L.RaymarchBwdArgs()
+    b, _, _, r, sc, sf = _ray_args("raymarch_bwd_camera", a.fwd, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1,
+                                   res, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision, planes_absmax,
+                                   None)
     dev = planes.device
-    if _chk(rec, "rec").shape != (b, r, sc + sf, 4):
+    if _chk(rec, "raymarch_bwd_camera: rec").shape != (b, r, sc + sf, 4):
         raise RuntimeError(f"raymarch_bwd_camera: rec must be [B, R, Sc + Sf, 4] = [{b}, {r}, {sc + sf}, 4], got {tuple(rec.shape)}")
-    if g_feat is not None and _chk(g_feat, "g_feat").shape != (b, r, 32):
+    if g_feat is not None and _chk(g_feat, "raymarch_bwd_camera: g_feat").shape != (b, r, 32):
         raise RuntimeError(f"raymarch_bwd_camera: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
     d_c2w = torch.empty(b, 16, device=dev, dtype=torch.float32)
     d_intr = torch.empty(b, 9, device=dev, dtype=torch.float32)
     ray_grad = torch.empty(b, r, 6, device=dev, dtype=torch.float32)
     if b == 0:
         return d_c2w, d_intr, ray_grad
-    a = L.RaymarchBwdArgs()
-    f = a.fwd
-    f.planes, f.cam2world, f.intrinsics = _ptr(planes), _ptr(_chk(cam2world, "cam2world")), _ptr(_chk(intrinsics, "intrinsics"))
-    f.u_strat, f.u_imp = _ptr(_chk(u_strat, "u_strat")), _ptr(_chk(u_imp, "u_imp"))
-    f.dec_w0, f.dec_b0, f.dec_w1, f.dec_b1 = _ptr(dec_w0), _ptr(dec_b0), _ptr(dec_w1), _ptr(dec_b1)
-    f.B, f.H, f.W, f.res, f.Sc, f.Sf = b, h, w, res, sc, sf
-    f.plane_axes, f.white_back = plane_axes, int(white_back)
-    f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
-    f.planes_absmax = _ptr(_decoder_bound(planes, decoder_precision, planes_absmax))
     a.g_feat, a.rec = _ptr(g_feat), _ptr(rec)
     L.check(L.lib().hfagp_raymarch_bwd_camera(C.byref(a), _ptr(ray_grad), _ptr(d_c2w), _ptr(d_intr), _stream()),
             "raymarch_bwd_camera")
