@@ -212,6 +212,9 @@ __global__ void __launch_bounds__(256) upfir_epilogue_kernel(HfagpUpfirEpilogueA
         o.y = lrelu_gain_clamp(o.y * d.y + nz + bs.y, a.act, a.alpha, a.gain, a.clamp);
         o.z = lrelu_gain_clamp(o.z * d.z + nz + bs.z, a.act, a.alpha, a.gain, a.clamp);
         o.w = lrelu_gain_clamp(o.w * d.w + nz + bs.w, a.act, a.alpha, a.gain, a.clamp);
+        if constexpr (H16) {     // fp16 storage: y_absmax bounds the values as STORED (a half may round up past the fp32 value)
+            o.x = (float)(_Float16)o.x; o.y = (float)(_Float16)o.y; o.z = (float)(_Float16)o.z; o.w = (float)(_Float16)o.w;
+        }
         vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
         return o;
     };

@@ -65,6 +65,28 @@ def _clamp(clamp: Optional[float]) -> float:
     return -1.0 if clamp is None else float(clamp)
 
 
+# The library sees pointers and integers, never a tensor's extent: for the streaming ops below these two checks are the only guard
+# between a mis-shaped operand and a kernel that reads or writes past it.  Shape tuples and dtypes only: they sit on the per-layer path.
+def _chk_operand(who: str, name: str, t: Optional[torch.Tensor], shape, like: torch.Tensor) -> Optional[torch.Tensor]:
+    """An optional fp32 operand of exactly `shape`, contiguous, on the device of `like`."""
+    if t is None:
+        return None
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != like.device or not t.is_contiguous():
+        raise RuntimeError(f"{who}: {name} must be a contiguous float32 tensor {list(shape)} on {like.device}, got "
+                           f"{list(t.shape)} {t.dtype} on {t.device}")
+    return t
+
+
+def _chk_absmax(who: str, name: str, t: Optional[torch.Tensor], like: torch.Tensor) -> Optional[torch.Tensor]:
+    """An optional slot buffer of the fp16 range tracking (`absmax_slots`): at least HFAGP_ABSMAX_FLOATS floats."""
+    if t is None:
+        return None
+    if t.numel() < L.ABSMAX_FLOATS or t.dtype != torch.float32 or t.device != like.device or not t.is_contiguous():
+        raise RuntimeError(f"{who}: {name} must be a contiguous float32 buffer of at least {L.ABSMAX_FLOATS} floats on {like.device}, "
+                           f"got {list(t.shape)} {t.dtype} on {t.device}")
+    return t
+
+
 # ----------------------------------------------------------------------------- weights
 def weight_prep(weight: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """weight [Cout, Cin, k, k] → (wt [k*k, Cin/4, Cout, 4], wsq [Cout, Cin])."""
@@ -196,17 +218,25 @@ def _style_args(a, who: str, w, affine_w, affine_b, wsq, style_gain: float, eps:
     """Fill the L.StyleArgs ``a`` of one layer; returns the outputs it points at: (styles [B, Cin], dcoef [B, Cout] | None)."""
     if w.dtype != torch.float32 or not w.is_cuda or w.stride(-1) != 1:
         raise RuntimeError(f"{who}: w must be a CUDA fp32 tensor with unit inner stride")
+    if w.dim() != 2 or affine_w.dim() != 2:
+        raise RuntimeError(f"{who}: w must be [B, w_dim] and affine_w [Cin, w_dim], got {list(w.shape)} and {list(affine_w.shape)}")
     b, wd = w.shape
     cin = affine_w.shape[0]
+    _chk_operand(who, "affine_w", affine_w, (cin, wd), w)
+    _chk_operand(who, "affine_b", affine_b, (cin,), w)
+    if wsq is not None:
+        if wsq.dim() != 2:
+            raise RuntimeError(f"{who}: wsq must be [Cout, Cin], got {list(wsq.shape)}")
+        _chk_operand(who, "wsq", wsq, (wsq.shape[0], cin), w)
     styles = torch.empty(b, cin, device=w.device, dtype=torch.float32)
     dcoef = None
-    a.w, a.affine_w, a.affine_b = _ptr(w), _ptr(_chk(affine_w, "affine_w")), _ptr(_chk(affine_b, "affine_b"))
+    a.w, a.affine_w, a.affine_b = _ptr(w), _ptr(affine_w), _ptr(affine_b)
     a.styles = _ptr(styles)
     a.B, a.w_dim, a.w_stride, a.Cin = b, wd, w.stride(0), cin
     a.style_gain, a.eps = style_gain, eps
     if wsq is not None:
         dcoef = torch.empty(b, wsq.shape[0], device=w.device, dtype=torch.float32)
-        a.wsq, a.dcoef, a.Cout = _ptr(_chk(wsq, "wsq")), _ptr(dcoef), wsq.shape[0]
+        a.wsq, a.dcoef, a.Cout = _ptr(wsq), _ptr(dcoef), wsq.shape[0]
     return styles, dcoef
 
 
@@ -454,12 +484,18 @@ def fused_torgb_supported(x: torch.Tensor, wt: torch.Tensor, cout: int, batch: i
 def torgb_finish(part: torch.Tensor, bias: torch.Tensor, rgb_in: Optional[torch.Tensor], clamp: Optional[float],
                  y_pre: Optional[torch.Tensor] = None) -> torch.Tensor:
     """rgb_part of a fused-toRGB conv -> NCHW image: clamp(sum of parts + bias) + upsample2d(rgb_in)."""
+    _chk(part, "part")
+    if part.dim() != 5 or part.shape[4] != 4 or bias.dim() != 1:
+        raise RuntimeError(f"torgb_finish: part must be [nparts, B, H, W, 4] and bias [Cout], got {list(part.shape)} and {list(bias.shape)}")
     nparts, b, h, w, _ = part.shape
     cout = bias.shape[0]
+    _chk_operand("torgb_finish", "bias", bias, (cout,), part)
+    _chk_operand("torgb_finish", "rgb_in", rgb_in, (b, cout, h // 2, w // 2), part)
+    _chk_operand("torgb_finish", "y_pre", y_pre, (b, cout, h, w), part)
     out = torch.empty(b, cout, h, w, device=part.device, dtype=torch.float32)
     a = L.TorgbFinishArgs()
-    a.part, a.bias, a.rgb_out, a.y_pre = _ptr(part), _ptr(_chk(bias, "bias")), _ptr(out), _ptr(y_pre)
-    a.rgb_in = _ptr(_chk(rgb_in, "rgb_in")) if rgb_in is not None else None
+    a.part, a.bias, a.rgb_out, a.y_pre = _ptr(part), _ptr(bias), _ptr(out), _ptr(y_pre)
+    a.rgb_in = _ptr(rgb_in)
     a.nparts, a.B, a.H, a.W, a.Cout = nparts, b, h, w, cout
     a.clamp = _clamp(clamp)
     L.check(L.lib().hfagp_torgb_finish_fwd(C.byref(a), _stream()), "torgb_finish_fwd")
@@ -526,10 +562,17 @@ def upfir_epilogue(yt: torch.Tensor, dcoef: Optional[torch.Tensor], noise: Optio
                    gain: float = math.sqrt(2.0), clamp: Optional[float] = None,
                    y_absmax: Optional[torch.Tensor] = None) -> torch.Tensor:
     """yt [B, 2H+1, 2W+1, C] raw transposed conv → FIR(pad 1, gain 4) → demod/noise/bias/act → [B,2H,2W,C].
-    A float16 ``yt`` (fp16 storage, `modconv` y_f16) gives a float16 result; the arithmetic is fp32 either way."""
+    A float16 ``yt`` (fp16 storage, `modconv` y_f16) gives a float16 result; the arithmetic is fp32 either way.
+    ``y_absmax`` (`absmax_slots`) receives max |result| of the values as stored."""
     half = _chk_act(yt, "yt").dtype == torch.float16
+    if yt.dim() != 4 or yt.shape[1] < 3 or yt.shape[2] < 3 or yt.shape[1] % 2 == 0 or yt.shape[2] % 2 == 0:
+        raise RuntimeError(f"upfir_epilogue: yt must be [B, 2H+1, 2W+1, C] with an odd height and width of at least 3, got {list(yt.shape)}")
     b, hi, wi, c = yt.shape
     h, w = (hi - 1) // 2, (wi - 1) // 2
+    _chk_operand("upfir_epilogue", "dcoef", dcoef, (b, c), yt)
+    _chk_operand("upfir_epilogue", "noise", noise, (2 * h, 2 * w), yt)
+    _chk_operand("upfir_epilogue", "bias", bias, (c,), yt)
+    _chk_absmax("upfir_epilogue", "y_absmax", y_absmax, yt)
     y = torch.empty(b, 2 * h, 2 * w, c, device=yt.device, dtype=yt.dtype)
     a = L.UpfirEpilogueArgs()
     a.yt, a.dcoef, a.noise, a.bias, a.y = yt.data_ptr(), _ptr(dcoef), _ptr(noise), _ptr(bias), y.data_ptr()
@@ -547,10 +590,15 @@ def skip_upsample_add(img: Optional[torch.Tensor], y: torch.Tensor, plane_major:
     """SynthesisBlock 'skip': upsample2d(img) + y (channels-last).  plane_major → [B,3,H,W,C/3].  out_absmax ([64 x 32],
     `absmax_slots`): receives max |output| (the bound the ray marcher's 16-bit decoder scales by)."""
     _chk(y, "y")
+    if y.dim() != 4:
+        raise RuntimeError(f"skip_upsample_add: y must be [B, H, W, C], got {list(y.shape)}")
     b, ho, wo, c = y.shape
+    _chk_absmax("skip_upsample_add", "out_absmax", out_absmax, y)
     a = L.SkipArgs()
     if img is not None:
-        _chk(img, "img")
+        if ho % 2 or wo % 2:
+            raise RuntimeError(f"skip_upsample_add: y {list(y.shape)} must have an even height and width to add an up-sampled img to")
+        _chk_operand("skip_upsample_add", "img", img, (b, ho // 2, wo // 2, c), y)
         a.img_in, a.H, a.W = _ptr(img), img.shape[1], img.shape[2]
     else:
         a.H, a.W = ho, wo
@@ -604,13 +652,20 @@ def torgb_small(x: torch.Tensor, weight: torch.Tensor, styles: torch.Tensor, bia
     """ToRGBLayer with ≤4 output channels + skip add; x channels-last, rgb NCHW.  `y_pre` (optional,
     [B,Cout,H,W]) receives the toRGB output before clamp and skip add (backward needs the clamp mask)."""
     _chk(x, "x")
+    if x.dim() != 4 or weight.dim() != 2:
+        raise RuntimeError(f"torgb_small: x must be [B, H, W, Cin] and weight [Cout, Cin], got {list(x.shape)} and {list(weight.shape)}")
     b, h, w, cin = x.shape
     cout = weight.shape[0]
+    _chk_operand("torgb_small", "weight", weight, (cout, cin), x)
+    _chk_operand("torgb_small", "styles", styles, (b, cin), x)
+    _chk_operand("torgb_small", "bias", bias, (cout,), x)
+    _chk_operand("torgb_small", "rgb_in", rgb_in, (b, cout, h // 2, w // 2), x)
+    _chk_operand("torgb_small", "y_pre", y_pre, (b, cout, h, w), x)
     out = torch.empty(b, cout, h, w, device=x.device, dtype=torch.float32)
     a = L.TorgbArgs()
     a.y_pre = _ptr(y_pre)
-    a.x, a.weight, a.styles, a.bias = _ptr(x), _ptr(_chk(weight, "weight")), _ptr(_chk(styles, "styles")), _ptr(bias)
-    a.rgb_in = _ptr(_chk(rgb_in, "rgb_in")) if rgb_in is not None else None
+    a.x, a.weight, a.styles, a.bias = _ptr(x), _ptr(weight), _ptr(styles), _ptr(bias)
+    a.rgb_in = _ptr(rgb_in)
     a.rgb_out = _ptr(out)
     a.B, a.H, a.W, a.Cin, a.Cout = b, h, w, cin, cout
     a.clamp = _clamp(clamp)

@@ -443,7 +443,7 @@ typedef struct {
     int32_t B, H, W, C;       /* H, W = INPUT resolution of the up-conv */
     int32_t act;
     float noise_strength, alpha, gain, clamp;
-    float*       y_absmax;    /* optional [HFAGP_ABSMAX_FLOATS]: max |y| (see HfagpModconvArgs) */
+    float*       y_absmax;    /* optional [HFAGP_ABSMAX_FLOATS]: max |y| (see HfagpModconvArgs); io_f16: of the halves as stored */
     int32_t      io_f16;      /* 1: yt and y are IEEE fp16 tensors (same shapes; HfagpModconvArgs::x_f16 / y_f16), math stays fp32 */
 } HfagpUpfirEpilogueArgs;
 

@@ -560,7 +560,8 @@ def test_upconv_and_fir_epilogue_with_fp16_storage(dev, x_half, h, cin, cout, b)
     assert out.dtype == torch.float16 and out.shape == (b, 2 * h, 2 * h, cout)
     # same inputs, same fp32 arithmetic: the result is the fp32 one rounded to fp16, exactly
     assert torch.equal(out, out_ref.half())
-    assert abs(am.max().item() - out_ref.abs().max().item()) <= 1e-6 * out_ref.abs().max().item()
+    # the published maximum is that of the tensor as STORED: the fp32 result's, rounded to fp16 (it may round up past the fp32 value)
+    assert am.max().item() == out_ref.half().float().abs().max().item()
 
 
 def test_generator_sr_storage_f16(dev, full_gen):
