@@ -3,7 +3,7 @@
 //   dW[t][ci][co] = sum_{b, m, n}  (x * s_b)[b][m + ady_t][n + adx_t][ci] * g[img_t][b][m + bdy_t][n + bdx_t][co]
 //
 // GEMM view per tap: M = ci, N = co, K = B*H*W positions.  A block owns a 64(ci) x 64(co) tile for ALL taps
-// (each wave a 32x32 tile x ntaps accumulators) and walks 4x16-position tiles: the x patch and the g patch
+// (each wave a 32x32 tile x ntaps accumulators) and walks 2x16-position tiles: the x patch and the g patch
 // (both with a 1-pixel halo) are staged in LDS once per position tile and reused by the 9 taps.  Split-K over
 // (b, position tile) writes deterministic slabs; wgrad_reduce_kernel sums them, adds the demodulation term
 // and writes the gradient in the parameter's [Cout][Cin][kh][kw] layout.
@@ -12,14 +12,13 @@
 //                  (ti&1, tj&1) at shift (ti>>1, tj>>1); x does not shift.
 //   1x1 (toRGB)  : one tap, no shifts.
 #include "common.h"
+#include "wgrad_plan.h"                          // TPH x TPW position tile (78 KB of LDS double-buffered -> 2 blocks per CU), WT
 
 namespace hfagp {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int TPH = 2, TPW = 16;                 // position tile (2 x 16: 78 KB of LDS double-buffered -> 2 blocks per CU)
 constexpr int PPH = TPH + 2, PPW = TPW + 2;      // patch with halo
-constexpr int WT = 64;                           // ci / co tile
 constexpr int WS = WT + 4;                       // LDS row stride (floats)
 
 struct WTap { signed char ady, adx, bdy, bdx, widx; };
@@ -35,8 +34,8 @@ struct WgradParams {
 
 // Double-buffered: the x / g patches of position tile u+1 are fetched into registers before the MFMAs of tile u
 // and written to the other LDS buffer after them, so there is ONE barrier per tile and the global latency hides
-// under 288 MFMAs.  117 KB of LDS -> one workgroup (one wave per SIMD) per CU, which is enough to keep the
-// matrix pipe busy because the 9 tap accumulators are independent.
+// under 144 MFMAs.  78 336 B of LDS -> two workgroups per CU (__launch_bounds__(256, 2)); within a wave the 9 tap accumulators
+// are independent, which keeps the matrix pipe busy.
 constexpr int STG = (PPH * PPW * 16 + 255) / 256;      // float4 per thread per patch
 
 // SHARE = 1: all taps read the same g element (3x3 / 1x1: only x shifts) -> one B fetch per K step;
@@ -319,7 +318,7 @@ __global__ void __launch_bounds__(256) wgrad_sum_final_kernel(const float* __res
 static int launch_wgrad_sum_final(const HfagpWgradArgs* a, hipStream_t s) {
     const size_t n4 = (size_t)a->Cin * a->Cout * 9 / 4;
     wgrad_sum_final_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, s>>>(a->workspace, a->weight, a->dd, a->dcoef, a->styles, a->dweight,
-                                                                        a->ksplit, a->Cin, a->Cout, a->B, a->accumulate, a->dd_stride > 0 ? a->dd_stride : a->Cout);
+                                                                        a->ksplit, a->Cin, a->Cout, a->B, a->accumulate, wgrad_dd_stride(a));
     return check_launch("conv_wgrad/sum");
 }
 
@@ -328,7 +327,7 @@ static int launch_wgrad_sum_final(const HfagpWgradArgs* a, hipStream_t s) {
 static int launch_wgrad_reduce(const HfagpWgradArgs* a, const RedTaps& rt, int ntaps, int wtaps, hipStream_t s) {
     wgrad_reduce_tiled_kernel<1><<<dim3((unsigned)(a->Cin / 8), (unsigned)(a->Cout / 32)), 256, 0, s>>>(
         a->workspace, a->weight, a->dd, a->dcoef, a->styles, a->dweight, a->ksplit, ntaps, a->Cin, a->Cout, a->B, wtaps, rt, a->accumulate,
-        a->dd_stride > 0 ? a->dd_stride : a->Cout);
+        wgrad_dd_stride(a));
     return check_launch("conv_wgrad/reduce");
 }
 
@@ -431,11 +430,6 @@ __global__ void __launch_bounds__(64) channel_sum_final_kernel(const float* __re
 
 }  // namespace hfagp
 
-namespace hfagp {      // wgrad_bf16.hip
-int launch_wgrad3x3_bf16(const HfagpWgradArgs* a, hipStream_t s);
-int launch_wgrad_up_bf16(const HfagpWgradArgs* a, hipStream_t s);
-}
-
 using namespace hfagp;
 
 template <int NT, int SHARE>
@@ -447,6 +441,7 @@ static int run_wgrad(WgradParams& p, const HfagpWgradArgs* a, hipStream_t s, boo
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<NT, SHARE>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        attr_set = true;
     }
     wgrad_kernel<NT, SHARE><<<grid, 256, lds, s>>>(p);
     int rc = check_launch("conv_wgrad");
@@ -464,32 +459,21 @@ static int run_wgrad(WgradParams& p, const HfagpWgradArgs* a, hipStream_t s, boo
     const dim3 rgrid((unsigned)((a->Cin * a->Cout + 255) / 256), (unsigned)NT);
     wgrad_reduce_kernel<<<rgrid, 256, 0, s>>>(p.slabs, a->weight, a->dd, a->dcoef, a->styles, a->dweight, a->ksplit, NT,
                                               a->Cin, a->Cout, a->B, wtaps, taps, a->accumulate,
-                                              a->dd_stride > 0 ? a->dd_stride : a->Cout);
+                                              wgrad_dd_stride(a));
     return check_launch("conv_wgrad/reduce");
 }
 
 extern "C" {
 
-// split-K policy (ABI 11; the host used to carry a copy of it): one resident block per CU for the split-bf16 kernel (measured 5 %
-// better than two rounds: half the slabs to write and reduce), two rounds for the fp32 one; never more slabs than position tiles
+// split-K policy (ABI 11): wgrad_plan.h
 int32_t hfagp_wgrad_ksplit(const HfagpWgradArgs* a) {
     if (!a || a->B <= 0 || a->H <= 0 || a->W <= 0 || a->Cin <= 0 || a->Cout <= 0) return 1;
-    const bool up = a->mode == HFAGP_CONVT3X3_UP2;
-    const bool split16 = a->precision == HFAGP_PREC_BF16X3 && (a->mode == HFAGP_CONV3X3 || up) && a->Cout % 64 == 0 &&
-                         (a->Cin % 64 == 0 || (up && a->Cin == 32));
-    const int rows = split16 ? 4 : 2;                  // position tile of the kernel that will run: rows x 16
-    const long long units = (long long)a->B * ((a->H + rows - 1) / rows) * ((a->W + 15) / 16);
-    long long tiles = (long long)((a->Cin + 63) / 64) * ((a->Cout + 63) / 64);
-    const long long want = (split16 ? 256 : 512) / (tiles > 0 ? tiles : 1);
-    long long k = want < 1 ? 1 : want;
-    if (k > units) k = units;
-    if (k > 256) k = 256;
-    return (int32_t)(k < 1 ? 1 : k);
+    return wgrad_ksplit_policy(a);
 }
 
 size_t hfagp_wgrad_workspace_bytes(const HfagpWgradArgs* a) {
     if (!a || a->ksplit <= 0) return 0;
-    // (up-sampling mode: the four parity launches write disjoint regions — 4 + 2 + 2 + 1 taps — and ONE reducer finishes them)
+    // (up-sampling mode in fp32: the four parity launches write disjoint regions — 4 + 2 + 2 + 1 taps — and ONE reducer finishes them)
     const int ntaps = a->mode == HFAGP_CONV1X1 ? 1 : 9;
     return (size_t)a->ksplit * ntaps * a->Cin * a->Cout * sizeof(float);
 }
@@ -507,7 +491,7 @@ int hfagp_conv_wgrad(const HfagpWgradArgs* a, void* stream) {
     if (a->mode == HFAGP_CONV3X3) {
         p.gH = a->H; p.gW = a->W;
         for (int t = 0; t < 9; ++t) p.tap[t] = WTap{(signed char)(t / 3 - 1), (signed char)(t % 3 - 1), 0, 0, (signed char)t};
-        if (a->precision == HFAGP_PREC_BF16X3 && a->Cin % 64 == 0 && a->Cout % 64 == 0) {
+        if (wgrad_split16(a)) {
             // split-bf16 MFMA kernel (slabs in the parameter layout), then the elementwise reducer
             int rc = launch_wgrad3x3_bf16(a, s);
             if (rc != HFAGP_OK) return rc;
@@ -529,7 +513,7 @@ int hfagp_conv_wgrad(const HfagpWgradArgs* a, void* stream) {
         const long long img = (long long)a->B * p.gH * p.gW * a->Cout;
         static const int taps_of[4][4] = {{0, 2, 6, 8}, {1, 7, -1, -1}, {3, 5, -1, -1}, {4, -1, -1, -1}};
         static const int ntaps_of[4] = {4, 2, 2, 1};
-        if (a->precision == HFAGP_PREC_BF16X3 && (a->Cin % 64 == 0 || a->Cin == 32) && a->Cout % 64 == 0) {
+        if (wgrad_split16(a)) {
             // split-bf16 MFMA kernel: all nine taps in ONE launch (slabs in the parameter layout), then the elementwise reducer
             int rc = launch_wgrad_up_bf16(a, s);
             if (rc != HFAGP_OK) return rc;

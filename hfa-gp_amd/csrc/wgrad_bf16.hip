@@ -1,7 +1,7 @@
 // Weight gradient of the 3x3 modulated conv on v_mfma_f32_32x32x16_bf16 with split operands (gfx950):
 //     dW[tap][ci][co] = sum_{b, pos} (x s)[b][pos + tap][ci] * g[b][pos][co]
 // Same decomposition as wgrad.hip (M = ci, N = co, K = positions; a block owns a 64 x 64 (ci, co) tile for all nine
-// taps and walks 4 x 16 position tiles; split-K slabs + wgrad_reduce_tiled_kernel), but the products are BF16X3: both
+// taps and walks 4 x 16 position tiles; split-K slabs + wgrad_sum_final_kernel), but the products are BF16X3: both
 // operands are split into hi + lo bf16 parts (a gradient needs fp32's exponent range, which bf16 keeps) and a
 // product is hi.hi + lo.hi + hi.lo accumulated in fp32 — 3 MFMAs of the 16x faster pipe instead of 8 fp32 MFMAs
 // per 16 positions.
@@ -21,7 +21,9 @@
 // conflict-free 8-byte writes) and the 32 lanes of an MFMA operand read 32 consecutive rows (conflict-free);
 // MFMA row / column l of wave w therefore stands for channel 4 (l & 15) + 2 w + (l >> 4) of the tile.
 #include <type_traits>
+#include <utility>
 #include "common.h"
+#include "wgrad_plan.h"                          // QH x QW position tile (4 rows: 108 MFMAs per wave per tile), CT
 
 namespace hfagp {
 
@@ -31,19 +33,17 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// The kernel is written in ROLES: the SHIFTED operand "a" (staged with a one-position halo, its channels are the MFMA
-// rows) and the PLAIN operand "b" (its channels are the MFMA columns).  3x3 conv: a = x*s (shift = tap offset), b = g.
-// Parity launches of the up-conv (SWAP): a = the parity image of the y_t gradient (shift 0 / +1), b = x*s.
+// Both kernels: x [B][H][W][Cin] is the SHIFTED operand (staged with a halo, its channels are the MFMA rows), g the plain one (its
+// channels are the MFMA columns).  tiles_h x tiles_w position tiles per sample (wgrad_plan.h: QH x QW positions).
 struct Wg16Params {
-    const float* a; const float* b; const float* styles;       // styles [B][channels of x] or null
+    const float* x; const float* g; const float* styles;       // g [B][gH][gW][Cout]; styles [B][Cin] or null
     float* slabs;                       // [ksplit][Cout][Cin][9]: the parameter layout (tap = 3 (dy) + dx)
-    int B, aH, aW, aC, bH, bW, bC;      // image extents / channel counts of the two operands (bH x bW = position grid)
-    int Cin, Cout, tiles_h, tiles_w, ksplit;
+    // gH x gW = H x W = the position grid.  g's extents stay parameters of their own: read from H and W, the same kernel allocates
+    // 210 vector registers instead of 204 (no spill, the same schedule otherwise)
+    int B, H, W, gH, gW, Cin, Cout, tiles_h, tiles_w, ksplit;
 };
 
-constexpr int QH = 4, QW = 16;                   // position tile (4 rows: 108 MFMAs per wave per tile)
 constexpr int XR = QH + 2;                       // x patch: 6 rows of 18 columns (halo 1 + 16 + 1)
-constexpr int CT = 64;                           // ci / co tile
 constexpr int XROW = 32;                         // bytes per patch row of one copy (16 columns)
 constexpr int XCOPY = XR * XROW;                 // 192: copy A at 0, copy B at XCOPY
 constexpr int XPITCH = 2 * XCOPY + 16;           // bytes per ci row of one part (400: 100 dwords = 36 mod 64, conflict-free b128);
@@ -102,9 +102,184 @@ __device__ __forceinline__ void store_slab_final(const f32x16 (&acc)[9], char* l
     }
 }
 
-// DYM / DXM: bit i set = patch-row / window offset i is used (shift i - 1).  3x3: 7, 7 (nine taps).  Parity images of the
-// up-conv: shifts {0, +1} = bits 1, 2 (6) or {0} (2).  SWAP: operand a is the gradient, b is x (styles go to b, and
-// the tile is stored transposed into the [Cin][Cout] slab).
+// ---------------------------------------------------------------------------------------------------------------
+// The pieces the two kernels below share.  Every one is inlined; where the compiled code dictates a form, the piece says so.
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in that order
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) { static_for_seq(f, std::make_integer_sequence<int, N>{}); }
+
+// ---- staging.  A unit = one row x one column group (4 neighbouring positions) x one channel group (4 channels): 4 float4 loads,
+// one per column.  x: 6 rows x 5 column groups (20 >= 18 columns) x 16 channel groups = 480 units, thread t owns units t and
+// 256 + t (t < 224; the others repeat the last unit: same data, same addresses); g: 4 rows x 4 column groups x 16 channel groups =
+// 256 units, one per thread.
+struct Unit { int q, cg, row; };
+constexpr int XUNITS = XR * 5 * 16;
+__device__ __forceinline__ Unit x_unit(int u) { return {u & 15, (u >> 4) % 5, (u >> 4) / 5}; }
+__device__ __forceinline__ Unit g_unit(int u) { return {u & 15, (u >> 4) & 3, u >> 6}; }
+// (x_unit's two indices are computed by the caller before either is taken apart, and a unit's byte offset inside its image,
+// ((row W + 4 cg) C + 4 q) 4, is written out in the kernels: as a function here it is simplified on its own before it is inlined, and
+// both kernels come out with other address arithmetic.)
+// LDS byte offsets of a unit's writes inside an x stage / a g stage, channel e = 0, hi part (+ 16 e XPITCH, + XPART: immediates).
+// x unit (row, cg) holds patch columns 4cg .. 4cg+3.  Copy A keeps columns 0..15: an 8-byte write for cg <= 3; copy B
+// keeps columns 2..17 at index col - 2: the pair's first dword goes to dword 2cg - 1 (cg >= 1), its second to dword
+// 2cg (cg <= 3).  What a copy does not hold is written into the row's 16 pad bytes instead (no branch in a piece).
+struct XOffsets { int oa, ob0, ob1; };
+// (Filled in through a reference, and g_offset's sum in this order: returned by value / with the terms the other way round the
+// kernels' prologues come out in another instruction order.)
+__device__ __forceinline__ void x_offsets(const Unit& u, XOffsets& o) {
+    const int base = u.q * XPITCH;
+    o.oa = base + (u.cg <= 3 ? u.row * XROW + 8 * u.cg : 2 * XCOPY);
+    o.ob0 = base + (u.cg >= 1 ? XCOPY + u.row * XROW + 4 * (2 * u.cg - 1) : 2 * XCOPY + 8);
+    o.ob1 = base + (u.cg <= 3 ? XCOPY + u.row * XROW + 8 * u.cg : 2 * XCOPY + 12);
+}
+__device__ __forceinline__ int g_offset(const Unit& u) { return (u.row * QW + 4 * u.cg) * 2 + u.q * GPITCH; }
+
+// ---- loads.  Raw buffer loads: the image of sample b is a buffer resource (4 scalar registers), a position is a 32-bit byte
+// offset = (scalar tile origin) + (per-thread constant), and what is not there (outside the image, a null tile) gets the offset OOB
+// past the end of any resource, for which the hardware returns zeros.
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+constexpr unsigned OOB = 0xfffffff0u;
+__device__ __forceinline__ rsrc_t image_rsrc(const float* base, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
+}
+__device__ __forceinline__ float4 load_b128(rsrc_t r, unsigned off) {
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
+}
+// the four columns col0 .. col0 + 3 of a unit (C channels per position; base_t: the tile's scalar offset, uoff: the unit's own).
+// `rowok` arrives as a value: with the row test written out in front of `&&` at the load, hipcc kept the short circuit of the up
+// kernel's g loads as branches inside the tile loop, and a `vmcnt(0)` behind each (profiles/wgrad_lift/README.md).
+__device__ __forceinline__ void load_unit(float4 (&r)[4], rsrc_t img, bool rowok, int col0, int W, int base_t, int C, int uoff) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const bool ok = rowok && (unsigned)(col0 + c) < (unsigned)W;
+        r[c] = load_b128(img, ok ? (unsigned)(base_t + c * C * 4 + uoff) : OOB);
+    }
+}
+// Styles [B][Cin] or none.  No styles: the resource is empty, the load returns zeros and `one` = 1 is added — a select on a
+// uniform condition became a branch around the load, which costs hipcc its exact count of the loads in flight.
+struct StyleSrc { rsrc_t rs; float one; };
+__device__ __forceinline__ StyleSrc style_src(const float* styles, const float* any, int n) {
+    return {image_rsrc(styles ? styles : any, styles ? (unsigned)n * 4u : 0u), styles ? 0.f : 1.f};
+}
+__device__ __forceinline__ float4 load_style(const StyleSrc& s, int chan0) {
+    const float4 v = load_b128(s.rs, (unsigned)(chan0 * 4));
+    return make_float4(v.x + s.one, v.y + s.one, v.z + s.one, v.w + s.one);
+}
+struct TileOrigin { int b, m0, n0; };
+__device__ __forceinline__ TileOrigin tile_origin(int u, int tiles_w, int tiles_h) {
+    const int tw = u % tiles_w, th = (u / tiles_w) % tiles_h;
+    return {u / (tiles_w * tiles_h), th * QH, tw * QW};
+}
+
+// ---- conversion pieces: channel e of a unit (four float4, one per column) -> one split_run + its LDS writes.  x (times its
+// style): an 8-byte write to copy A and two 4-byte writes to copy B, per part; g: an 8-byte write per part.
+template <int e> __device__ __forceinline__ float chan(const float4& v) { return e == 0 ? v.x : e == 1 ? v.y : e == 2 ? v.z : v.w; }
+template <int e, int STAGE>                                  // STAGE: bytes between two x stages
+__device__ __forceinline__ void commit_x_piece(char* lds, int stage, const XOffsets& o, const float4 (&r)[4], float sv) {
+    uint2 hi, lo;
+    split_run(chan<e>(r[0]) * sv, chan<e>(r[1]) * sv, chan<e>(r[2]) * sv, chan<e>(r[3]) * sv, hi, lo);
+    char* row = lds + stage * STAGE + 16 * e * XPITCH;       // (the stage's address after the split, as both kernels had it)
+    *reinterpret_cast<uint2*>(row + o.oa) = hi;
+    *reinterpret_cast<uint2*>(row + o.oa + XPART) = lo;
+    *reinterpret_cast<unsigned*>(row + o.ob0) = hi.x;
+    *reinterpret_cast<unsigned*>(row + o.ob1) = hi.y;
+    *reinterpret_cast<unsigned*>(row + o.ob0 + XPART) = lo.x;
+    *reinterpret_cast<unsigned*>(row + o.ob1 + XPART) = lo.y;
+}
+template <int e>
+__device__ __forceinline__ void commit_g_piece(char* gunit, const float4 (&r)[4]) {       // gunit: g stage + g_offset of the unit
+    uint2 hi, lo;
+    split_run(chan<e>(r[0]), chan<e>(r[1]), chan<e>(r[2]), chan<e>(r[3]), hi, lo);
+    char* dst = gunit + 16 * e * GPITCH;
+    *reinterpret_cast<uint2*>(dst) = hi;
+    *reinterpret_cast<uint2*>(dst + GPART) = lo;
+}
+
+// per-lane fragment base (bytes inside a stage): LDS row 32 w + l31 of the wave's tile, columns 8h..
+__device__ __forceinline__ int frag_base(int w, int l31, int h, int pitch) { return (32 * w + l31) * pitch + 8 * h * 2; }
+// fragments of one group as they come out of LDS: copy A / copy B window of the patch row, hi and lo part
+struct Raw { u32x4 ha, hb, la, lb; };
+__device__ __forceinline__ Raw read_a(const char* xst, int abase, int prow) {
+    const char* ar = xst + abase + prow * XROW;
+    Raw r;
+    r.ha = *reinterpret_cast<const u32x4*>(ar);
+    r.hb = *reinterpret_cast<const u32x4*>(ar + XCOPY);
+    r.la = *reinterpret_cast<const u32x4*>(ar + XPART);
+    r.lb = *reinterpret_cast<const u32x4*>(ar + XPART + XCOPY);
+    return r;
+}
+
+// ---- the K loop.  A GROUP = one patch row of one K step (tile row kr, patch row kr + dy): 4 LDS reads, the dx windows, the MFMAs
+// of the taps that row serves.  Which rows and windows a kernel (or a phase of it) uses, and which accumulator a tap lands in:
+//   dym / dxm: bit i set = patch-row / window offset i is used (shift i - 1);  slot(dy, dx): accumulator of that tap.
+template <int DYM, int DXM>
+struct Taps3x3 {                                             // 7, 7: the nine taps in (dy, dx) order
+    static constexpr int dym = DYM, dxm = DXM;
+    static constexpr int slot(int dy, int dx) { return rank3(DYM, dy) * popc3(DXM) + rank3(DXM, dx); }
+};
+template <int PP, int PQ>
+struct TapsUp {                                              // parity image (PP, PQ) of the up-conv: shifts -1 / 0, or 0 alone
+    static constexpr int dym = PP ? 2 : 3, dxm = PQ ? 2 : 3;
+    // (dy = 1: shift 0 -> sy = 0; dy = 0: shift -1 -> sy = 1, the same for dx; tap slot = 3 ky + kx, ky = PP + 2 sy, kx = PQ + 2 sx)
+    static constexpr int slot(int dy, int dx) { return 3 * (PP + 2 * (1 - dy)) + PQ + 2 * (1 - dx); }
+};
+// the fragments a group consumes: the x windows and the g row of its K step, hi and lo part
+struct Group { Raw a; u32x4 bh, bl; };
+template <class Taps>
+__device__ __forceinline__ Group read_group0(const char* xst, int abase, const char* gfrag) {        // gfrag: g stage + its frag_base
+    return {read_a(xst, abase, nth3(Taps::dym, 0)), *reinterpret_cast<const u32x4*>(gfrag), *reinterpret_cast<const u32x4*>(gfrag + GPART)};
+}
+// the MFMAs of one group
+template <class Taps, int dy>
+__device__ __forceinline__ void mfma_group(f32x16 (&acc)[9], const Raw& w, const u32x4& bh, const u32x4& bl) {
+    constexpr int DXM = Taps::dxm;
+    u32x4 ah[3], al[3];                           // the three dx windows (start column 8h + dx)
+    ah[0] = w.ha; al[0] = w.la; ah[2] = w.hb; al[2] = w.lb;
+    if constexpr ((DXM >> 1) & 1) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {             // columns 8h+1+2e, 8h+2+2e = high half of A's dword e, low half of B's
+            ah[1][e] = __builtin_amdgcn_alignbit(w.hb[e], w.ha[e], 16);
+            al[1][e] = __builtin_amdgcn_alignbit(w.lb[e], w.la[e], 16);
+        }
+    }
+    // product-major (hi.hi, lo.hi, hi.lo): the three MFMAs of one accumulator are up to two other MFMAs apart
+#pragma unroll
+    for (int pr = 0; pr < 3; ++pr)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx)
+            if ((DXM >> dx) & 1) {
+                const int t = Taps::slot(dy, dx);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pr == 1 ? al[dx] : ah[dx]),
+                                                                 __builtin_bit_cast(bf16x8, pr == 2 ? bl : bh), acc[t], 0, 0, 0);
+            }
+}
+// Group G of a K loop with read-ahead: the LDS reads of group G + 1, the MFMAs of group G, then the pieces P = G, G + NG, ... < NP of
+// the conversion that rides along (piece(integral_constant<int, P>)); a sched_barrier per group pins that order.
+template <class Taps, int G, int NP, class Piece>
+__device__ __forceinline__ void group_step(f32x16 (&acc)[9], Group& cur, const char* xst, int abase, const char* gfrag, Piece&& piece) {
+    constexpr int DYM = Taps::dym, NDY = popc3(DYM), NG = QH * NDY;
+    constexpr int kr = G / NDY, dy = nth3(DYM, G % NDY);
+    constexpr int G1 = G + 1, kr1 = G1 / NDY, dy1 = nth3(DYM, G1 % NDY);
+    Group nxt = cur;
+    if constexpr (G1 < NG) {
+        nxt.a = read_a(xst, abase, kr1 + dy1);
+        if constexpr (kr1 != kr) {
+            nxt.bh = *reinterpret_cast<const u32x4*>(gfrag + kr1 * QW * 2);
+            nxt.bl = *reinterpret_cast<const u32x4*>(gfrag + GPART + kr1 * QW * 2);
+        }
+    }
+    mfma_group<Taps, dy>(acc, cur.a, cur.bh, cur.bl);
+    static_for<(NP > G ? (NP - G + NG - 1) / NG : 0)>([&](auto j) __attribute__((always_inline)) {
+        piece(std::integral_constant<int, G + decltype(j)::value * NG>{});
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    cur = nxt;
+}
+
+// The 3x3 kernel.  DYM / DXM: the masks of Taps3x3; the one instance is <7, 7> (nine taps).
 //
 // Schedule (round 5).  One wave per SIMD (144 accumulator registers), so nothing but this wave's own instruction stream can
 // fill the matrix pipe's shadow.  PMC of the round-4 kernel (profiles/r05_pmc/wgrad_256_256_at256.txt): 5.4 vector-ALU
@@ -122,237 +297,79 @@ __device__ __forceinline__ void store_slab_final(const f32x16 (&acc)[9], char* l
 //   * raw buffer loads: a position is a 32-bit offset = scalar tile origin + per-thread constant, and an out-of-image (or
 //     null-tile) position gets an offset past the end of the resource, for which the hardware returns zeros: no masks (12
 //     registers and 48 multiplies per tile), no 64-bit address arithmetic, no memory traffic for what is not there.
-template <int DYM, int DXM, bool SWAP>
+template <int DYM, int DXM>
 __global__ void __launch_bounds__(256, 1) wgrad_bf16_kernel(const Wg16Params p) {
-    constexpr int NDX = popc3(DXM), NDY = popc3(DYM), NT = NDY * NDX;
-    constexpr int NG = QH * NDY;                      // groups of the K loop
+    using Taps = Taps3x3<DYM, DXM>;
+    constexpr int NG = QH * popc3(DYM);               // groups of the K loop
+    static_assert(popc3(DYM) * popc3(DXM) == 9, "nine accumulators, and the final-layout epilogue is written for the nine-tap kernel");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wi = wave >> 1, wj = wave & 1;     // wave tile: a-channel rows 32*wi.., b-channel cols 32*wj..
+    const int wi = wave >> 1, wj = wave & 1;     // wave tile: ci rows 32*wi.., co cols 32*wj..
     const int h = lane >> 5, l31 = lane & 31;
-    const int ci0 = blockIdx.x * CT, co0 = blockIdx.y * CT, ks = blockIdx.z;      // a-channel / b-channel tile origins
+    const int ci0 = blockIdx.x * CT, co0 = blockIdx.y * CT, ks = blockIdx.z;
 
-    f32x16 acc[NT];
+    f32x16 acc[9];
 #pragma unroll
-    for (int t = 0; t < NT; ++t)
+    for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
     const int units = p.B * p.tiles_h * p.tiles_w;
     const int u_begin = (int)(((long long)units * ks) / p.ksplit), u_end = (int)(((long long)units * (ks + 1)) / p.ksplit);
 
-    // ---- staging.  x: 6 rows x 5 column groups (4 columns each, 20 >= 18) x 16 channel groups = 480 units, thread t
-    // owns units t and 256 + t (t < 224; the others repeat the last unit: same data, same addresses); g: 4 rows x 4 column
-    // groups x 16 channel groups = 256 units, one per thread.  Unit = 4 float4 loads (one per column, 4 channels each);
-    // nothing in fetch() consumes a loaded value, so the loads stay in flight under the MFMAs.
-    float4 rx[2][2][4], rg[2][4], sx[2][2], sg[2];       // [register set][...]
-    const int ux0 = tid, ux1 = min(tid + 256, XR * 5 * 16 - 1);
-    const int xq0 = ux0 & 15, xcg0 = (ux0 >> 4) % 5, xrow0 = (ux0 >> 4) / 5;
-    const int xq1 = ux1 & 15, xcg1 = (ux1 >> 4) % 5, xrow1 = (ux1 >> 4) / 5;
-    const int gq = tid & 15, gcg = (tid >> 4) & 3, grow = tid >> 6;
-    // LDS byte offsets of a unit's writes inside a stage, channel e = 0, hi part (+ 16 e XPITCH, + XPART: immediates).
-    // x unit (row, cg) holds patch columns 4cg .. 4cg+3.  Copy A keeps columns 0..15: an 8-byte write for cg <= 3; copy B
-    // keeps columns 2..17 at index col - 2: the pair's first dword goes to dword 2cg - 1 (cg >= 1), its second to dword
-    // 2cg (cg <= 3).  What a copy does not hold is written into the row's 16 pad bytes instead (no branch in a piece).
-    auto x_offsets = [&](int row, int cg, int q, int& oa, int& ob0, int& ob1) {
-        const int base = q * XPITCH;
-        oa = base + (cg <= 3 ? row * XROW + 8 * cg : 2 * XCOPY);
-        ob0 = base + (cg >= 1 ? XCOPY + row * XROW + 4 * (2 * cg - 1) : 2 * XCOPY + 8);
-        ob1 = base + (cg <= 3 ? XCOPY + row * XROW + 8 * cg : 2 * XCOPY + 12);
-    };
-    int oa0, ob00, ob10, oa1, ob01, ob11;
-    x_offsets(xrow0, xcg0, xq0, oa0, ob00, ob10);
-    x_offsets(xrow1, xcg1, xq1, oa1, ob01, ob11);
-    const int og = 2 * XPART + gq * GPITCH + (grow * QW + 4 * gcg) * 2;
+    // ---- staging: two x units and one g unit per thread.  Nothing in fetch() consumes a loaded value, so the loads stay in flight
+    // under the MFMAs.
+    float4 rx[2][2][4], rg[2][4], sx[2][2];       // [register set][...]
+    const int ux0 = tid, ux1 = min(tid + 256, XUNITS - 1);
+    const Unit xu[2] = {x_unit(ux0), x_unit(ux1)}, gu = g_unit(tid);
+    XOffsets xo[2];
+    x_offsets(xu[0], xo[0]);
+    x_offsets(xu[1], xo[1]);
+    const int og = 2 * XPART + g_offset(gu);
 
-    // Loads are raw buffer loads: the image of sample b is a buffer resource (4 scalar registers), a position is a 32-bit byte
-    // offset = (scalar tile origin) + (per-thread constant).
-    const int xoff0 = ((xrow0 * p.aW + 4 * xcg0) * p.aC + 4 * xq0) * 4, xoff1 = ((xrow1 * p.aW + 4 * xcg1) * p.aC + 4 * xq1) * 4;
-    const int goff = ((grow * p.bW + 4 * gcg) * p.bC + 4 * gq) * 4;
-    const unsigned abytes = (unsigned)(p.aH * p.aW * p.aC) * 4u, bbytes = (unsigned)(p.bH * p.bW * p.bC) * 4u;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.styles ? p.styles : p.a), 0, p.styles ? (unsigned)(p.B * (SWAP ? p.bC : p.aC)) * 4u : 0u, 0x00020000);
-    // (no styles: the resource is empty, the load returns zeros and `one` = 1 is added — a select on a uniform condition
-    // became a branch around the load, which costs hipcc its exact count of the loads in flight)
-    const float one = p.styles ? 0.f : 1.f;
-    constexpr unsigned OOB = 0xfffffff0u;
+    const int xoff[2] = {((xu[0].row * p.W + 4 * xu[0].cg) * p.Cin + 4 * xu[0].q) * 4, ((xu[1].row * p.W + 4 * xu[1].cg) * p.Cin + 4 * xu[1].q) * 4};
+    const int goff = ((gu.row * p.gW + 4 * gu.cg) * p.Cout + 4 * gu.q) * 4;
+    const unsigned abytes = (unsigned)(p.H * p.W * p.Cin) * 4u, bbytes = (unsigned)(p.gH * p.gW * p.Cout) * 4u;
+    const StyleSrc styles = style_src(p.styles, p.x, p.B * p.Cin);
     auto fetch = [&](int u, auto set_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value;
         const bool live = u < u_end;                         // (a null tile: every offset out of range)
-        const int uc = live ? u : u_end - 1;
-        const int tw = uc % p.tiles_w, th = (uc / p.tiles_w) % p.tiles_h, b = uc / (p.tiles_w * p.tiles_h);
-        const int m0 = th * QH, n0 = tw * QW;
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.a + (size_t)b * p.aH * p.aW * p.aC + ci0), 0, live ? abytes - 4u * ci0 : 0u, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.b + (size_t)b * p.bH * p.bW * p.bC + co0), 0, live ? bbytes - 4u * co0 : 0u, 0x00020000);
-        const int abase_t = (((m0 - 1) * p.aW + n0 - 1) * p.aC) * 4, bbase_t = ((m0 * p.bW + n0) * p.bC) * 4;      // scalar
+        const TileOrigin t = tile_origin(live ? u : u_end - 1, p.tiles_w, p.tiles_h);
+        const rsrc_t ra = image_rsrc(p.x + (size_t)t.b * p.H * p.W * p.Cin + ci0, live ? abytes - 4u * ci0 : 0u);
+        const rsrc_t rb = image_rsrc(p.g + (size_t)t.b * p.gH * p.gW * p.Cout + co0, live ? bbytes - 4u * co0 : 0u);
+        const int abase_t = (((t.m0 - 1) * p.W + t.n0 - 1) * p.Cin) * 4, bbase_t = ((t.m0 * p.gW + t.n0) * p.Cout) * 4;      // scalar
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const int row = k ? xrow1 : xrow0, cg = k ? xcg1 : xcg0, q = k ? xq1 : xq0;
-            const bool rowok = (unsigned)(m0 - 1 + row) < (unsigned)p.aH;
-            if constexpr (!SWAP) {
-                const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)((b * p.aC + ci0 + 4 * q) * 4), 0, 0));
-                sx[S][k] = make_float4(v.x + one, v.y + one, v.z + one, v.w + one);
-            }
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const bool ok = rowok && (unsigned)(n0 - 1 + 4 * cg + c) < (unsigned)p.aW;
-                const unsigned off = (unsigned)(abase_t + c * p.aC * 4 + (k ? xoff1 : xoff0));
-                rx[S][k][c] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? off : OOB, 0, 0));
-            }
+            const bool rowok = (unsigned)(t.m0 - 1 + xu[k].row) < (unsigned)p.H;
+            sx[S][k] = load_style(styles, t.b * p.Cin + ci0 + 4 * xu[k].q);
+            load_unit(rx[S][k], ra, rowok, t.n0 - 1 + 4 * xu[k].cg, p.W, abase_t, p.Cin, xoff[k]);
         }
-        {
-            const bool rowok = m0 + grow < p.bH;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const bool ok = rowok && n0 + 4 * gcg + c < p.bW;
-                const unsigned off = (unsigned)(bbase_t + c * p.bC * 4 + goff);
-                rg[S][c] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rb, ok ? off : OOB, 0, 0));
-            }
-            if constexpr (SWAP) {
-                const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)((b * p.bC + co0 + 4 * gq) * 4), 0, 0));
-                sg[S] = make_float4(v.x + one, v.y + one, v.z + one, v.w + one);
-            }
-        }
+        load_unit(rg[S], rb, t.m0 + gu.row < p.gH, t.n0 + 4 * gu.cg, p.gW, bbase_t, p.Cout, goff);
     };
     // piece P of the conversion of register set S into LDS stage `buf`: P = 0..3 channel e of x unit 0, 4..7 of x unit 1,
-    // 8..11 of the g unit.  One split_run + its LDS writes (x: 8-byte to copy A, two 4-byte to copy B, per part).
+    // 8..11 of the g unit
     auto commit_piece = [&](int buf, auto set_tag, auto piece_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(set_tag)::value, P = decltype(piece_tag)::value, e = P & 3;
         char* base = lds + buf * BUF;
-        uint2 hi, lo;
-        if constexpr (P < 8) {
-            constexpr int k = P >> 2;
-            const float* f0 = &rx[S][k][0].x; const float* f1 = &rx[S][k][1].x;
-            const float* f2 = &rx[S][k][2].x; const float* f3 = &rx[S][k][3].x;
-            if constexpr (!SWAP) {
-                const float sv = e == 0 ? sx[S][k].x : e == 1 ? sx[S][k].y : e == 2 ? sx[S][k].z : sx[S][k].w;
-                split_run(f0[e] * sv, f1[e] * sv, f2[e] * sv, f3[e] * sv, hi, lo);
-            } else {
-                split_run(f0[e], f1[e], f2[e], f3[e], hi, lo);
-            }
-            char* row = base + 16 * e * XPITCH;
-            *reinterpret_cast<uint2*>(row + (k ? oa1 : oa0)) = hi;
-            *reinterpret_cast<uint2*>(row + (k ? oa1 : oa0) + XPART) = lo;
-            *reinterpret_cast<unsigned*>(row + (k ? ob01 : ob00)) = hi.x;
-            *reinterpret_cast<unsigned*>(row + (k ? ob11 : ob10)) = hi.y;
-            *reinterpret_cast<unsigned*>(row + (k ? ob01 : ob00) + XPART) = lo.x;
-            *reinterpret_cast<unsigned*>(row + (k ? ob11 : ob10) + XPART) = lo.y;
-        } else {
-            const float* f0 = &rg[S][0].x; const float* f1 = &rg[S][1].x; const float* f2 = &rg[S][2].x; const float* f3 = &rg[S][3].x;
-            if constexpr (SWAP) {
-                const float sv = e == 0 ? sg[S].x : e == 1 ? sg[S].y : e == 2 ? sg[S].z : sg[S].w;
-                split_run(f0[e] * sv, f1[e] * sv, f2[e] * sv, f3[e] * sv, hi, lo);
-            } else {
-                split_run(f0[e], f1[e], f2[e], f3[e], hi, lo);
-            }
-            char* dst = base + og + 16 * e * GPITCH;
-            *reinterpret_cast<uint2*>(dst) = hi;
-            *reinterpret_cast<uint2*>(dst + GPART) = lo;
-        }
+        if constexpr (P < 8) commit_x_piece<e, BUF>(lds, buf, xo[P >> 2], rx[S][P >> 2], chan<e>(sx[S][P >> 2]));
+        else commit_g_piece<e>(base + og, rg[S]);
     };
     auto commit_all = [&](int buf, auto set_tag) __attribute__((always_inline)) {
-        commit_piece(buf, set_tag, std::integral_constant<int, 0>{});  commit_piece(buf, set_tag, std::integral_constant<int, 1>{});
-        commit_piece(buf, set_tag, std::integral_constant<int, 2>{});  commit_piece(buf, set_tag, std::integral_constant<int, 3>{});
-        commit_piece(buf, set_tag, std::integral_constant<int, 4>{});  commit_piece(buf, set_tag, std::integral_constant<int, 5>{});
-        commit_piece(buf, set_tag, std::integral_constant<int, 6>{});  commit_piece(buf, set_tag, std::integral_constant<int, 7>{});
-        commit_piece(buf, set_tag, std::integral_constant<int, 8>{});  commit_piece(buf, set_tag, std::integral_constant<int, 9>{});
-        commit_piece(buf, set_tag, std::integral_constant<int, 10>{}); commit_piece(buf, set_tag, std::integral_constant<int, 11>{});
+        static_for<12>([&](auto piece_tag) __attribute__((always_inline)) { commit_piece(buf, set_tag, piece_tag); });
     };
 
-    // per-lane fragment bases (bytes inside a stage): A = LDS row 32 wi + l31, columns 8h..; B = LDS row 32 wj + l31
-    const int abase = (32 * wi + l31) * XPITCH + 8 * h * 2;
-    const int bbase = 2 * XPART + (32 * wj + l31) * GPITCH + 8 * h * 2;
+    const int abase = frag_base(wi, l31, h, XPITCH), bbase = 2 * XPART + frag_base(wj, l31, h, GPITCH);
 
-    // fragments of one group as they come out of LDS: copy A / copy B window of the patch row, hi and lo part
-    struct Raw { u32x4 ha, hb, la, lb; };
-    auto read_a = [&](const char* st, int prow) __attribute__((always_inline)) {
-        const char* ar = st + abase + prow * XROW;
-        Raw r;
-        r.ha = *reinterpret_cast<const u32x4*>(ar);
-        r.hb = *reinterpret_cast<const u32x4*>(ar + XCOPY);
-        r.la = *reinterpret_cast<const u32x4*>(ar + XPART);
-        r.lb = *reinterpret_cast<const u32x4*>(ar + XPART + XCOPY);
-        return r;
-    };
-    // the MFMAs of one group: K step kr (tile row), patch row kr + dy
-    auto mfmas = [&](const Raw& w, auto dy_tag, const u32x4& bh, const u32x4& bl) __attribute__((always_inline)) {
-        constexpr int dy = decltype(dy_tag)::value;
-        u32x4 ah[3], al[3];                       // the three dx windows (start column 8h + dx)
-        ah[0] = w.ha; al[0] = w.la; ah[2] = w.hb; al[2] = w.lb;
-        if constexpr ((DXM >> 1) & 1) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {         // columns 8h+1+2e, 8h+2+2e = high half of A's dword e, low half of B's
-                ah[1][e] = __builtin_amdgcn_alignbit(w.hb[e], w.ha[e], 16);
-                al[1][e] = __builtin_amdgcn_alignbit(w.lb[e], w.la[e], 16);
-            }
-        }
-        constexpr int trow = rank3(DYM, dy) * NDX;    // first tap slot of this row
-        // product-major: the three MFMAs of one accumulator are up to two other MFMAs apart
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx)
-            if ((DXM >> dx) & 1)
-                acc[trow + rank3(DXM, dx)] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[dx]), __builtin_bit_cast(bf16x8, bh), acc[trow + rank3(DXM, dx)], 0, 0, 0);
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx)
-            if ((DXM >> dx) & 1)
-                acc[trow + rank3(DXM, dx)] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, al[dx]), __builtin_bit_cast(bf16x8, bh), acc[trow + rank3(DXM, dx)], 0, 0, 0);
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx)
-            if ((DXM >> dx) & 1)
-                acc[trow + rank3(DXM, dx)] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ah[dx]), __builtin_bit_cast(bf16x8, bl), acc[trow + rank3(DXM, dx)], 0, 0, 0);
-    };
-    // the pieces of the next tile's conversion that ride in group G (12 pieces over NG groups: piece P goes to group P % NG)
-    auto pieces_of = [&](int buf, auto set_tag, auto g_tag) __attribute__((always_inline)) {
-        constexpr int G = decltype(g_tag)::value;
-        if constexpr (G < 12) commit_piece(buf, set_tag, std::integral_constant<int, (G < 12 ? G : 0)>{});
-        if constexpr (G + NG < 12) commit_piece(buf, set_tag, std::integral_constant<int, (G + NG < 12 ? G + NG : 0)>{});
-        if constexpr (G + 2 * NG < 12) commit_piece(buf, set_tag, std::integral_constant<int, (G + 2 * NG < 12 ? G + 2 * NG : 0)>{});
-    };
-    // K loop of the tile staged in `cur`, groups in (kr, dy) order, while register set S (the next tile) is converted into
-    // the other stage
-    auto tile = [&](int cur, auto set_tag) __attribute__((always_inline)) {
-        const char* st = lds + cur * BUF;
-        Raw cur_a = read_a(st, nth3(DYM, 0));
-        u32x4 bh = *reinterpret_cast<const u32x4*>(st + bbase);
-        u32x4 bl = *reinterpret_cast<const u32x4*>(st + bbase + GPART);
-        auto step = [&](auto g_tag) __attribute__((always_inline)) {
-            constexpr int G = decltype(g_tag)::value;
-            constexpr int kr = G / NDY, dy = nth3(DYM, G % NDY);
-            constexpr int G1 = G + 1, kr1 = G1 / NDY, dy1 = nth3(DYM, G1 % NDY);
-            Raw nxt = cur_a;
-            u32x4 nbh = bh, nbl = bl;
-            if constexpr (G1 < NG) {
-                nxt = read_a(st, kr1 + dy1);
-                if constexpr (kr1 != kr) {
-                    nbh = *reinterpret_cast<const u32x4*>(st + bbase + kr1 * QW * 2);
-                    nbl = *reinterpret_cast<const u32x4*>(st + bbase + GPART + kr1 * QW * 2);
-                }
-            }
-            mfmas(cur_a, std::integral_constant<int, dy>{}, bh, bl);
-            pieces_of(cur ^ 1, set_tag, g_tag);
-            __builtin_amdgcn_sched_barrier(0);
-            cur_a = nxt; bh = nbh; bl = nbl;
-        };
-        step(std::integral_constant<int, 0>{});
-        if constexpr (NG > 1) step(std::integral_constant<int, (NG > 1 ? 1 : 0)>{});
-        if constexpr (NG > 2) step(std::integral_constant<int, (NG > 2 ? 2 : 0)>{});
-        if constexpr (NG > 3) step(std::integral_constant<int, (NG > 3 ? 3 : 0)>{});
-        if constexpr (NG > 4) step(std::integral_constant<int, (NG > 4 ? 4 : 0)>{});
-        if constexpr (NG > 5) step(std::integral_constant<int, (NG > 5 ? 5 : 0)>{});
-        if constexpr (NG > 6) step(std::integral_constant<int, (NG > 6 ? 6 : 0)>{});
-        if constexpr (NG > 7) step(std::integral_constant<int, (NG > 7 ? 7 : 0)>{});
-        if constexpr (NG > 8) step(std::integral_constant<int, (NG > 8 ? 8 : 0)>{});
-        if constexpr (NG > 9) step(std::integral_constant<int, (NG > 9 ? 9 : 0)>{});
-        if constexpr (NG > 10) step(std::integral_constant<int, (NG > 10 ? 10 : 0)>{});
-        if constexpr (NG > 11) step(std::integral_constant<int, (NG > 11 ? 11 : 0)>{});
-    };
-    // phase: tile u sits in stage S (converted from register set S, which is free again); register set 1 - S holds tile u + 1
+    // phase: tile u sits in stage S (converted from register set S, which is free again); register set 1 - S holds tile u + 1 and
+    // is converted into the other stage inside the K loop (12 pieces over NG groups: piece P rides in group P % NG); groups in
+    // (kr, dy) order
     auto phase = [&](int u, auto s_tag) __attribute__((always_inline)) {
         constexpr int S = decltype(s_tag)::value;
         fetch(u + 2, s_tag);
-        tile(S, std::integral_constant<int, 1 - S>{});
+        const char* st = lds + S * BUF;
+        Group cur = read_group0<Taps>(st, abase, st + bbase);
+        auto piece = [&](auto piece_tag) __attribute__((always_inline)) { commit_piece(S ^ 1, std::integral_constant<int, 1 - S>{}, piece_tag); };
+        static_for<NG>([&](auto g) __attribute__((always_inline)) { group_step<Taps, decltype(g)::value, 12>(acc, cur, st, abase, st + bbase, piece); });
         __syncthreads();
     };
 
@@ -364,9 +381,7 @@ __global__ void __launch_bounds__(256, 1) wgrad_bf16_kernel(const Wg16Params p) 
         phase(u, std::integral_constant<int, 0>{});
         phase(u + 1, std::integral_constant<int, 1>{});
     }
-    // ---- slab [Cout][Cin][9] (the parameter layout): C/D layout row = (r&3) + 8*(r>>2) + 4*h (operand-a channel = ci),
-    // col = lane&31 (operand-b channel = co)
-    static_assert(NT == 9 && !SWAP, "the final-layout epilogue is written for the nine-tap, un-swapped kernel");
+    // ---- slab [Cout][Cin][9] (the parameter layout): C/D layout row = (r&3) + 8*(r>>2) + 4*h (ci), col = lane&31 (co)
     store_slab_final(acc, lds, p.slabs + (size_t)ks * 9 * p.Cin * p.Cout, p.Cin, ci0, co0, wi, wj, h, l31, tid);
 }
 
@@ -388,6 +403,7 @@ struct WgUpParams {
     int B, H, W, Cin, Cout, tiles_h, tiles_w, ksplit;
 };
 constexpr int UBX = 2 * XPART, UBG = 2 * GPART;               // one x stage (hi, lo), one g stage
+constexpr int up_parity(int J) { return J == 0 ? 3 : J == 1 ? 1 : J == 2 ? 2 : 0; }      // phase J of a tile -> parity image 2 p + q
 
 __global__ void __launch_bounds__(256, 1) wgrad_up_bf16_kernel(const WgUpParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];     // [x stage 0][x stage 1][g stage 0][g stage 1]
@@ -407,172 +423,68 @@ __global__ void __launch_bounds__(256, 1) wgrad_up_bf16_kernel(const WgUpParams 
     const int u_begin = (int)(((long long)units * ks) / p.ksplit), u_end = (int)(((long long)units * (ks + 1)) / p.ksplit);
 
     float4 rx[2][4], sx[2], rg[4][4];                          // x: one register set (two units); g: [set = phase of the tile][column]
-    const int ux0 = tid, ux1 = min(tid + 256, XR * 5 * 16 - 1);
-    const int xq0 = ux0 & 15, xcg0 = (ux0 >> 4) % 5, xrow0 = (ux0 >> 4) / 5;
-    const int xq1 = ux1 & 15, xcg1 = (ux1 >> 4) % 5, xrow1 = (ux1 >> 4) / 5;
-    const int gq = tid & 15, gcg = (tid >> 4) & 3, grow = tid >> 6;
-    auto x_offsets = [&](int row, int cg, int q, int& oa, int& ob0, int& ob1) {      // (as in the 3x3 kernel)
-        const int base = q * XPITCH;
-        oa = base + (cg <= 3 ? row * XROW + 8 * cg : 2 * XCOPY);
-        ob0 = base + (cg >= 1 ? XCOPY + row * XROW + 4 * (2 * cg - 1) : 2 * XCOPY + 8);
-        ob1 = base + (cg <= 3 ? XCOPY + row * XROW + 8 * cg : 2 * XCOPY + 12);
-    };
-    int oa0, ob00, ob10, oa1, ob01, ob11;
-    x_offsets(xrow0, xcg0, xq0, oa0, ob00, ob10);
-    x_offsets(xrow1, xcg1, xq1, oa1, ob01, ob11);
-    const int og = gq * GPITCH + (grow * QW + 4 * gcg) * 2;
+    const int ux0 = tid, ux1 = min(tid + 256, XUNITS - 1);
+    const Unit xu[2] = {x_unit(ux0), x_unit(ux1)}, gu = g_unit(tid);
+    XOffsets xo[2];
+    x_offsets(xu[0], xo[0]);
+    x_offsets(xu[1], xo[1]);
+    const int og = g_offset(gu);
 
-    const int xoff0 = ((xrow0 * p.W + 4 * xcg0) * p.Cin + 4 * xq0) * 4, xoff1 = ((xrow1 * p.W + 4 * xcg1) * p.Cin + 4 * xq1) * 4;
-    const int goff = ((grow * gW + 4 * gcg) * p.Cout + 4 * gq) * 4;
+    const int xoff[2] = {((xu[0].row * p.W + 4 * xu[0].cg) * p.Cin + 4 * xu[0].q) * 4, ((xu[1].row * p.W + 4 * xu[1].cg) * p.Cin + 4 * xu[1].q) * 4};
+    const int goff = ((gu.row * gW + 4 * gu.cg) * p.Cout + 4 * gu.q) * 4;
     const unsigned xbytes = (unsigned)(p.H * p.W * p.Cin) * 4u, gbytes = (unsigned)(gH * gW * p.Cout) * 4u;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(p.styles ? p.styles : p.x), 0, p.styles ? (unsigned)(p.B * p.Cin) * 4u : 0u, 0x00020000);
-    const float one = p.styles ? 0.f : 1.f;
-    constexpr unsigned OOB = 0xfffffff0u;
+    const StyleSrc styles = style_src(p.styles, p.x, p.B * p.Cin);
     const size_t par_stride = (size_t)p.B * gH * gW * p.Cout;        // floats between parity images
 
-    auto tile_origin = [&](int u, int& b, int& m0, int& n0) __attribute__((always_inline)) {
-        const int tw = u % p.tiles_w, th = (u / p.tiles_w) % p.tiles_h;
-        b = u / (p.tiles_w * p.tiles_h); m0 = th * QH; n0 = tw * QW;
-    };
     // x patch of tile u: rows m0-1 .. m0+4, columns n0-1 .. n0+18 (5 column groups of 4)
     auto fetch_x = [&](int u) __attribute__((always_inline)) {
         const bool live = u < u_end;
-        int b, m0, n0;
-        tile_origin(live ? u : u_end - 1, b, m0, n0);
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.x + (size_t)b * p.H * p.W * p.Cin + ci0), 0, live ? xbytes - 4u * ci0 : 0u, 0x00020000);
-        const int base_t = (((m0 - 1) * p.W + n0 - 1) * p.Cin) * 4;
+        const TileOrigin t = tile_origin(live ? u : u_end - 1, p.tiles_w, p.tiles_h);
+        const rsrc_t ra = image_rsrc(p.x + (size_t)t.b * p.H * p.W * p.Cin + ci0, live ? xbytes - 4u * ci0 : 0u);
+        const int base_t = (((t.m0 - 1) * p.W + t.n0 - 1) * p.Cin) * 4;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-            const int row = k ? xrow1 : xrow0, cg = k ? xcg1 : xcg0, q = k ? xq1 : xq0;
             // (shifts -1 / 0: five patch rows; a partial ci tile — Cin = 32 — loads zeros for the channels it does not have)
-            const bool rowok = (unsigned)(m0 - 1 + row) < (unsigned)p.H && row < XR - 1 && ci0 + 4 * q < p.Cin;
-            const float4 v = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, (unsigned)((b * p.Cin + ci0 + 4 * q) * 4), 0, 0));
-            sx[k] = make_float4(v.x + one, v.y + one, v.z + one, v.w + one);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const bool ok = rowok && (unsigned)(n0 - 1 + 4 * cg + c) < (unsigned)p.W;
-                const unsigned off = (unsigned)(base_t + c * p.Cin * 4 + (k ? xoff1 : xoff0));
-                rx[k][c] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(ra, ok ? off : OOB, 0, 0));
-            }
+            const bool rowok = (unsigned)(t.m0 - 1 + xu[k].row) < (unsigned)p.H && xu[k].row < XR - 1 && ci0 + 4 * xu[k].q < p.Cin;
+            sx[k] = load_style(styles, t.b * p.Cin + ci0 + 4 * xu[k].q);
+            load_unit(rx[k], ra, rowok, t.n0 - 1 + 4 * xu[k].cg, p.W, base_t, p.Cin, xoff[k]);
         }
     };
-    // gradient tile of (tile u, parity PAR) into register set S
-    auto fetch_g = [&](int u, auto par_tag, auto set_tag) __attribute__((always_inline)) {
-        constexpr int PAR = decltype(par_tag)::value, S = decltype(set_tag)::value;
+    // gradient tile of (tile u, phase J) into register set J
+    auto fetch_g = [&](int u, auto j_tag) __attribute__((always_inline)) {
+        constexpr int PAR = up_parity(decltype(j_tag)::value), S = decltype(j_tag)::value;
         const bool live = u < u_end;
-        int b, m0, n0;
-        tile_origin(live ? u : u_end - 1, b, m0, n0);
-        const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<float*>(p.g + PAR * par_stride + (size_t)b * gH * gW * p.Cout + co0), 0, live ? gbytes - 4u * co0 : 0u, 0x00020000);
-        const int base_t = ((m0 * gW + n0) * p.Cout) * 4;
-        const bool rowok = m0 + grow < gH;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const bool ok = rowok && n0 + 4 * gcg + c < gW;
-            const unsigned off = (unsigned)(base_t + c * p.Cout * 4 + goff);
-            rg[S][c] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rb, ok ? off : OOB, 0, 0));
-        }
+        const TileOrigin t = tile_origin(live ? u : u_end - 1, p.tiles_w, p.tiles_h);
+        const rsrc_t rb = image_rsrc(p.g + PAR * par_stride + (size_t)t.b * gH * gW * p.Cout + co0, live ? gbytes - 4u * co0 : 0u);
+        load_unit(rg[S], rb, t.m0 + gu.row < gH, t.n0 + 4 * gu.cg, gW, ((t.m0 * gW + t.n0) * p.Cout) * 4, p.Cout, goff);
     };
     // conversion pieces: x piece P = 0..7 (unit P >> 2, channel P & 3) into x stage `xs`; g piece e of set S into g stage `gs`
     auto x_piece = [&](int xs, auto piece_tag) __attribute__((always_inline)) {
-        constexpr int P = decltype(piece_tag)::value, e = P & 3, k = P >> 2;
-        const float* f0 = &rx[k][0].x; const float* f1 = &rx[k][1].x; const float* f2 = &rx[k][2].x; const float* f3 = &rx[k][3].x;
-        const float sv = e == 0 ? sx[k].x : e == 1 ? sx[k].y : e == 2 ? sx[k].z : sx[k].w;
-        uint2 hi, lo;
-        split_run(f0[e] * sv, f1[e] * sv, f2[e] * sv, f3[e] * sv, hi, lo);
-        char* row = lds + xs * UBX + 16 * e * XPITCH;
-        *reinterpret_cast<uint2*>(row + (k ? oa1 : oa0)) = hi;
-        *reinterpret_cast<uint2*>(row + (k ? oa1 : oa0) + XPART) = lo;
-        *reinterpret_cast<unsigned*>(row + (k ? ob01 : ob00)) = hi.x;
-        *reinterpret_cast<unsigned*>(row + (k ? ob11 : ob10)) = hi.y;
-        *reinterpret_cast<unsigned*>(row + (k ? ob01 : ob00) + XPART) = lo.x;
-        *reinterpret_cast<unsigned*>(row + (k ? ob11 : ob10) + XPART) = lo.y;
+        constexpr int P = decltype(piece_tag)::value;
+        commit_x_piece<(P & 3), UBX>(lds, xs, xo[P >> 2], rx[P >> 2], chan<(P & 3)>(sx[P >> 2]));
     };
     auto g_piece = [&](int gs, auto set_tag, auto e_tag) __attribute__((always_inline)) {
-        constexpr int S = decltype(set_tag)::value, e = decltype(e_tag)::value;
-        const float* f0 = &rg[S][0].x; const float* f1 = &rg[S][1].x; const float* f2 = &rg[S][2].x; const float* f3 = &rg[S][3].x;
-        uint2 hi, lo;
-        split_run(f0[e], f1[e], f2[e], f3[e], hi, lo);
-        char* dst = lds + 2 * UBX + gs * UBG + og + 16 * e * GPITCH;
-        *reinterpret_cast<uint2*>(dst) = hi;
-        *reinterpret_cast<uint2*>(dst + GPART) = lo;
+        commit_g_piece<decltype(e_tag)::value>(lds + 2 * UBX + gs * UBG + og, rg[decltype(set_tag)::value]);
     };
 
-    const int abase = (32 * wi + l31) * XPITCH + 8 * h * 2;
-    const int bbase = (32 * wj + l31) * GPITCH + 8 * h * 2;
-    struct Raw { u32x4 ha, hb, la, lb; };
-    auto read_a = [&](const char* st, int prow) __attribute__((always_inline)) {
-        const char* ar = st + abase + prow * XROW;
-        Raw r;
-        r.ha = *reinterpret_cast<const u32x4*>(ar);
-        r.hb = *reinterpret_cast<const u32x4*>(ar + XCOPY);
-        r.la = *reinterpret_cast<const u32x4*>(ar + XPART);
-        r.lb = *reinterpret_cast<const u32x4*>(ar + XPART + XCOPY);
-        return r;
-    };
+    const int abase = frag_base(wi, l31, h, XPITCH), bbase = frag_base(wj, l31, h, GPITCH);
 
-    // one phase: K loop of (x stage xs, g stage J & 1) for parity PAR = (PP, PQ); riding along: the four g pieces of the NEXT
-    // phase (register set (J + 1) & 1 -> g stage (J + 1) & 1) and, in the last two phases of a tile, four x pieces of the next tile
+    // one phase: K loop of (x stage xs, g stage J & 1) for the parity image of phase J; riding along: the four g pieces of the NEXT
+    // phase (register set (J + 1) & 3 -> g stage (J + 1) & 1) and, in the last phase of a tile, the eight x pieces of the next tile
     auto phase = [&](int xs, auto j_tag) __attribute__((always_inline)) {
         constexpr int J = decltype(j_tag)::value;                      // phase of the tile: parities in the order 3, 1, 2, 0
-        constexpr int PAR = J == 0 ? 3 : J == 1 ? 1 : J == 2 ? 2 : 0, PP = PAR >> 1, PQ = PAR & 1;
-        constexpr int DYM = PP ? 2 : 3, DXM = PQ ? 2 : 3, NDY = popc3(DYM), NG = QH * NDY;
+        using Taps = TapsUp<(up_parity(J) >> 1), (up_parity(J) & 1)>;
+        constexpr int NG = QH * popc3(Taps::dym);
         constexpr int NP = J == 3 ? 12 : 4;                            // pieces that ride in this phase (the 4-tap phase also converts x)
         const char* xst = lds + xs * UBX;
         const char* gst = lds + 2 * UBX + (J & 1) * UBG;
-        Raw cur_a = read_a(xst, nth3(DYM, 0));
-        u32x4 bh = *reinterpret_cast<const u32x4*>(gst + bbase);
-        u32x4 bl = *reinterpret_cast<const u32x4*>(gst + bbase + GPART);
+        Group cur = read_group0<Taps>(xst, abase, gst + bbase);
         auto piece = [&](auto k_tag) __attribute__((always_inline)) {
             constexpr int K = decltype(k_tag)::value;
-            if constexpr (K < 4) g_piece((J + 1) & 1, std::integral_constant<int, (J + 1) & 3>{}, std::integral_constant<int, (K < 4 ? K : 0)>{});
-            else x_piece(xs ^ 1, std::integral_constant<int, (K >= 4 ? K - 4 : 0)>{});
+            if constexpr (K < 4) g_piece((J + 1) & 1, std::integral_constant<int, (J + 1) & 3>{}, k_tag);
+            else x_piece(xs ^ 1, std::integral_constant<int, K - 4>{});
         };
-        auto step = [&](auto g_tag) __attribute__((always_inline)) {
-            constexpr int G = decltype(g_tag)::value;
-            constexpr int kr = G / NDY, dy = nth3(DYM, G % NDY);
-            constexpr int G1 = G + 1, kr1 = G1 / NDY, dy1 = nth3(DYM, G1 % NDY);
-            Raw nxt = cur_a;
-            u32x4 nbh = bh, nbl = bl;
-            if constexpr (G1 < NG) {
-                nxt = read_a(xst, kr1 + dy1);
-                if constexpr (kr1 != kr) {
-                    nbh = *reinterpret_cast<const u32x4*>(gst + bbase + kr1 * QW * 2);
-                    nbl = *reinterpret_cast<const u32x4*>(gst + bbase + GPART + kr1 * QW * 2);
-                }
-            }
-            {
-                u32x4 ah[2], al[2];                                    // windows dx = 0 (shift -1: copy A) and dx = 1 (shift 0)
-                ah[0] = cur_a.ha; al[0] = cur_a.la;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    ah[1][e] = __builtin_amdgcn_alignbit(cur_a.hb[e], cur_a.ha[e], 16);
-                    al[1][e] = __builtin_amdgcn_alignbit(cur_a.lb[e], cur_a.la[e], 16);
-                }
-                constexpr int ky = PP + 2 * (1 - dy);                   // dy = 1: shift 0 -> sy = 0; dy = 0: shift -1 -> sy = 1
-#pragma unroll
-                for (int pr = 0; pr < 3; ++pr)                          // products hi.hi, lo.hi, hi.lo
-#pragma unroll
-                    for (int dx = 0; dx < 2; ++dx)
-                        if ((DXM >> dx) & 1) {
-                            const int t = 3 * ky + PQ + 2 * (1 - dx);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, pr == 1 ? al[dx] : ah[dx]),
-                                                                             __builtin_bit_cast(bf16x8, pr == 2 ? bl : bh), acc[t], 0, 0, 0);
-                        }
-            }
-            if constexpr (G < NP) piece(std::integral_constant<int, (G < NP ? G : 0)>{});
-            if constexpr (G + NG < NP) piece(std::integral_constant<int, (G + NG < NP ? G + NG : 0)>{});
-            __builtin_amdgcn_sched_barrier(0);
-            cur_a = nxt; bh = nbh; bl = nbl;
-        };
-        step(std::integral_constant<int, 0>{}); step(std::integral_constant<int, 1>{});
-        step(std::integral_constant<int, 2>{}); step(std::integral_constant<int, 3>{});
-        if constexpr (NG > 4) {
-            step(std::integral_constant<int, (NG > 4 ? 4 : 0)>{}); step(std::integral_constant<int, (NG > 4 ? 5 : 0)>{});
-            step(std::integral_constant<int, (NG > 4 ? 6 : 0)>{}); step(std::integral_constant<int, (NG > 4 ? 7 : 0)>{});
-        }
+        static_for<NG>([&](auto g) __attribute__((always_inline)) { group_step<Taps, decltype(g)::value, NP>(acc, cur, xst, abase, gst + bbase, piece); });
         __syncthreads();
     };
 
@@ -581,31 +493,18 @@ __global__ void __launch_bounds__(256, 1) wgrad_up_bf16_kernel(const WgUpParams 
     // ahead: with two sets / two phases ahead (first version) a phase of 12 - 24 MFMAs was over before its successor's loads had
     // landed, SQ_WAIT_ANY 43 % of the wave cycles, MFMA pipe 0.27 busy — and converted inside the phase before its own.
     fetch_x(u_begin);
-    fetch_g(u_begin, std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{});
-    fetch_g(u_begin, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-    fetch_g(u_begin, std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-    fetch_g(u_begin, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
-    x_piece(0, std::integral_constant<int, 0>{}); x_piece(0, std::integral_constant<int, 1>{});
-    x_piece(0, std::integral_constant<int, 2>{}); x_piece(0, std::integral_constant<int, 3>{});
-    x_piece(0, std::integral_constant<int, 4>{}); x_piece(0, std::integral_constant<int, 5>{});
-    x_piece(0, std::integral_constant<int, 6>{}); x_piece(0, std::integral_constant<int, 7>{});
-    g_piece(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
-    g_piece(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-    g_piece(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
-    g_piece(0, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
+    static_for<4>([&](auto j_tag) __attribute__((always_inline)) { fetch_g(u_begin, j_tag); });
+    static_for<8>([&](auto piece_tag) __attribute__((always_inline)) { x_piece(0, piece_tag); });
+    static_for<4>([&](auto e_tag) __attribute__((always_inline)) { g_piece(0, std::integral_constant<int, 0>{}, e_tag); });
     __syncthreads();
     int xs = 0;
     for (int u = u_begin; u < u_end; ++u) {
         // (set J held tile u's phase-J tile, converted during phase J - 1: free when phase J starts)
         fetch_x(u + 1);                                                                          // converted inside phase 3
-        fetch_g(u + 1, std::integral_constant<int, 3>{}, std::integral_constant<int, 0>{});
-        phase(xs, std::integral_constant<int, 0>{});
-        fetch_g(u + 1, std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{});
-        phase(xs, std::integral_constant<int, 1>{});
-        fetch_g(u + 1, std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
-        phase(xs, std::integral_constant<int, 2>{});
-        fetch_g(u + 1, std::integral_constant<int, 0>{}, std::integral_constant<int, 3>{});
-        phase(xs, std::integral_constant<int, 3>{});
+        static_for<4>([&](auto j_tag) __attribute__((always_inline)) {
+            fetch_g(u + 1, j_tag);
+            phase(xs, j_tag);
+        });
         xs ^= 1;
     }
     store_slab_final(acc, lds, p.slabs + (size_t)ks * 9 * p.Cin * p.Cout, p.Cin, ci0, co0, wi, wj, h, l31, tid);
@@ -627,27 +526,26 @@ int launch_wgrad_up_bf16(const HfagpWgradArgs* a, hipStream_t s) {
     return check_launch("conv_wgrad (up-sampling conv, split bf16)");
 }
 
-template <int DYM, int DXM, bool SWAP>
+template <int DYM, int DXM>
 static int launch_wg16(const Wg16Params& p, dim3 grid, hipStream_t s) {
     const size_t lds = 2 * BUF > EPI_BYTES ? (size_t)(2 * BUF) : (size_t)EPI_BYTES;
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<DYM, DXM, SWAP>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_bf16_kernel<DYM, DXM>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
     }
-    wgrad_bf16_kernel<DYM, DXM, SWAP><<<grid, 256, lds, s>>>(p);
+    wgrad_bf16_kernel<DYM, DXM><<<grid, 256, lds, s>>>(p);
     return check_launch("conv_wgrad (split bf16)");
 }
 
-// host side (called by hfagp_conv_wgrad when Cin, Cout are multiples of 64): the 3x3 conv ...
+// host side (called by hfagp_conv_wgrad where wgrad_split16 holds, wgrad_plan.h): the 3x3 conv
 int launch_wgrad3x3_bf16(const HfagpWgradArgs* a, hipStream_t s) {
     Wg16Params p{};
-    p.a = a->x; p.b = a->g; p.styles = a->styles; p.slabs = a->workspace;
-    p.B = a->B; p.aH = a->H; p.aW = a->W; p.aC = a->Cin; p.bH = a->H; p.bW = a->W; p.bC = a->Cout;
-    p.Cin = a->Cin; p.Cout = a->Cout; p.ksplit = a->ksplit;
+    p.x = a->x; p.g = a->g; p.styles = a->styles; p.slabs = a->workspace;
+    p.B = a->B; p.H = a->H; p.W = a->W; p.gH = a->H; p.gW = a->W; p.Cin = a->Cin; p.Cout = a->Cout; p.ksplit = a->ksplit;
     p.tiles_h = (a->H + QH - 1) / QH; p.tiles_w = (a->W + QW - 1) / QW;
-    return launch_wg16<7, 7, false>(p, dim3(a->Cin / CT, a->Cout / CT, a->ksplit), s);
+    return launch_wg16<7, 7>(p, dim3(a->Cin / CT, a->Cout / CT, a->ksplit), s);
 }
 
 }  // namespace hfagp

@@ -726,6 +726,7 @@ typedef struct {
     int32_t ksplit;           /* number of split-K slabs over (b, position tiles); >= 1 */
     int32_t precision;        /* HFAGP_PREC_F32 (exact fp32 MFMA) or HFAGP_PREC_BF16X3: modes 0 and 1 with Cin, Cout    */
                               /* multiples of 64 (mode 1 also Cin = 32) then run on the split-bf16 MFMA kernels, the rest fp32 */
+                              /* (the one predicate: wgrad_split16, csrc/wgrad_plan.h; hfagp_wgrad_ksplit follows it)          */
     int32_t accumulate;       /* ABI 11: 1 = dweight += (the parameter's .grad slice: no separate add pass), 0 = overwrite */
     int32_t dd_stride;        /* ABI 12: row stride of dd in elements (0 = Cout): row 3 of hfagp_pointwise_bwd's sums without a copy */
 } HfagpWgradArgs;

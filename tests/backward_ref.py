@@ -478,6 +478,11 @@ WGRAD_SHAPES = (                      # (B, H, W, Cin, Cout), precisions, modes
     ((2, 9, 5, 24, 96), ("fp32",), ("3x3", "up", "1x1")),
     ((2, 5, 3, 64, 64), ("fp32", "bf16x3"), ("3x3", "up", "1x1")),
     ((1, 8, 9, 32, 128), ("fp32", "bf16x3"), ("up",)),
+    # two samples, two position tiles each way with a ragged last row and column, two ci blocks (ci0 != 0 in the buffer resources
+    # and in the slab epilogue)
+    ((2, 5, 18, 128, 64), ("fp32", "bf16x3"), ("3x3", "up")),
+    # Cin % 8 != 0: the per-element wgrad_reduce_kernel (the encoder's 4-channel input layer)
+    ((1, 4, 4, 4, 32), ("fp32",), ("3x3", "up", "1x1")),
 )
 
 

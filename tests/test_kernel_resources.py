@@ -18,7 +18,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     ("modconv_bf16.hip", [r"modconv_bf16_kernelILi[124]E", r"upconv_bf16_kernelILi[124]E"]),
     ("modconv.hip", [r"modconv_kernelI"]),
     ("smallconv.hip", [r"smallconv_kernelILi[1245]E"]),
-    ("wgrad_bf16.hip", [r"wgrad_bf16_kernelI"]),
+    ("wgrad_bf16.hip", [r"wgrad_bf16_kernelI", r"wgrad_up_bf16_kernel"]),
     ("wgrad.hip", [r"wgrad_kernelI"]),
     ("upfir_lean.hip", [r"upfir_lean_kernelI"]),      # round 6: the streaming first-SR-layer kernel: <= 256 registers, scratch 0
 ])
@@ -27,16 +27,48 @@ def test_conv_kernels_do_not_spill(tmp_path, src, patterns):
                           os.path.join(ROOT, "hfa-gp_amd", "csrc", src), "-o", str(tmp_path / "x.o"),
                           "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
-    name, seen = None, 0
+    name, seen, scratch = None, set(), 0
     for line in out.stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
             name = m.group(1)
+        hit = [p for p in patterns if name and re.search(p, name)]
         m = re.search(r"VGPRs Spill: (\d+)", line)
-        if m and name and any(re.search(p, name) for p in patterns):
-            seen += 1
+        if m and hit:
+            seen.update(hit)
             assert int(m.group(1)) == 0, f"{name} spills {m.group(1)} VGPRs"
-    assert seen >= len(patterns), "resource remarks not found"
+        m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
+        if m and hit and src in ("wgrad.hip", "wgrad_bf16.hip"):       # the weight-gradient kernels: no scratch at all
+            scratch += 1
+            assert int(m.group(1)) == 0, f"{name}: {m.group(1)} bytes of scratch per lane"
+    assert seen == set(patterns), ("resource remarks not found", seen)
+    assert scratch or not src.startswith("wgrad"), "scratch remarks not found"
+
+
+def test_weight_gradient_staging_and_plan_have_a_single_source():
+    """The pieces that wgrad_bf16_kernel and wgrad_up_bf16_kernel share are each defined once, at file scope of wgrad_bf16.hip; the
+    rule "which kernel runs" is one predicate in wgrad_plan.h; the role the 3x3 kernel no longer has is gone."""
+    csrc = os.path.join(ROOT, "hfa-gp_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".hip")))
+    text = {f: open(os.path.join(csrc, f)).read() for f in files}
+    functions = {"static_for": "wgrad_bf16.hip", "x_unit": "wgrad_bf16.hip", "g_unit": "wgrad_bf16.hip", "x_offsets": "wgrad_bf16.hip",
+                 "g_offset": "wgrad_bf16.hip", "load_unit": "wgrad_bf16.hip", "load_style": "wgrad_bf16.hip", "style_src": "wgrad_bf16.hip",
+                 "tile_origin": "wgrad_bf16.hip", "commit_x_piece": "wgrad_bf16.hip", "commit_g_piece": "wgrad_bf16.hip",
+                 "read_a": "wgrad_bf16.hip", "mfma_group": "wgrad_bf16.hip", "group_step": "wgrad_bf16.hip",
+                 "wgrad_split16": "wgrad_plan.h", "wgrad_ksplit_policy": "wgrad_plan.h", "wgrad_dd_stride": "wgrad_plan.h"}
+    for name, home in functions.items():       # a definition: return type, name, parameter list, `{` (calls and declarations have no body)
+        where = [f for f in files for _ in re.finditer(r"^[^\n;=]*\b\w+\s+%s\s*\([^;{}]*\)\s*\{" % name, text[f], re.M)]
+        assert where == [home], (name, where)
+    for name in ("Raw", "Group", "Unit", "XOffsets", "Taps3x3", "TapsUp"):
+        where = [f for f in files for _ in re.finditer(r"\bstruct\s+%s\b\s*\{" % name, text[f])]
+        assert where == ["wgrad_bf16.hip"], (name, where)
+    unit = text["wgrad_bf16.hip"]
+    assert "SWAP" not in unit and "x_offsets = [&]" not in unit and "read_a = [&]" not in unit
+    assert unit.count("__builtin_amdgcn_mfma_f32_32x32x16_bf16") == 1 and unit.count("__builtin_amdgcn_sched_barrier") == 1
+    for f in ("wgrad.hip", "wgrad_bf16.hip"):
+        assert '#include "wgrad_plan.h"' in text[f], f
+        assert "% 64 == 0" not in text[f], f        # (no second copy of the predicate)
+    assert "launch_wgrad3x3_bf16(const HfagpWgradArgs* a, hipStream_t s);" not in text["wgrad.hip"]
 
 
 @pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="hipcc not available")
