@@ -367,7 +367,7 @@ class SynthesisFn(torch.autograd.Function):
         return SynthesisFn._forward(ctx, False, ws, c, u_strat, u_imp, gen, params)
 
     @staticmethod
-    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params, query=None):
+    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params, query=None, normal=False):
         tape = {}
         ws_c = ws.detach().float().contiguous()
         with torch.no_grad():
@@ -383,6 +383,14 @@ class SynthesisFn(torch.autograd.Function):
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape = ws.shape
         ctx.c_dtype = c.dtype
+        if normal:                                   # synthesis(normal_grad=True): a fixed seven outputs, the unused ones empty
+            ctx.set_materialize_grads(False)
+            ctx.q_dtype = None if query is None else query.dtype
+            outs = (img, rgb_raw, depth, mask[0] if geometry else depth.new_empty(0),
+                    q_sigma if query is not None else depth.new_empty(0), q_rgb if query is not None else depth.new_empty(0),
+                    gen._last_normal)        # (the body took the normals from the state the tape keeps: generator._forward_body)
+            ctx.mark_non_differentiable(*([] if geometry else outs[2:4]), *([] if query is not None else outs[4:6]))
+            return outs
         if query is not None:
             ctx.set_materialize_grads(False)
             ctx.q_dtype = query.dtype
@@ -404,7 +412,7 @@ class SynthesisFn(torch.autograd.Function):
         return (d_ws, d_c, None, None, None) + pgrads
 
     @staticmethod
-    def _backward(ctx, g_img, g_raw, g_depth, g_mask=None, g_qsigma=None, g_qrgb=None, need_coords=False):
+    def _backward(ctx, g_img, g_raw, g_depth, g_mask=None, g_qsigma=None, g_qrgb=None, need_coords=False, g_normal=None):
         gen, tape = ctx.gen, ctx.tape
         if tape is None:
             raise RuntimeError("TriPlaneGenerator.synthesis: backward called a second time — the saved activations "
@@ -468,6 +476,14 @@ class SynthesisFn(torch.autograd.Function):
             _, d_coords = gen._timed("planes_query_bwd", float(b), _query_backward, gen, tape["planes"], tape["query"],
                                      tape.get("planes_absmax"), g_qsigma, g_qrgb, rb[0] if ctx.pg else rb, need_coords,
                                      rb[1] if ctx.pg else None)
+        if g_normal is not None:
+            # 'image_normal' of synthesis(normal_grad=True): one launch that adds into the renderer's d_planes and decoder gradients,
+            # after raymarch_bwd for the same reason as the point query (it adds to every plane at its true texels)
+            gen._timed("raymarch_normals_bwd", float(b), ops.raymarch_normals_bwd,
+                       g_normal.float().permute(0, 2, 3, 1).reshape(b, res * res, 3).contiguous(), tape["planes"], tape["ray_state"],
+                       u_strat=tape["u_strat"], u_imp=tape["u_imp"], planes_absmax=tape.get("planes_absmax"),
+                       d_planes=rb[0] if ctx.pg else rb, decoder_grads=ctx.pg, dec_out=rb[1] if ctx.pg else None,
+                       **gen._render_args(tape["c"]))
         if ctx.pg:
             d_planes, dec = rb
             for prm, g in zip(dec_prm, dec):
@@ -507,6 +523,26 @@ class SynthesisQueryFn(SynthesisFn):
     def backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb):
         need_coords = ctx.needs_input_grad[4] and (g_qsigma is not None or g_qrgb is not None)
         d_ws, d_c, d_coords, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, need_coords)
+        if d_coords is not None:
+            d_coords = d_coords.to(ctx.q_dtype)
+        return (d_ws, d_c, None, None, d_coords, None, None) + pgrads
+
+
+class SynthesisNormalFn(SynthesisFn):
+    """`synthesis(normal_grad=True)`: the inputs of SynthesisQueryFn (coords may be None); outputs image, image_raw, image_depth,
+    image_mask, query_sigma, query_rgb, image_normal [B,3,r,r] (what `geometry` / `query` do not ask for: empty, non-differentiable).
+    The gradient of the last reaches the planes and the decoder through ops.raymarch_normals_bwd after ops.raymarch_bwd and the
+    point query's backward, into their d_planes and decoder gradients: one backbone pass serves every loss term."""
+    @staticmethod
+    def forward(ctx, ws, c, u_strat, u_imp, coords, geometry, gen, *params):
+        return SynthesisFn._forward(ctx, bool(geometry), ws, c, u_strat, u_imp, gen, params, query=coords, normal=True)
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, g_normal):
+        need_coords = ctx.needs_input_grad[4] and (g_qsigma is not None or g_qrgb is not None)
+        d_ws, d_c, d_coords, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, need_coords,
+                                                            g_normal)
         if d_coords is not None:
             d_coords = d_coords.to(ctx.q_dtype)
         return (d_ws, d_c, None, None, d_coords, None, None) + pgrads

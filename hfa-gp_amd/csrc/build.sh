@@ -35,6 +35,7 @@ units+=(weight_prep)
 units+=(raymarch_camera)
 units+=(planes_query_bwd)
 units+=(raymarch_normals)
+units+=(raymarch_normals_bwd)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

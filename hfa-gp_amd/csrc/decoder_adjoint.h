@@ -9,6 +9,8 @@
 //   dec_grad_*              decoder-parameter gradients (PG): per-tile operand images + 64 MFMAs, one flush per wave
 //   publish_df / publish_taps / scatter_tile_runs    dL/dF -> d planes by run-merged 128-byte atomics
 //   gather_position_grad    positional derivative of the bilinear gather
+//   publish_taps2 / scatter_tile_runs2 / w0_mul / w0t_mul / nrm_grad_*     second order (raymarch_normals_bwd.hip): the scatter
+//                           with two value / weight sets, the fp32 products with W0', the weight-gradient sums
 #pragma once
 #include "raymarch_common.h"
 
@@ -456,6 +458,185 @@ __device__ __forceinline__ void gather_position_grad(const HfagpRaymarchArgs& a,
             if (a.plane_axes == 0) dq[0] += diy; else dq[1] += diy;
         }
     }
+}
+
+// ---------------------------------------------------------------- second order: the backward of the normals
+// (raymarch_normals_bwd.hip) differentiates the decoder adjoint itself.  Its pieces sit here next to their first-order
+// siblings: the scatter with two value / weight sets, the two fp32 products with W0', and the weight-gradient sums.
+
+// ---- d planes: the run-merged line scatter (scatter_tile_runs) with TWO value / weight sets per tap: the
+// texel of tap k receives  dF w_k / 3 + a w'_k / 3  as ONE 128-byte atomic per run (two calls of scatter_tile_runs<6> would issue
+// two: the cost of the scatter follows the atomics).  Same tables, same walk, same merging rule; a tap is skipped when both of
+// its weights are 0 (outside the plane, or a sample that contributes nothing).
+struct Tile2Lds {
+    float df[16 * 32];                                      // dL/dF, then a = d sigma / dF, of the 16 samples, [sample][channel]
+    __attribute__((aligned(16))) int   idx[12 * 16];        // texel index of every tap, [plane*4 + tap][sample]
+    __attribute__((aligned(16))) float wgt[12 * 16];        // w_k / 3
+    __attribute__((aligned(16))) float dwg[12 * 16];        // w'_k / 3
+};
+// a lane (j, g = pl) publishes plane pl's taps of sample j (one plane per call, under the caller's `if (g == pl)`: publish_taps)
+__device__ __forceinline__ void publish_taps2(Tile2Lds& lds, int pl, const PlaneTaps& t, const PlaneTaps& dt, int j, bool valid) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        lds.idx[(pl * 4 + k) * 16 + j] = t.idx[k];
+        lds.wgt[(pl * 4 + k) * 16 + j] = valid ? t.w[k] * 0.3333333333333333f : 0.f;
+        lds.dwg[(pl * 4 + k) * 16 + j] = valid ? dt.w[k] * 0.3333333333333333f : 0.f;
+    }
+}
+// lane (j, g), register r of tile ft -> channel 16 ft + 4 g + r of sample j (publish_df); then the column of channel lane & 31
+__device__ __forceinline__ void publish_df2(Tile2Lds& lds, int j, int g, const f32x4 v[2]) {
+#pragma unroll
+    for (int ft = 0; ft < 2; ++ft)
+        *reinterpret_cast<float4*>(&lds.df[j * 32 + 16 * ft + 4 * g]) = make_float4(v[ft][0], v[ft][1], v[ft][2], v[ft][3]);
+}
+__device__ __forceinline__ void channel_column(const Tile2Lds& lds, int lane, float col[16]) {
+#pragma unroll
+    for (int sm = 0; sm < 16; ++sm) col[sm] = lds.df[sm * 32 + (lane & 31)];
+}
+// dfc, avc: this lane's channel of dL/dF and of a for the 16 samples (channel_column: the two pass through lds.df one after the other)
+template <int NPK>
+__device__ __forceinline__ void scatter_tile_runs2(const Tile2Lds& lds, const float dfc[16], const float avc[16], float* base,
+                                                   size_t plane_stride, int lane) {
+    const int c = lane & 31, hf = lane >> 5;
+    base += c;
+#pragma unroll 1
+    for (int pk = 0; pk < NPK; ++pk) {
+        const int pl = pk >> 1, k = 2 * (pk & 1) + hf;
+        float* pbase = base + (size_t)pl * plane_stride;
+        float wv[16], dv[16];
+        int tv[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 w4 = *reinterpret_cast<const float4*>(&lds.wgt[(pl * 4 + k) * 16 + 4 * q]);
+            const float4 d4 = *reinterpret_cast<const float4*>(&lds.dwg[(pl * 4 + k) * 16 + 4 * q]);
+            const int4 t4 = *reinterpret_cast<const int4*>(&lds.idx[(pl * 4 + k) * 16 + 4 * q]);
+            wv[4 * q] = w4.x; wv[4 * q + 1] = w4.y; wv[4 * q + 2] = w4.z; wv[4 * q + 3] = w4.w;
+            dv[4 * q] = d4.x; dv[4 * q + 1] = d4.y; dv[4 * q + 2] = d4.z; dv[4 * q + 3] = d4.w;
+            tv[4 * q] = t4.x; tv[4 * q + 1] = t4.y; tv[4 * q + 2] = t4.z; tv[4 * q + 3] = t4.w;
+        }
+        int cur = -1;
+        float run = 0.f;
+#pragma unroll
+        for (int sm = 0; sm < 16; ++sm) {
+            const int t = tv[sm];
+            const float v = fmaf(avc[sm], dv[sm], dfc[sm] * wv[sm]);
+            if (wv[sm] != 0.f || dv[sm] != 0.f) {
+                if (t == cur) {
+                    run += v;
+                } else {
+                    if (cur >= 0) unsafeAtomicAdd(pbase + (size_t)cur * 32, run);
+                    cur = t;
+                    run = v;
+                }
+            }
+        }
+        if (cur >= 0) unsafeAtomicAdd(pbase + (size_t)cur * 32, run);
+    }
+}
+
+// out^T[32x16] = W0'^T . x^T on the fp32 matrix pipe (the second product of decoder_bwd_lds): x in the C layout of the hidden
+// tiles, out in the C layout of the two feature tiles (channel 16 ft + 4 g + r)
+__device__ __forceinline__ void w0t_mul(const float* w0t, int lane, const f32x4 x[4], f32x4 out[2]) {
+    const float* W0 = w0t + lane;
+#pragma unroll
+    for (int ft = 0; ft < 2; ++ft) {
+        out[ft] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                out[ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(W0[(ft * 16 + mt * 4 + r) * 64], x[mt][r], out[ft], 0, 0, 0);
+    }
+}
+// v^T[64x16] = W0' . u^T on the fp32 matrix pipe (layer 1 of decoder_fwd_lds without its bias): w0f rows mt * 8 + t of lane
+// (j, g) = W0'[16 mt + j][8 g + t]; u in the gather's layout (channels 8 g + t), v in the C layout of the hidden tiles
+__device__ __forceinline__ void w0_mul(const float* w0f, int lane, const float u[8], f32x4 v[4]) {
+    const float* W = w0f + lane;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        v[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int t = 0; t < 8; ++t) v[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(W[(mt * 8 + t) * 64], u[t], v[mt], 0, 0, 0);
+    }
+}
+
+// operand images of the sample-contracting products  dW0'[64x32] += x[64x16] . F[16x32] + dH[64x16] . u[16x32]
+struct NrmGradLds {
+    float x[64 * 17], dh[64 * 17], f[16 * 33], u[16 * 33];
+};
+struct NrmGradAcc {                              // a wave's running sums over its tiles
+    f32x4 aw0[4][2];                             // dW0' tiles [kt][ft]
+    float s_x[4][4], s_sw[4][4], s_ds;           // per-lane b0' / sigma-row sums, dbsig
+};
+
+// one tile of the weight-gradient products (the operand layouts of dec_grad_tile)
+__device__ __forceinline__ void nrm_grad_tile(NrmGradAcc& acc, NrmGradLds& gl, int j, int g, const float f[8], const float u[8],
+                                              const f32x4 x[4], const f32x4 dH[4]) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            gl.x[(16 * mt + 4 * g + r) * 17 + j] = x[mt][r];
+            gl.dh[(16 * mt + 4 * g + r) * 17 + j] = dH[mt][r];
+        }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        gl.f[j * 33 + 8 * g + t] = f[t];
+        gl.u[j * 33 + 8 * g + t] = u[t];
+    }
+    WAVE_SYNC();
+    // MFMA operands: A[i][k] -> lane (i = j, k = g); B[k][n] -> lane (k = g, n = j); 4 samples per step
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+        const int smp = 4 * st + g;
+        float ax[4], ad[4], bf[2], bu[2];
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt) {
+            ax[kt] = gl.x[(16 * kt + j) * 17 + smp];
+            ad[kt] = gl.dh[(16 * kt + j) * 17 + smp];
+        }
+#pragma unroll
+        for (int ft = 0; ft < 2; ++ft) {
+            bf[ft] = gl.f[smp * 33 + 16 * ft + j];
+            bu[ft] = gl.u[smp * 33 + 16 * ft + j];
+        }
+#pragma unroll
+        for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+            for (int ft = 0; ft < 2; ++ft) {
+                acc.aw0[kt][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(ax[kt], bf[ft], acc.aw0[kt][ft], 0, 0, 0);
+                acc.aw0[kt][ft] = __builtin_amdgcn_mfma_f32_16x16x4f32(ad[kt], bu[ft], acc.aw0[kt][ft], 0, 0, 0);
+            }
+    }
+}
+
+// end of the kernel: one set of atomics per wave, with the gains of dec_grad_flush; the colour rows of the second layer get nothing
+__device__ __forceinline__ void nrm_grad_flush(const NrmGradAcc& acc, const DecGrads& dg, float lr_mul, int lane) {
+    const int j = lane & 15, g = lane >> 4;
+    const float g0 = lr_mul * 0.17677669529663687f, g1 = lr_mul * 0.125f, gb = lr_mul;
+#pragma unroll
+    for (int kt = 0; kt < 4; ++kt)
+#pragma unroll
+        for (int ft = 0; ft < 2; ++ft)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                unsafeAtomicAdd(dg.w0 + (16 * kt + 4 * g + r) * 32 + 16 * ft + j, acc.aw0[kt][ft][r] * g0);
+    auto red16 = [](float v) {
+        v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
+        return v;
+    };
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float vb = red16(acc.s_x[mt][r]), vw = red16(acc.s_sw[mt][r]);
+            if (j == 0) {
+                unsafeAtomicAdd(dg.b0 + 16 * mt + 4 * g + r, vb * gb);
+                unsafeAtomicAdd(dg.w1 + 16 * mt + 4 * g + r, vw * g1);          // sigma row of W1
+            }
+        }
+    const float vs = red16(acc.s_ds);
+    if (lane == 0) unsafeAtomicAdd(dg.b1, vs * gb);
 }
 
 }  // namespace hfagp

@@ -173,6 +173,7 @@ class TriPlaneGenerator(nn.Module):
         self._planes_absmax = None               # [64] slots with max |planes| of the pass in flight (16-bit decoder)
         self._want_normals = False               # synthesis(normals=True) in flight: _forward_body takes the normal pass too ...
         self._last_normal = None                 # ... and leaves 'image_normal' here for synthesis to pick up
+        self._want_normal_grad = False           # synthesis(normal_grad=True) in flight: 'image_normal' is an autograd output
         self._scalars: Dict[int, tuple] = {}     # id(param) -> (version, data_ptr, python float)
         self._const_nhwc: Optional[tuple] = None
         self.timing: Optional[Dict[str, list]] = None   # bench.py: {'raymarch': [(ev0, ev1, units)], 'modconv': [...]}
@@ -740,6 +741,18 @@ class TriPlaneGenerator(nn.Module):
             raise ValueError(f"expected ws [B,{cfg.num_ws},{cfg.w_dim}] and c [B,{cfg.c_dim}], got "
                              f"{tuple(ws.shape)} and {tuple(c.shape)}")
 
+    def _check_normal_grad(self, ws, c) -> None:
+        """The refusals of `synthesis(normal_grad=True)` under grad, before anything is launched."""
+        cfg = self.cfg
+        if c.requires_grad:
+            raise NotImplementedError("TriPlaneGenerator.synthesis(normal_grad=True): the camera gradient of the normal term is not "
+                                      "implemented (c.requires_grad); detach the label, or use normals=True for a detached map")
+        frame_bytes = cfg.neural_rendering_resolution ** 2 * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
+        if ws.shape[0] * frame_bytes > RAY_STATE_CAP_BYTES:
+            raise RuntimeError(f"TriPlaneGenerator.synthesis(normal_grad=True): the backward of 'image_normal' reads the ray marcher's "
+                               f"per-sample state, {ws.shape[0] * frame_bytes} bytes for {ws.shape[0]} frames, above "
+                               f"RAY_STATE_CAP_BYTES = {RAY_STATE_CAP_BYTES}; {RAY_STATE_CAP_BYTES // frame_bytes} frames fit")
+
     def _forward_impl(self, ws, c, u_strat, u_imp, tape, geometry=False):
         """ws, c: detached contiguous fp32 CUDA tensors.  Returns image, image_raw, depth, planes, feat_img — and, with
         `geometry`, the opacity image [B,1,r,r] as a sixth; when `tape` is a dict it is filled with everything the backward
@@ -796,7 +809,7 @@ class TriPlaneGenerator(nn.Module):
     def synthesis(self, ws: torch.Tensor, c: torch.Tensor, noise_mode: str = "const",
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                   return_planes: bool = False, geometry: bool = False, query: Optional[torch.Tensor] = None,
-                  normals: bool = False, **_unused) -> Dict[str, torch.Tensor]:
+                  normals: bool = False, normal_grad: bool = False, **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
         HFA-GP), w.r.t. the generator parameters that require grad (after `tune_generator()`) and w.r.t. the camera label `c`
         when it requires grad (pose refinement; the importance depths are detached as in EG3D).
@@ -812,17 +825,31 @@ class TriPlaneGenerator(nn.Module):
         `normals=True`: the dict also has 'image_normal' [B,3,r,r], the per-ray surface normal in WORLD space, pixel-aligned with
         'image_raw' / 'image_depth': N = Σ_s ω_s n_s with n = −∇σ·rsqrt(‖∇σ‖² + 1e-12) the unit normal of the raw density (from
         dense to empty) at every sample and ω the renderer's colour weights, so ‖N‖ ≤ 'image_mask'; not normalised
-        (`render.normal_map` turns it into a picture).  It is detached — forward only, inside a differentiable step too: its
-        gradient would be a second derivative of the tri-plane gather.  The other outputs and their gradients are unchanged."""
+        (`render.normal_map` turns it into a picture).  With `normals=True` alone it is detached, inside a differentiable step
+        too; the other outputs and their gradients are unchanged.
+        `normal_grad=True` (implies `normals=True`): 'image_normal' is a differentiable output — normal-map supervision (a cosine
+        or L1 term against an estimated or mesh normal map) reaches `ws` and the generator parameters that require grad, through
+        the compositing weights and through the normals themselves (the second derivative of the tri-plane gather:
+        ops.raymarch_normals_bwd, one launch that joins the renderer's plane and decoder gradients before the one backbone
+        backward pass; a loss that does not touch 'image_normal' launches nothing extra).  It composes with `geometry=True` and
+        `query=`.  The camera gradient of the normal term is not implemented: with `c.requires_grad` the call raises
+        NotImplementedError.  The backward reads the ray marcher's saved per-sample state: a batch whose state exceeds
+        RAY_STATE_CAP_BYTES raises RuntimeError (fitting batches are far below it)."""
         self._check_inputs(ws, c, noise_mode)
-        if normals:                   # one pass of the body below with the request set (the state of the ray marcher is shared)
+        if normals or normal_grad:    # one pass of the body below with the request set (the state of the ray marcher is shared)
+            if normal_grad and torch.is_grad_enabled():
+                self._check_normal_grad(ws, c)
             self._want_normals, self._last_normal = True, None
+            self._want_normal_grad = bool(normal_grad)
             try:
                 out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query)
             finally:
-                self._want_normals = False
-            r = self.cfg.neural_rendering_resolution
-            out["image_normal"] = self._last_normal if ws.shape[0] else torch.zeros(0, 3, r, r, device=ws.device)
+                self._want_normals = self._want_normal_grad = False
+            if "image_normal" not in out:         # (a differentiable one is an output of the autograd function itself)
+                r = self.cfg.neural_rendering_resolution
+                out["image_normal"] = self._last_normal if ws.shape[0] else torch.zeros(0, 3, r, r, device=ws.device)
+                if normal_grad and not ws.shape[0] and torch.is_grad_enabled():
+                    out["image_normal"] = out["image_normal"] + 0.0 * ws.sum()      # keeps the autograd edge to ws
             self._last_normal = None
             return out
         if query is not None:
@@ -851,7 +878,17 @@ class TriPlaneGenerator(nn.Module):
         c_in = c if cam_grad else c.detach()
         if need_grad:
             from .autograd import SynthesisFn
-            if query is not None:
+            if getattr(self, "_want_normal_grad", False):
+                from .autograd import SynthesisNormalFn
+                img, rgb_raw, depth, mask, q_sigma, q_rgb, normal = SynthesisNormalFn.apply(ws, c_in, u_strat, u_imp, query, geometry,
+                                                                                            self, *params)
+                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
+                if geometry:
+                    out["image_mask"] = mask
+                if query is not None:
+                    out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
+                out["image_normal"] = normal
+            elif query is not None:
                 from .autograd import SynthesisQueryFn
                 img, rgb_raw, depth, mask, q_sigma, q_rgb = SynthesisQueryFn.apply(ws, c_in, u_strat, u_imp, query, geometry, self,
                                                                                    *params)

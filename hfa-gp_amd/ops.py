@@ -12,6 +12,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+import types
 from typing import Optional, Tuple
 
 import torch
@@ -780,7 +781,8 @@ def raymarch_normals(planes: torch.Tensor, state: torch.Tensor, *, cam2world: to
     """Per-ray surface normals [B,R,3] (hfagp_raymarch_normals) of the `raymarch(..., state=state)` call with the same arguments:
     N = Σ_s ω_s n_s over the Sc + Sf depth-sorted samples, n = −g·rsqrt(g·g + 1e-12) with g = ∇ₓσ the WORLD-space gradient of the
     raw decoder density (before softplus(σ − 1)), ω the colour weights of the forward.  ‖N‖ ≤ wsum; not normalised; `white_back`
-    does not enter.  Forward only: the result carries no gradient.  No atomics: two calls return the same bits."""
+    does not enter.  The result carries no gradient (its backward is `raymarch_normals_bwd`).  No atomics: two calls return the
+    same bits."""
     if state is None:
         raise RuntimeError("raymarch_normals: state must be the `raymarch_state` buffer the forward call filled, got None")
     a = L.RaymarchArgs()
@@ -791,6 +793,43 @@ def raymarch_normals(planes: torch.Tensor, state: torch.Tensor, *, cam2world: to
         return normal
     L.check(L.lib().hfagp_raymarch_normals(C.byref(a), _ptr(normal), _stream()), "raymarch_normals")
     return normal
+
+
+def raymarch_normals_bwd(g_normal: torch.Tensor, planes: torch.Tensor, state: torch.Tensor, *, cam2world: torch.Tensor,
+                         intrinsics: torch.Tensor, u_strat: torch.Tensor, u_imp: torch.Tensor, dec_w0: torch.Tensor,
+                         dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, res: int, ray_start: float, ray_end: float,
+                         box_warp: float, decoder_lr_mul: float, plane_axes: int, white_back: bool, decoder_precision: str,
+                         planes_absmax: Optional[torch.Tensor] = None, d_planes: Optional[torch.Tensor] = None,
+                         decoder_grads: bool = False, dec_out=None):
+    """Backward of `raymarch_normals(planes, state, ...)` (hfagp_raymarch_normals_bwd) → ``(d_planes, dec)``.  ``g_normal`` [B,R,3]:
+    dL/d normal.  Through the compositing weights (the normals as three colours) and through the normals themselves (the second
+    derivative of the tri-plane gather: include/hfagp.h has the formulas); the sample depths carry no gradient.
+
+      * ``d_planes``: a [B,3,H,W,32] tensor the plane gradient is ACCUMULATED into (returned); None = fresh zeros.  A tensor shared
+        with `raymarch_bwd` must have been through that call FIRST: on mirrored planes it overwrites plane 2, and this kernel adds
+        to all three planes at their true texels.
+      * ``decoder_grads`` / ``dec_out``: as `raymarch_bwd` — the four decoder-parameter gradients, accumulated into ``dec_out`` when
+        given, else into fresh zeros; ``dec`` is None without them.  The colour rows of the second layer receive nothing.
+    A ray whose ``g_normal`` is exactly zero touches nothing.  The other keywords are the forward's; pass its ``planes_absmax``."""
+    if state is None:
+        raise RuntimeError("raymarch_normals_bwd: state must be the `raymarch_state` buffer the forward call filled, got None")
+    a = L.RaymarchArgs()
+    b, _, _, r, _, _ = _ray_args("raymarch_normals_bwd", a, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1,
+                                 res, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision,
+                                 planes_absmax, state)
+    if _chk(g_normal, "raymarch_normals_bwd: g_normal").shape != (b, r, 3):
+        raise RuntimeError(f"raymarch_normals_bwd: g_normal must be [B, R, 3] = [{b}, {r}, 3], got {tuple(g_normal.shape)}")
+    if d_planes is None:
+        d_planes = torch.zeros_like(planes)
+    elif _chk(d_planes, "raymarch_normals_bwd: d_planes").shape != planes.shape:
+        raise RuntimeError(f"raymarch_normals_bwd: d_planes must be shaped like planes {tuple(planes.shape)}, got {tuple(d_planes.shape)}")
+    out = types.SimpleNamespace(d_dec_w0=None, d_dec_b0=None, d_dec_w1=None, d_dec_b1=None)      # (the entry takes them one by one)
+    dec = _dec_grad_out("raymarch_normals_bwd", out, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_grads, dec_out)
+    if b == 0:
+        return d_planes, dec
+    L.check(L.lib().hfagp_raymarch_normals_bwd(C.byref(a), _ptr(g_normal), _ptr(d_planes), out.d_dec_w0, out.d_dec_b0, out.d_dec_w1,
+                                               out.d_dec_b1, _stream()), "raymarch_normals_bwd")
+    return d_planes, dec
 
 
 def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *, grid=None, dec_w0: torch.Tensor,

@@ -30,6 +30,7 @@
  *                              (skimage.measure.marching_cubes + plyfile in EG3D's shape_utils), on the GPU (ABI 14)
  *   hfagp_raymarch_normals  <- (no reference counterpart: the per-ray surface normal map of EG3D-family geometry renders — the
  *                              density gradient of every sample composited with MipRayMarcher2's weights)
+ *   hfagp_raymarch_normals_bwd <- (none either: what autograd would do with a normal-map loss on such a render)
  *   hfagp_depth_clamp       <- MipRayMarcher2's torch.clamp(depth, min sample depth, max sample depth) over the batch, one launch (ABI 10)
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
@@ -129,10 +130,34 @@ int hfagp_raymarch_fwd(const HfagpRaymarchArgs* a, void* stream);
  * weights of the forward, omega = (w_{r-1} + w_r) / 2 at sorted position r (MipRayMarcher2's midpoint rule with the normals as
  * colours, before its * 2 - 1).  |normal| <= wsum; not normalised; white_back does not enter.  Decoder arithmetic as the forward:
  * split 16-bit operands given planes_absmax (gradient products: bf16 parts), exact fp32 without it.  One writer per ray, no
- * atomics: two calls give the same bits.  Forward only (its gradient would be a second derivative of the gather).
+ * atomics: two calls give the same bits.  Its backward is hfagp_raymarch_normals_bwd.
  * HFAGP_EBADARG, nothing launched: fwd, normal, fwd->state or fwd->planes NULL (then the checks of hfagp_raymarch_fwd on the
  * inputs); HFAGP_EUNSUPPORTED: sample counts the forward does not support.                                                    */
 int hfagp_raymarch_normals(const HfagpRaymarchArgs* fwd, float* normal /* [B][R][3] */, void* stream);
+
+/* Backward of hfagp_raymarch_normals (additive to ABI 15): from g_normal = dL/d normal to the plane gradient and the decoder-
+ * parameter gradients, one launch, same arguments and state as the forward call.  With F the 32 gathered features of a sample at
+ * q = (2 / box_warp) x, hp = W0' F + b0' (the lr_mul gains folded in as in the forward), sigma = wsig . softplus(hp) + bsig,
+ * a = d sigma / dF = W0'^T (wsig * sigmoid(hp)), J = dF / dq, g = (2 / box_warp) J^T a, r = sqrt(g.g + 1e-12), n = -g / r:
+ *   through the weights   G_e = g_normal . (n_e + n_{e+1}) / 2 is dL/dw_e of the midpoint weights (the normals are three colours
+ *                         of the compositing, no * 2 - 1, no white_back); the compositing adjoint of hfagp_raymarch_bwd gives
+ *                         d sigma_s of the raw densities.  The sample depths carry no gradient.
+ *   through the normals   gamma = dL/dg_s = -(omega_s / r)(g_normal - n (n . g_normal)); per tap k of every plane, with w_k its
+ *                         bilinear weight, w'_k = (2 / box_warp) gamma . grad_q w_k (0 for a tap outside the plane),
+ *                         u = sum_planes sum_k texel w'_k / 3,  v = W0' u,  e = wsig * sigmoid(hp) * (1 - sigmoid(hp)) * v,
+ *                         dF = a d sigma_s + W0'^T e.
+ *   d_planes    += (w_k / 3) dF + (w'_k / 3) a at every tap, all three planes at their true texels (fp32 atomics): on mirrored
+ *                  planes call it AFTER hfagp_raymarch_bwd on the same buffer, which overwrites plane 2.
+ *   d_dec_w0    += [(d sigma_s dH + e) F^T + dH u^T] * gain, dH = wsig * sigmoid(hp);   d_dec_b0 += (d sigma_s dH + e) * gain;
+ *   d_dec_w1[0] += [d sigma_s softplus(hp) + sigmoid(hp) * v] * gain;   d_dec_b1[0] += d sigma_s * gain; the colour rows get
+ *                  nothing.  The four go together (all or none); gains as hfagp_raymarch_bwd.
+ * The second-order products run on the exact fp32 matrix instructions with either decoder.  A ray whose g_normal is exactly 0
+ * touches nothing.  HFAGP_EBADARG, nothing launched: fwd, fwd->state, fwd->planes, g_normal or d_planes NULL, or only some of the
+ * four decoder outputs given (then the checks of hfagp_raymarch_fwd); HFAGP_EUNSUPPORTED: sample counts.                       */
+int hfagp_raymarch_normals_bwd(const HfagpRaymarchArgs* fwd, const float* g_normal /* [B][R][3] */,
+                               float* d_planes /* [B][3][H][W][32], accumulated into */,
+                               float* d_dec_w0, float* d_dec_b0, float* d_dec_w1, float* d_dec_b1 /* all four or none; accumulated */,
+                               void* stream);
 
 /* ------------------------------------------------------------------ point queries (ABI 13)
  * The decoder at arbitrary points, no compositing: per point the same tri-plane gather and OSGDecoder the ray marcher runs,
