@@ -383,6 +383,7 @@ class SynthesisFn(torch.autograd.Function):
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape = ws.shape
         ctx.c_dtype = c.dtype
+        ctx.normal_camera = bool(getattr(gen, "_want_normal_camera_grad", False))      # synthesis(normal_camera_grad=True)
         if normal:                                   # synthesis(normal_grad=True): a fixed seven outputs, the unused ones empty
             ctx.set_materialize_grads(False)
             ctx.q_dtype = None if query is None else query.dtype
@@ -463,10 +464,20 @@ class SynthesisFn(torch.autograd.Function):
                         dec_out=tuple(p.grad for p in dec_prm) if dec_direct else None, rec_out=rec_out,
                         **geom, **gen._render_args(tape["c"]))
         d_c = None
+        g_nrm = None
+        if g_normal is not None:
+            g_nrm = g_normal.float().permute(0, 2, 3, 1).reshape(b, res * res, 3).contiguous()
         if need_c:      # the camera label: positional derivative of the gather along every ray, then the adjoint of the ray generation
-            d_c2w, d_intr, _ = gen._timed("raymarch_bwd_camera", float(b), ops.raymarch_bwd_camera, g_feat.view(b, res * res, 32),
-                                          tape["planes"], rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
-                                          planes_absmax=tape.get("planes_absmax"), **gen._render_args(tape["c"]))
+            nrm_c = g_nrm is not None and ctx.normal_camera       # the normal term joins the per-ray records: one reduction for the loss
+            d_c2w, d_intr, ray_grad = gen._timed("raymarch_bwd_camera", float(b), ops.raymarch_bwd_camera, g_feat.view(b, res * res, 32),
+                                                 tape["planes"], rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
+                                                 planes_absmax=tape.get("planes_absmax"), reduce=not nrm_c,
+                                                 **gen._render_args(tape["c"]))
+            if nrm_c:
+                d_c2w, d_intr, _ = gen._timed("raymarch_normals_bwd_camera", float(b), ops.raymarch_normals_bwd_camera, g_nrm,
+                                              tape["planes"], tape["ray_state"], ray_grad=ray_grad, u_strat=tape["u_strat"],
+                                              u_imp=tape["u_imp"], planes_absmax=tape.get("planes_absmax"),
+                                              **gen._render_args(tape["c"]))
             d_c = torch.cat((d_c2w, d_intr), 1).to(ctx.c_dtype)
         d_coords = None
         if g_qsigma is not None or g_qrgb is not None:
@@ -479,8 +490,7 @@ class SynthesisFn(torch.autograd.Function):
         if g_normal is not None:
             # 'image_normal' of synthesis(normal_grad=True): one launch that adds into the renderer's d_planes and decoder gradients,
             # after raymarch_bwd for the same reason as the point query (it adds to every plane at its true texels)
-            gen._timed("raymarch_normals_bwd", float(b), ops.raymarch_normals_bwd,
-                       g_normal.float().permute(0, 2, 3, 1).reshape(b, res * res, 3).contiguous(), tape["planes"], tape["ray_state"],
+            gen._timed("raymarch_normals_bwd", float(b), ops.raymarch_normals_bwd, g_nrm, tape["planes"], tape["ray_state"],
                        u_strat=tape["u_strat"], u_imp=tape["u_imp"], planes_absmax=tape.get("planes_absmax"),
                        d_planes=rb[0] if ctx.pg else rb, decoder_grads=ctx.pg, dec_out=rb[1] if ctx.pg else None,
                        **gen._render_args(tape["c"]))

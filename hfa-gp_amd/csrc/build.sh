@@ -36,6 +36,7 @@ units+=(raymarch_camera)
 units+=(planes_query_bwd)
 units+=(raymarch_normals)
 units+=(raymarch_normals_bwd)
+units+=(raymarch_normals_camera)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

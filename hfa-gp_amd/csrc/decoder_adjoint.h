@@ -9,6 +9,8 @@
 //   dec_grad_*              decoder-parameter gradients (PG): per-tile operand images + 64 MFMAs, one flush per wave
 //   publish_df / publish_taps / scatter_tile_runs    dL/dF -> d planes by run-merged 128-byte atomics
 //   gather_position_grad    positional derivative of the bilinear gather
+//   gather_position_cross_grad   the same plus the mixed second derivative of the tap weights, one read of the texels;
+//   decoder_dh_lds          dH alone (raymarch_normals_camera.hip)
 //   publish_taps2 / scatter_tile_runs2 / w0_mul / w0t_mul / nrm_grad_*     second order (raymarch_normals_bwd.hip): the scatter
 //                           with two value / weight sets, the fp32 products with W0', the weight-gradient sums
 #pragma once
@@ -457,6 +459,69 @@ __device__ __forceinline__ void gather_position_grad(const HfagpRaymarchArgs& a,
             dq[2] += dix;
             if (a.plane_axes == 0) dq[0] += diy; else dq[1] += diy;
         }
+    }
+}
+
+// gather_position_grad of dF PLUS the mixed second derivative of the bilinear weights (raymarch_normals_camera.hip), from one
+// read of the twelve texel lines: the positional gradient of a loss that also reaches g = J^T a (J = dF / dq) through
+// gamma_q = dL/dg.  Bilinear weights have no pure second derivative, only d2 w_k / dgx dgy = s_k (W / 2)(H / 2) with
+// s = (+1, -1, -1, +1) for nw, ne, sw, se, so per plane, with (cx, cy) the components of gamma_q its two coordinates carry
+// (plane_coords) and zero padding through ok_k,
+//   m = (W / 2)(H / 2) sum_k s_k ok_k <texel_k, a> / 3,    dL/dgx = [gather_position_grad's] + m cy,    dL/dgy = [...] + m cx,
+// routed to dq as gather_position_grad routes its terms.  Lane (j, g) holds dF and a = d sigma / dF (av) of channels
+// 16 ft + 4 g + r and forms its share.  sx, sy: gather_position_grad's; sxy = (W / 2)(H / 2) / 3.
+__device__ __forceinline__ void gather_position_cross_grad(const HfagpRaymarchArgs& a, int b, int g, const float q[3],
+                                                           const f32x4 dF[2], const f32x4 av[2], const float gq[3], float sx,
+                                                           float sy, float sxy, float dq[3]) {
+    dq[0] = dq[1] = dq[2] = 0.f;
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl) {
+        float gx, gy;
+        plane_coords(a, q, pl, gx, gy);
+        PlaneTapsD t;
+        plane_taps_d(a, gx, gy, t);
+        const char* base = reinterpret_cast<const char*>(a.planes + ((size_t)(b * 3 + pl) * a.H * a.W) * 32);
+        float P[4], A[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned off = ((unsigned)t.idx[k] * 32u + 4u * g) * 4u;      // < 2^32: one plane
+            const float4 v0 = *reinterpret_cast<const float4*>(base + off);
+            const float4 v1 = *reinterpret_cast<const float4*>(base + off + 64);
+            float acc = dF[0][0] * v0.x, aca = av[0][0] * v0.x;
+            acc = fmaf(dF[0][1], v0.y, acc); aca = fmaf(av[0][1], v0.y, aca);
+            acc = fmaf(dF[0][2], v0.z, acc); aca = fmaf(av[0][2], v0.z, aca);
+            acc = fmaf(dF[0][3], v0.w, acc); aca = fmaf(av[0][3], v0.w, aca);
+            acc = fmaf(dF[1][0], v1.x, acc); aca = fmaf(av[1][0], v1.x, aca);
+            acc = fmaf(dF[1][1], v1.y, acc); aca = fmaf(av[1][1], v1.y, aca);
+            acc = fmaf(dF[1][2], v1.z, acc); aca = fmaf(av[1][2], v1.z, aca);
+            acc = fmaf(dF[1][3], v1.w, acc); aca = fmaf(av[1][3], v1.w, aca);
+            P[k] = t.ok[k] ? acc : 0.f;
+            A[k] = t.ok[k] ? aca : 0.f;
+        }
+        const float m = ((A[0] - A[1]) - (A[2] - A[3])) * sxy;
+        const float cx = pl == 2 ? gq[2] : gq[0];
+        const float cy = pl == 0 ? gq[1] : pl == 1 ? gq[2] : (a.plane_axes == 0 ? gq[0] : gq[1]);
+        const float dix = fmaf(m, cy, fmaf(1.f - t.fy, P[1] - P[0], t.fy * (P[3] - P[2])) * sx);
+        const float diy = fmaf(m, cx, fmaf(t.fx, P[3] - P[1], (1.f - t.fx) * (P[2] - P[0])) * sy);
+        if (pl == 0) { dq[0] += dix; dq[1] += diy; }
+        else if (pl == 1) { dq[0] += dix; dq[2] += diy; }
+        else {
+            dq[2] += dix;
+            if (a.plane_axes == 0) dq[0] += diy; else dq[1] += diy;
+        }
+    }
+}
+
+// dH = wsig * sigmoid(hp) alone (d sigma = 1, no colour gradient): the first half of decoder_bwd[16]_lds<false>, for a caller
+// that forms a = W0'^T dH itself (w0t_mul).  dimg: the decoder image of decoder_images_lds<DEC16>.
+template <bool DEC16>
+__device__ __forceinline__ void decoder_dh_lds(const float* dimg, int lane, const f32x4 hp[4], f32x4 dH[4]) {
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        const float* ws_ = dimg + ((DEC16 ? kDec16Wsig : kDecWsig) + mt * 4) * 64 + lane;
+        dH[mt] = f32x4{ws_[0], ws_[64], ws_[128], ws_[192]};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dH[mt][r] *= sigmoid_f(hp[mt][r]);      // softplus' = sigmoid
     }
 }
 

@@ -180,6 +180,11 @@ static void launch_camera(const RayParams& p, float* ray_grad, hipStream_t s) {
     else raymarch_bwd_camera_kernel<S, false><<<blocks, kCamWaves * 64, 0, s>>>(p, ray_grad);
 }
 
+// (raymarch_common.h) the reduction alone, for the other producer of ray_grad records: raymarch_normals_camera.hip
+void launch_camera_reduce(const HfagpRaymarchArgs& a, const float* ray_grad, float* d_cam2world, float* d_intrinsics, hipStream_t s) {
+    camera_reduce_kernel<<<(unsigned)a.B, kCamReduceThreads, 0, s>>>(a, ray_grad, d_cam2world, d_intrinsics);
+}
+
 }  // namespace hfagp
 
 using namespace hfagp;

@@ -44,6 +44,8 @@ inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char*
 }
 
 int launch_raymarch(const RayParams& p, bool grads, hipStream_t s);   // raymarch.hip
+// raymarch_camera.hip: camera_reduce_kernel on ray_grad [B][R][6] -> d_cam2world [B][16], d_intrinsics [B][9]
+void launch_camera_reduce(const HfagpRaymarchArgs& a, const float* ray_grad, float* d_cam2world, float* d_intrinsics, hipStream_t s);
 
 // 4 channels of a ray's dL/dfeat for pass 2 of the backward (off = ray * 32 + channel); no image gradient = zeros
 __device__ __forceinline__ float4 load_g_feat4(const RayParams& p, size_t off) {

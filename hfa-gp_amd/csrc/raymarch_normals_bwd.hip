@@ -25,53 +25,15 @@
 //   normals use (split bf16 with the 16-bit decoder): n has the forward's bits.
 //   A ray with G^ == 0 is skipped; a tile whose samples all have omega == 0 and d sigma == 0 is skipped; a sample like that in
 //   a live tile publishes weight 0.  The sample depths carry no gradient.
-#include "decoder_adjoint.h"
+#include "raymarch_normals_common.h"
 
 namespace hfagp {
 
 constexpr int kNbWaves = 4;
 
-// the forward's compositing over the S-1 midpoints (raymarch_normals_kernel's lines: the same bits), two midpoints per lane
-struct Composite {
-    float al[2], sh[2], dl[2], sbar[2], T[2], w[2];
-};
-template <int S>
-__device__ __forceinline__ void composite(const float* ts, const float* ss, int lane, Composite& c) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int e = lane + 64 * k;
-        c.al[k] = 0.f; c.sh[k] = 1.f; c.dl[k] = 0.f; c.sbar[k] = 0.f;
-        if (e < S - 1) {
-            const float t0 = ts[e], t1 = ts[e + 1];
-            c.sbar[k] = (ss[e] + ss[e + 1]) * 0.5f - 1.f;
-            const float dm = softplus_f(c.sbar[k]);
-            c.dl[k] = t1 - t0;
-            c.al[k] = 1.f - exp_f(-(dm * c.dl[k]));
-            c.sh[k] = 1.f - c.al[k] + 1e-10f;
-        }
-    }
-    const float i0 = wave_scan_mul(c.sh[0], lane);
-    const float tot0 = __shfl(i0, 63);
-    float T0 = __shfl_up(i0, 1);
-    if (lane == 0) T0 = 1.f;
-    const float i1 = wave_scan_mul(c.sh[1], lane);
-    float T1 = __shfl_up(i1, 1);
-    if (lane == 0) T1 = 1.f;
-    T1 *= tot0;
-    c.T[0] = T0; c.T[1] = T1;
-    c.w[0] = c.al[0] * T0; c.w[1] = c.al[1] * T1;       // zero beyond S-2
-}
-// v by sorted position = (v_{e-1} + v_e) / 2 of the per-midpoint values (two per lane), into dst[S]
-template <int S>
-__device__ __forceinline__ void midpoints_to_samples(float v0, float v1, int lane, float* dst) {
-    float p0 = __shfl_up(v0, 1);
-    if (lane == 0) p0 = 0.f;
-    float p1 = __shfl_up(v1, 1);
-    const float v0_63 = __shfl(v0, 63);
-    if (lane == 0) p1 = v0_63;
-    if (lane < S) dst[lane] = 0.5f * (p0 + v0);
-    if (lane + 64 < S) dst[lane + 64] = 0.5f * (p1 + v1);
-}
+// (Composite, composite, midpoints_to_samples: raymarch_normals_common.h, shared with raymarch_normals_camera.hip.  The blocks
+// below marked `twin:` have a copy there as functions, used by that unit: calling them from here changed this unit's register
+// allocation and instruction order, so the lines stay inline; keep the two in step.)
 
 template <int S, bool DEC16, bool PG>
 __global__ void __launch_bounds__(kNbWaves * 64, PG ? 1 : 2)
@@ -138,6 +100,7 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
         any = true;
         float o3[3], d3[3];
         ray_setup(a, b, pi, pj, o3, d3);
+        // (twin: normals_load_ray, raymarch_normals_common.h)
         {
             const float* st = a.state + (size_t)ray * (S * HFAGP_RAYMARCH_STATE_FLOATS_PER_SAMPLE);
 #pragma unroll
@@ -157,6 +120,7 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
         }
         WAVE_SYNC();
         // ---- pass A: n_s and 1 / r_s of every sample, as raymarch_normals_kernel computes them
+        // (twin: normals_pass_a, raymarch_normals_common.h, which forms a in fp32; a change here belongs there too)
 #pragma unroll 1
         for (int tt = 0; tt < NT; ++tt) {
             const int s = 16 * tt + j;
@@ -195,6 +159,7 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
         }
         WAVE_SYNC();
         // ---- the compositing adjoint (raymarch.hip) with the normals as colours: G_e = G^ . (n_e + n_{e+1}) / 2 -> d sigma_s
+        // (twin: normals_weight_adjoint, raymarch_normals_common.h)
         {
             Composite c;
             composite<S>(ts, ss, lane, c);
@@ -233,7 +198,7 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
             asm volatile("" : "+v"(ln));
             float q[3];
             sample_point(p, o3, d3, ts[s], q);
-            // gamma_q = coord_scale dL/dg = -coord_scale (omega / r) (G^ - n (n . G^))
+            // gamma_q = coord_scale dL/dg = -coord_scale (omega / r) (G^ - n (n . G^))   (twin: normals_gamma_q, raymarch_normals_common.h)
             float gq[3];
             {
                 const float n3[3] = {nx[s], ny[s], nz[s]};
@@ -243,6 +208,7 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
                 for (int k = 0; k < 3; ++k) gq[k] = cf * (Gh[k] - n3[k] * ndg);
             }
             // the bilinear taps (w_k) and their derivative weights (w'_k), all three planes on every lane
+            // (twin: normals_second_taps, raymarch_normals_common.h)
             PlaneTaps taps[3], dtaps[3];
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl) {

@@ -173,6 +173,7 @@ class TriPlaneGenerator(nn.Module):
         self._planes_absmax = None               # [64] slots with max |planes| of the pass in flight (16-bit decoder)
         self._want_normals = False               # synthesis(normals=True) in flight: _forward_body takes the normal pass too ...
         self._last_normal = None                 # ... and leaves 'image_normal' here for synthesis to pick up
+        self._want_normal_camera_grad = False    # synthesis(normal_camera_grad=True) in flight: its gradient reaches the label c too
         self._want_normal_grad = False           # synthesis(normal_grad=True) in flight: 'image_normal' is an autograd output
         self._scalars: Dict[int, tuple] = {}     # id(param) -> (version, data_ptr, python float)
         self._const_nhwc: Optional[tuple] = None
@@ -741,12 +742,13 @@ class TriPlaneGenerator(nn.Module):
             raise ValueError(f"expected ws [B,{cfg.num_ws},{cfg.w_dim}] and c [B,{cfg.c_dim}], got "
                              f"{tuple(ws.shape)} and {tuple(c.shape)}")
 
-    def _check_normal_grad(self, ws, c) -> None:
+    def _check_normal_grad(self, ws, c, normal_camera_grad: bool = False) -> None:
         """The refusals of `synthesis(normal_grad=True)` under grad, before anything is launched."""
         cfg = self.cfg
-        if c.requires_grad:
-            raise NotImplementedError("TriPlaneGenerator.synthesis(normal_grad=True): the camera gradient of the normal term is not "
-                                      "implemented (c.requires_grad); detach the label, or use normals=True for a detached map")
+        if c.requires_grad and not normal_camera_grad:
+            raise NotImplementedError("TriPlaneGenerator.synthesis(normal_grad=True): the camera gradient of the normal term is opt-in "
+                                      "(c.requires_grad): pass normal_camera_grad=True for it, detach the label, or use normals=True "
+                                      "for a detached map")
         frame_bytes = cfg.neural_rendering_resolution ** 2 * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
         if ws.shape[0] * frame_bytes > RAY_STATE_CAP_BYTES:
             raise RuntimeError(f"TriPlaneGenerator.synthesis(normal_grad=True): the backward of 'image_normal' reads the ray marcher's "
@@ -809,7 +811,8 @@ class TriPlaneGenerator(nn.Module):
     def synthesis(self, ws: torch.Tensor, c: torch.Tensor, noise_mode: str = "const",
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                   return_planes: bool = False, geometry: bool = False, query: Optional[torch.Tensor] = None,
-                  normals: bool = False, normal_grad: bool = False, **_unused) -> Dict[str, torch.Tensor]:
+                  normals: bool = False, normal_grad: bool = False, normal_camera_grad: bool = False,
+                  **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
         HFA-GP), w.r.t. the generator parameters that require grad (after `tune_generator()`) and w.r.t. the camera label `c`
         when it requires grad (pose refinement; the importance depths are detached as in EG3D).
@@ -832,19 +835,25 @@ class TriPlaneGenerator(nn.Module):
         the compositing weights and through the normals themselves (the second derivative of the tri-plane gather:
         ops.raymarch_normals_bwd, one launch that joins the renderer's plane and decoder gradients before the one backbone
         backward pass; a loss that does not touch 'image_normal' launches nothing extra).  It composes with `geometry=True` and
-        `query=`.  The camera gradient of the normal term is not implemented: with `c.requires_grad` the call raises
-        NotImplementedError.  The backward reads the ray marcher's saved per-sample state: a batch whose state exceeds
+        `query=`.  The camera gradient of the normal term is opt-in: with `c.requires_grad` the call raises NotImplementedError
+        unless `normal_camera_grad=True`.
+        `normal_camera_grad=True` (implies `normal_grad=True`): a loss on 'image_normal' also reaches the camera label `c` when it
+        requires grad — pose refinement with normal-map supervision.  ops.raymarch_normals_bwd_camera adds the normal term's per-ray
+        records to those of ops.raymarch_bwd_camera and one reduction gives `c.grad` of the whole loss; a loss that does not touch
+        'image_normal', or a `c` without grad, launches nothing extra.  The backward reads the ray marcher's saved per-sample state: a batch whose state exceeds
         RAY_STATE_CAP_BYTES raises RuntimeError (fitting batches are far below it)."""
         self._check_inputs(ws, c, noise_mode)
+        normal_grad = normal_grad or normal_camera_grad
         if normals or normal_grad:    # one pass of the body below with the request set (the state of the ray marcher is shared)
             if normal_grad and torch.is_grad_enabled():
-                self._check_normal_grad(ws, c)
+                self._check_normal_grad(ws, c, normal_camera_grad)
             self._want_normals, self._last_normal = True, None
             self._want_normal_grad = bool(normal_grad)
+            self._want_normal_camera_grad = bool(normal_camera_grad)
             try:
                 out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query)
             finally:
-                self._want_normals = self._want_normal_grad = False
+                self._want_normals = self._want_normal_grad = self._want_normal_camera_grad = False
             if "image_normal" not in out:         # (a differentiable one is an output of the autograd function itself)
                 r = self.cfg.neural_rendering_resolution
                 out["image_normal"] = self._last_normal if ws.shape[0] else torch.zeros(0, 3, r, r, device=ws.device)

@@ -172,7 +172,7 @@ class _LatentBasis(nn.Module):
         return out.view(weights.shape[0], -1, self.dim) + delta.view(-1, self.dim)
 
     def get_image(self, latent: torch.Tensor, label: torch.Tensor, *, geometry: bool = False, query=None, normals: bool = False,
-                  normal_grad: bool = False, **renderer_uniforms):
+                  normal_grad: bool = False, normal_camera_grad: bool = False, **renderer_uniforms):
         """`geometry=True`: the whole synthesis dict ('image', 'image_raw', 'image_depth', 'image_mask'; depth and mask
         differentiable) instead of the image — for silhouette / depth terms of a fitting loss.
         `query=coords` [B or 1, M, 3]: the dict as well, with 'query_sigma' / 'query_rgb' at the points (`synthesis(query=)`:
@@ -180,9 +180,11 @@ class _LatentBasis(nn.Module):
         `normals=True`: the dict as well, with 'image_normal' [B,3,r,r] (`synthesis(normals=)`: world space, detached) — for
         geometry videos and shading previews (`render.normal_map`).
         `normal_grad=True`: as `normals=True` with 'image_normal' differentiable (`synthesis(normal_grad=)`) — for normal-map
-        supervision of a fitting loss."""
+        supervision of a fitting loss.
+        `normal_camera_grad=True`: as `normal_grad=True`, and the normal term also reaches a `label` that requires grad
+        (`synthesis(normal_camera_grad=)`) — pose refinement under normal-map supervision."""
         flip_label_(label)                               # in place, on the caller's tensor
-        return self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad)
+        return self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad, normal_camera_grad)
 
     def get_shape(self, latent: torch.Tensor, resolution: int = 512, **kw) -> torch.Tensor:
         """Density volume [B, N, N, N] of a fitted latent (`generator.density_grid`): the geometry next to `get_image`.
@@ -195,7 +197,7 @@ class _LatentBasis(nn.Module):
         return self.generator.extract_mesh(latent, **kw)
 
     def _synthesis(self, latent, label, renderer_uniforms, geometry: bool = False, query=None, normals: bool = False,
-                   normal_grad: bool = False):
+                   normal_grad: bool = False, normal_camera_grad: bool = False):
         """`generator.synthesis(latent, c=label, noise_mode='const')['image']` (headnerf.py:112).  `renderer_uniforms`
         (keyword-only `u_strat` [B,R,Sc], `u_imp` [B*R,Sf]) is a TEST HOOK: EG3D's renderer draws its stratified-jitter and
         importance-sampling uniforms inside the call, which makes two renders of one frame differ; a parity
@@ -204,8 +206,9 @@ class _LatentBasis(nn.Module):
         if bad:
             raise TypeError(f"unexpected keyword arguments {sorted(bad)}")
         kw = {k: v for k, v in renderer_uniforms.items() if v is not None}
-        if normal_grad:
-            return self.generator.synthesis(latent, c=label, noise_mode="const", geometry=geometry, query=query, normal_grad=True, **kw)
+        if normal_grad or normal_camera_grad:
+            return self.generator.synthesis(latent, c=label, noise_mode="const", geometry=geometry, query=query, normal_grad=True,
+                                            normal_camera_grad=normal_camera_grad, **kw)
         if normals:
             return self.generator.synthesis(latent, c=label, noise_mode="const", geometry=geometry, query=query, normals=True, **kw)
         if query is not None:
@@ -248,14 +251,15 @@ class HeadNeRF_final(_LatentBasis):
     def get_weights(self, image):
         return self.encoder(image)          # (weights, pose) when out_pose
 
-    def forward(self, image, label, person_2=False, *, geometry=False, query=None, normals=False, normal_grad=False, **renderer_uniforms):
+    def forward(self, image, label, person_2=False, *, geometry=False, query=None, normals=False, normal_grad=False,
+                normal_camera_grad=False, **renderer_uniforms):
         flip_label_(label)
         if self.out_pose:
             weights, pose = self.encoder(image)
         else:
             weights, pose = self.encoder(image), None
         latent = self.get_latent(weights, person_2)
-        img = self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad)
+        img = self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad, normal_camera_grad)
         return (img, pose) if self.out_pose else img
 
 
@@ -288,10 +292,11 @@ class _ParamDriven(_LatentBasis):
     def get_weights(self, params):
         return self.weights_3dmm(params)
 
-    def forward(self, params, label, person_2=False, *, geometry=False, query=None, normals=False, normal_grad=False, **renderer_uniforms):
+    def forward(self, params, label, person_2=False, *, geometry=False, query=None, normals=False, normal_grad=False,
+                normal_camera_grad=False, **renderer_uniforms):
         flip_label_(label)
         latent = self.get_latent(self.weights_3dmm(params), person_2)
-        return self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad)
+        return self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad, normal_camera_grad)
 
 
 class HeadNeRF_3DMM(_ParamDriven):

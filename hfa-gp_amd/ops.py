@@ -832,6 +832,44 @@ def raymarch_normals_bwd(g_normal: torch.Tensor, planes: torch.Tensor, state: to
     return d_planes, dec
 
 
+def raymarch_normals_bwd_camera(g_normal: torch.Tensor, planes: torch.Tensor, state: torch.Tensor, *,
+                                ray_grad: Optional[torch.Tensor] = None, reduce: bool = True, cam2world: torch.Tensor,
+                                intrinsics: torch.Tensor, u_strat: torch.Tensor, u_imp: torch.Tensor, dec_w0: torch.Tensor,
+                                dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, res: int, ray_start: float,
+                                ray_end: float, box_warp: float, decoder_lr_mul: float, plane_axes: int, white_back: bool,
+                                decoder_precision: str, planes_absmax: Optional[torch.Tensor] = None):
+    """The camera gradient of `raymarch_normals(planes, state, ...)` (hfagp_raymarch_normals_bwd_camera) →
+    ``(d_cam2world [B,16], d_intrinsics [B,9], ray_grad [B,R,6])``.  ``g_normal`` [B,R,3]: dL/d normal.  The sample depths carry no
+    gradient; the positions do, through the compositing weights, the decoder's curvature and the mixed second derivative of the
+    bilinear tap weights (include/hfagp.h has the formulas).
+
+      * ``ray_grad``: a [B,R,6] tensor the per-ray records (d origin, d direction) are ADDED to — the one `raymarch_bwd_camera`
+        returned, so that one reduction serves the whole loss; None = a fresh tensor that is written.
+      * ``reduce``: run the reduction over the final ``ray_grad``; False returns (None, None, ray_grad).
+    A ray whose ``g_normal`` is exactly zero adds nothing (writes zeros into a fresh tensor).  No atomics: two calls return the same
+    bits.  The other keywords are the forward's; pass its ``planes_absmax``."""
+    if state is None:
+        raise RuntimeError("raymarch_normals_bwd_camera: state must be the `raymarch_state` buffer the forward call filled, got None")
+    a = L.RaymarchArgs()
+    b, _, _, r, _, _ = _ray_args("raymarch_normals_bwd_camera", a, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0, dec_w1,
+                                 dec_b1, res, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision,
+                                 planes_absmax, state)
+    if _chk(g_normal, "raymarch_normals_bwd_camera: g_normal").shape != (b, r, 3):
+        raise RuntimeError(f"raymarch_normals_bwd_camera: g_normal must be [B, R, 3] = [{b}, {r}, 3], got {tuple(g_normal.shape)}")
+    accumulate = ray_grad is not None
+    if ray_grad is None:
+        ray_grad = torch.empty(b, r, 6, device=planes.device, dtype=torch.float32)
+    elif _chk(ray_grad, "raymarch_normals_bwd_camera: ray_grad").shape != (b, r, 6):
+        raise RuntimeError(f"raymarch_normals_bwd_camera: ray_grad must be [B, R, 6] = [{b}, {r}, 6], got {tuple(ray_grad.shape)}")
+    d_c2w = torch.empty(b, 16, device=planes.device, dtype=torch.float32) if reduce else None
+    d_intr = torch.empty(b, 9, device=planes.device, dtype=torch.float32) if reduce else None
+    if b == 0:
+        return d_c2w, d_intr, ray_grad
+    L.check(L.lib().hfagp_raymarch_normals_bwd_camera(C.byref(a), _ptr(g_normal), _ptr(ray_grad), int(accumulate), _ptr(d_c2w),
+                                                      _ptr(d_intr), _stream()), "raymarch_normals_bwd_camera")
+    return d_c2w, d_intr, ray_grad
+
+
 def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *, grid=None, dec_w0: torch.Tensor,
                  dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, box_warp: float, plane_axes,
                  decoder_lr_mul: float, decoder_precision: str, planes_absmax: Optional[torch.Tensor] = None,
@@ -1521,11 +1559,12 @@ def _raymarch_bwd_frames(*, g_feat, planes, cam2world, intrinsics, u_strat, u_im
 def raymarch_bwd_camera(g_feat: Optional[torch.Tensor], planes: torch.Tensor, rec: torch.Tensor, cam2world, intrinsics, u_strat,
                         u_imp, dec_w0, dec_b0, dec_w1, dec_b1, res: int, ray_start: float, ray_end: float, box_warp: float,
                         decoder_lr_mul: float = 1.0, plane_axes: int = 0, white_back: bool = False,
-                        decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None):
+                        decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None, reduce: bool = True):
     """The camera gradient of the renderer (hfagp_raymarch_bwd_camera) → (d cam2world [B,16], d intrinsics [B,9], ray_grad [B,R,6]:
     d origin, d direction per ray).  ``g_feat`` and the other arguments as in the `raymarch_bwd` call that wrote ``rec`` (its
     ``rec_out=`` / ``return_rec=True``): the depth, opacity and white_back terms are already in the records.  Independent of which
-    pass-2 form that call ran; no atomics, two calls return the same bits."""
+    pass-2 form that call ran; no atomics, two calls return the same bits.  ``reduce=False``: the per-ray records alone, (None, None,
+    ray_grad) — for `raymarch_normals_bwd_camera(..., ray_grad=ray_grad)`, whose reduction then serves both."""
     a = L.RaymarchBwdArgs()
     b, _, _, r, sc, sf = _ray_args("raymarch_bwd_camera", a.fwd, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1,
                                    res, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision, planes_absmax,
@@ -1535,8 +1574,8 @@ def raymarch_bwd_camera(g_feat: Optional[torch.Tensor], planes: torch.Tensor, re
         raise RuntimeError(f"raymarch_bwd_camera: rec must be [B, R, Sc + Sf, 4] = [{b}, {r}, {sc + sf}, 4], got {tuple(rec.shape)}")
     if g_feat is not None and _chk(g_feat, "raymarch_bwd_camera: g_feat").shape != (b, r, 32):
         raise RuntimeError(f"raymarch_bwd_camera: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
-    d_c2w = torch.empty(b, 16, device=dev, dtype=torch.float32)
-    d_intr = torch.empty(b, 9, device=dev, dtype=torch.float32)
+    d_c2w = torch.empty(b, 16, device=dev, dtype=torch.float32) if reduce else None
+    d_intr = torch.empty(b, 9, device=dev, dtype=torch.float32) if reduce else None
     ray_grad = torch.empty(b, r, 6, device=dev, dtype=torch.float32)
     if b == 0:
         return d_c2w, d_intr, ray_grad

@@ -31,6 +31,7 @@
  *   hfagp_raymarch_normals  <- (no reference counterpart: the per-ray surface normal map of EG3D-family geometry renders — the
  *                              density gradient of every sample composited with MipRayMarcher2's weights)
  *   hfagp_raymarch_normals_bwd <- (none either: what autograd would do with a normal-map loss on such a render)
+ *   hfagp_raymarch_normals_bwd_camera <- (none either: the same loss's gradient w.r.t. the camera label)
  *   hfagp_depth_clamp       <- MipRayMarcher2's torch.clamp(depth, min sample depth, max sample depth) over the batch, one launch (ABI 10)
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
@@ -158,6 +159,32 @@ int hfagp_raymarch_normals_bwd(const HfagpRaymarchArgs* fwd, const float* g_norm
                                float* d_planes /* [B][3][H][W][32], accumulated into */,
                                float* d_dec_w0, float* d_dec_b0, float* d_dec_w1, float* d_dec_b1 /* all four or none; accumulated */,
                                void* stream);
+
+/* Camera gradient of hfagp_raymarch_normals (additive to ABI 15): from g_normal = dL/d normal to the per-ray record
+ * ray_grad[b][r][0..5] = (dL/d origin, dL/d direction) of hfagp_raymarch_bwd_camera and, through the same reduction, to
+ * d_cam2world [B][16] and d_intrinsics [B][9].  Call it after hfagp_raymarch_fwd with fwd->state given, on the same stream.  The
+ * sample depths t carry no gradient; per sample q = (2 / box_warp)(o + t d).  With a, g, r, n, d sigma_s, gamma, w'_k, u, v, e of
+ * hfagp_raymarch_normals_bwd, gamma_q = (2 / box_warp) gamma, (cx, cy) the components of gamma_q a plane's two grid coordinates
+ * (gx, gy) carry, x = wsig * sigmoid(hp) * d sigma_s + e and dF = W0'^T x, the positional gradient is, per plane in grid units,
+ *   dL/dgx = sum_k (texel_k . dF) dw_k/dgx / 3 + m cy,      dL/dgy = sum_k (texel_k . dF) dw_k/dgy / 3 + m cx,
+ *   m = (W / 2)(H / 2) sum_k s_k ok_k (texel_k . a) / 3,    s = (+1, -1, -1, +1) for the taps nw, ne, sw, se
+ * (bilinear weights have no pure second derivative, only d2 w_k / dgx dgy = s_k; ok_k = 0 for a tap outside the plane), routed to
+ * the three axes of q as plane_axes projects them; dL/dp = (2 / box_warp) dL/dq, and per ray
+ *   ray_grad = (sum_s dL/dp_s, sum_s t_s dL/dp_s).
+ * accumulate != 0: the six floats are ADDED to what ray_grad holds (one plain load, add, store per ray) -- after
+ * hfagp_raymarch_bwd_camera on the same buffer, so that one reduction serves the whole loss; 0: they are written (zeros for a ray
+ * whose g_normal is exactly 0, which is otherwise skipped).  d_cam2world and d_intrinsics: both or neither; when given,
+ * the reduction of hfagp_raymarch_bwd_camera runs on the final ray_grad.  One writer per ray, no atomics: two calls give the same
+ * bits.  Decoder arithmetic: the forward products (hp) as hfagp_raymarch_fwd (split 16-bit operands given planes_absmax, exact fp32
+ * without it); the second-order products AND a = W0'^T (wsig * sigmoid(hp)) on the exact fp32 matrix instructions with either
+ * decoder.  Unlike hfagp_raymarch_normals / hfagp_raymarch_normals_bwd, which take a from split-bf16 parts (2^-16 per product)
+ * with the 16-bit decoder, the n this entry forms there is the forward's to ~2^-16, not to the bit: that error has one sign over
+ * neighbouring rays and would not average out in the reduction over a frame.
+ * HFAGP_EBADARG, nothing launched: fwd, fwd->state, fwd->planes, g_normal or ray_grad NULL, or only one of d_cam2world /
+ * d_intrinsics given (then the checks of hfagp_raymarch_fwd); HFAGP_EUNSUPPORTED: sample counts.                               */
+int hfagp_raymarch_normals_bwd_camera(const HfagpRaymarchArgs* fwd, const float* g_normal /* [B][R][3] */,
+                                      float* ray_grad /* [B][R][6] */, int accumulate,
+                                      float* d_cam2world, float* d_intrinsics, void* stream);
 
 /* ------------------------------------------------------------------ point queries (ABI 13)
  * The decoder at arbitrary points, no compositing: per point the same tri-plane gather and OSGDecoder the ray marcher runs,
