@@ -190,6 +190,8 @@ SYMBOLS = {
     "hfagp_raymarch_normals_bwd_camera": (C.c_int, [C.POINTER(RaymarchArgs), C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 3),
     "hfagp_planes_query": (C.c_int, [C.POINTER(PlanesQueryArgs), C.c_void_p]),
     "hfagp_planes_query_bwd": (C.c_int, [C.POINTER(PlanesQueryBwdArgs), C.c_void_p]),
+    "hfagp_planes_query_normals": (C.c_int, [C.POINTER(PlanesQueryArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hfagp_planes_query_normals_bwd": (C.c_int, [C.POINTER(PlanesQueryBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hfagp_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "hfagp_marching_cubes_count": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),
     "hfagp_marching_cubes_emit": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),

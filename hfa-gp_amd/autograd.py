@@ -358,6 +358,15 @@ def _query_backward(gen, planes, coords, pam, g_sigma, g_rgb, d_planes, need_coo
     return d_planes, d_co
 
 
+def _query_normals_backward(gen, planes, coords, pam, g_grad, g_normal, d_planes, dec):
+    """ops.planes_query_normals_bwd of a query that rode on `planes`: the plane gradient is added INTO d_planes (None: fresh zeros)
+    and the decoder gradients into the tensors `dec` (None: the generator is frozen) → d_planes."""
+    b, m = planes.shape[0], coords.shape[1]
+    g_grad, g_normal = (None if g is None else g.float().reshape(b, m, 3).contiguous() for g in (g_grad, g_normal))
+    return ops.planes_query_normals_bwd(planes, coords, g_grad, g_normal, planes_absmax=pam, d_planes=d_planes,
+                                        decoder_grads=dec is not None, dec_out=dec, **gen._query_kwargs())[0]
+
+
 class SynthesisFn(torch.autograd.Function):
     """inputs: ws, c, u_strat, u_imp, gen, *generator parameters (listed only so that autograd can hand their
     gradients back when the generator is being tuned; the forward reads them from `gen`)."""
@@ -367,7 +376,7 @@ class SynthesisFn(torch.autograd.Function):
         return SynthesisFn._forward(ctx, False, ws, c, u_strat, u_imp, gen, params)
 
     @staticmethod
-    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params, query=None, normal=False):
+    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params, query=None, normal=False, query_normals=False):
         tape = {}
         ws_c = ws.detach().float().contiguous()
         with torch.no_grad():
@@ -375,8 +384,13 @@ class SynthesisFn(torch.autograd.Function):
                                                                              u_imp, tape, geometry)
             if query is not None:                    # points evaluated on this call's planes (synthesis(query=))
                 tape["query"] = query.detach().float().contiguous()
-                q_sigma, q_rgb = ops.planes_query(planes, tape["query"], planes_absmax=tape.get("planes_absmax"),
-                                                  **gen._query_kwargs())
+                if query_normals:                    # synthesis(query_normals=True): the same launch slot, four outputs
+                    q = gen._timed("planes_query_normals", float(planes.shape[0]), ops.planes_query_normals, planes, tape["query"],
+                                   planes_absmax=tape.get("planes_absmax"), **gen._query_kwargs())
+                    q_sigma, q_rgb, q_grad, q_normal = q["sigma"], q["rgb"], q["grad"], q["normal"]
+                else:
+                    q_sigma, q_rgb = ops.planes_query(planes, tape["query"], planes_absmax=tape.get("planes_absmax"),
+                                                      **gen._query_kwargs())
         gen._last_extras = (planes, feat_img)        # for synthesis(return_planes=True)
         ctx.gen, ctx.tape, ctx.ws_c = gen, tape, ws_c
         ctx.params = params
@@ -395,11 +409,12 @@ class SynthesisFn(torch.autograd.Function):
         if query is not None:
             ctx.set_materialize_grads(False)
             ctx.q_dtype = query.dtype
+            q_more = (q_grad, q_normal) if query_normals else ()
             if geometry:
-                return img, rgb_raw, depth, mask[0], q_sigma, q_rgb
+                return (img, rgb_raw, depth, mask[0], q_sigma, q_rgb) + q_more
             no_mask = depth.new_empty(0)             # (a fixed number of outputs; without geometry=True the dict has no 'image_mask'
             ctx.mark_non_differentiable(depth, no_mask)      # and the depth carries no gradient, as in a call without query)
-            return img, rgb_raw, depth, no_mask, q_sigma, q_rgb
+            return (img, rgb_raw, depth, no_mask, q_sigma, q_rgb) + q_more
         if geometry:
             ctx.set_materialize_grads(False)         # an output the loss does not use hands backward None, not a zero image
             return img, rgb_raw, depth, mask[0]
@@ -413,7 +428,8 @@ class SynthesisFn(torch.autograd.Function):
         return (d_ws, d_c, None, None, None) + pgrads
 
     @staticmethod
-    def _backward(ctx, g_img, g_raw, g_depth, g_mask=None, g_qsigma=None, g_qrgb=None, need_coords=False, g_normal=None):
+    def _backward(ctx, g_img, g_raw, g_depth, g_mask=None, g_qsigma=None, g_qrgb=None, need_coords=False, g_normal=None,
+                  g_qgrad=None, g_qnormal=None):
         gen, tape = ctx.gen, ctx.tape
         if tape is None:
             raise RuntimeError("TriPlaneGenerator.synthesis: backward called a second time — the saved activations "
@@ -487,6 +503,11 @@ class SynthesisFn(torch.autograd.Function):
             _, d_coords = gen._timed("planes_query_bwd", float(b), _query_backward, gen, tape["planes"], tape["query"],
                                      tape.get("planes_absmax"), g_qsigma, g_qrgb, rb[0] if ctx.pg else rb, need_coords,
                                      rb[1] if ctx.pg else None)
+        if g_qgrad is not None or g_qnormal is not None:
+            # 'query_sigma_grad' / 'query_normal' of synthesis(query_normals=True): one launch that adds into the same d_planes and
+            # decoder gradients, after raymarch_bwd for the point query's reason (it adds to every plane at its true texels)
+            gen._timed("planes_query_normals_bwd", float(b), _query_normals_backward, gen, tape["planes"], tape["query"],
+                       tape.get("planes_absmax"), g_qgrad, g_qnormal, rb[0] if ctx.pg else rb, rb[1] if ctx.pg else None)
         if g_normal is not None:
             # 'image_normal' of synthesis(normal_grad=True): one launch that adds into the renderer's d_planes and decoder gradients,
             # after raymarch_bwd for the same reason as the point query (it adds to every plane at its true texels)
@@ -536,6 +557,24 @@ class SynthesisQueryFn(SynthesisFn):
         if d_coords is not None:
             d_coords = d_coords.to(ctx.q_dtype)
         return (d_ws, d_c, None, None, d_coords, None, None) + pgrads
+
+
+class SynthesisQueryNormalFn(SynthesisFn):
+    """`synthesis(query=coords, query_normals=True)`: the inputs of SynthesisQueryFn; outputs image, image_raw, image_depth,
+    image_mask, query_sigma, query_rgb, query_sigma_grad [B,M,3], query_normal [B,M,3].  The gradients of the last two reach the
+    planes and the decoder through ops.planes_query_normals_bwd after ops.raymarch_bwd and the point query's backward, into their
+    d_planes and decoder gradients: one backbone pass serves every loss term.  The points get no gradient from these two outputs
+    (synthesis refuses points that require grad)."""
+    @staticmethod
+    def forward(ctx, ws, c, u_strat, u_imp, coords, geometry, gen, *params):
+        return SynthesisFn._forward(ctx, bool(geometry), ws, c, u_strat, u_imp, gen, params, query=coords, query_normals=True)
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, g_qgrad, g_qnormal):
+        d_ws, d_c, _, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, False, None,
+                                                     g_qgrad, g_qnormal)
+        return (d_ws, d_c, None, None, None, None, None) + pgrads
 
 
 class SynthesisNormalFn(SynthesisFn):
@@ -603,3 +642,56 @@ class SampleMixedFn(torch.autograd.Function):
             d_coords = d_coords.to(ctx.q_dtype)
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
         return (d_ws, d_coords, None) + pgrads
+
+
+class SampleMixedNormalFn(torch.autograd.Function):
+    """`sample_mixed(..., normals=True, differentiable=True)` on its own: inputs ws, coords, gen, *parameters; outputs sigma, rgb,
+    sigma_grad [B,M,3], normal [B,M,3].  A backbone forward with a tape, one launch (ops.planes_query_normals); backward =
+    ops.planes_query_bwd for sigma / rgb if the loss used them, then ops.planes_query_normals_bwd into the same buffers, then the
+    backbone backward `synthesis` runs.  The points get no gradient (sample_mixed refuses points that require grad)."""
+    @staticmethod
+    def forward(ctx, ws, coords, gen, *params):
+        ws_c = ws.detach().float().contiguous()
+        co = coords.detach().float().contiguous()
+        tape = []
+        with torch.no_grad():
+            planes = gen.backbone_planes(ws_c, tape)
+            pam = getattr(gen, "_planes_absmax", None)
+            q = gen._timed("planes_query_normals", float(planes.shape[0]), ops.planes_query_normals, planes, co, planes_absmax=pam,
+                           **gen._query_kwargs())
+        ctx.gen, ctx.tape, ctx.ws_c, ctx.co, ctx.planes, ctx.pam = gen, tape, ws_c, co, planes, pam
+        ctx.params = params
+        ctx.pg = any(p.requires_grad for p in params)
+        ctx.ws_shape = ws.shape
+        ctx.set_materialize_grads(False)
+        return q["sigma"], q["rgb"], q["grad"], q["normal"]
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_sigma, g_rgb, g_grad, g_normal):
+        gen = ctx.gen
+        if ctx.tape is None:
+            raise RuntimeError("TriPlaneGenerator.sample_mixed: backward called a second time — the saved activations are released "
+                               "by the first backward pass (retain_graph is not supported)")
+        none = (None,) * (3 + len(ctx.params))
+        if g_sigma is None and g_rgb is None and g_grad is None and g_normal is None:
+            return none
+        planes = ctx.planes
+        b, dev = planes.shape[0], planes.device
+        d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
+        bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
+        dec_prm = gen.decoder_params()
+        dec = tuple(torch.zeros_like(p) for p in dec_prm) if ctx.pg else None
+        d_planes = None
+        if g_sigma is not None or g_rgb is not None:
+            d_planes, _ = _query_backward(gen, planes, ctx.co, ctx.pam, g_sigma, g_rgb, None, False, dec)
+        if g_grad is not None or g_normal is not None:
+            d_planes = gen._timed("planes_query_normals_bwd", float(b), _query_normals_backward, gen, planes, ctx.co, ctx.pam, g_grad,
+                                  g_normal, d_planes, dec)
+        if ctx.pg:
+            for prm, g in zip(dec_prm, dec):
+                bw._acc(prm, g)
+        _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
+        ctx.tape = ctx.planes = None
+        pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
+        return (d_ws, None, None) + pgrads

@@ -37,6 +37,8 @@ units+=(planes_query_bwd)
 units+=(raymarch_normals)
 units+=(raymarch_normals_bwd)
 units+=(raymarch_normals_camera)
+units+=(planes_query_normals)
+units+=(planes_query_normals_bwd)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

@@ -13,6 +13,7 @@
 //   decoder_dh_lds          dH alone (raymarch_normals_camera.hip)
 //   publish_taps2 / scatter_tile_runs2 / w0_mul / w0t_mul / nrm_grad_*     second order (raymarch_normals_bwd.hip): the scatter
 //                           with two value / weight sets, the fp32 products with W0', the weight-gradient sums
+//   build_w0_lds            the fp32 A operands of W0' for w0_mul next to a 16-bit forward image (planes_query_normals_bwd.hip)
 #pragma once
 #include "raymarch_common.h"
 
@@ -625,6 +626,16 @@ __device__ __forceinline__ void w0_mul(const float* w0f, int lane, const float u
     }
 }
 
+// the fp32 A operands of W0' for w0_mul where the forward image is the 16-bit one (rows 0-31 of the fp32 image of
+// store_decoder_lds otherwise), built by all `nthreads` threads of the block: w0f[mt * 8 + t][lane] = W0[16 mt + j][8 g + t] * g0
+__device__ __forceinline__ void build_w0_lds(const HfagpRaymarchArgs& a, float* w0f, int tid, int nthreads) {
+    const float g0 = a.decoder_lr_mul * 0.17677669529663687f;
+    for (int i = tid; i < 32 * 64; i += nthreads) {
+        const int l = i & 63, row = i >> 6;              // row = mt * 8 + t
+        w0f[i] = a.dec_w0[(16 * (row >> 3) + (l & 15)) * 32 + 8 * (l >> 4) + (row & 7)] * g0;
+    }
+}
+
 // operand images of the sample-contracting products  dW0'[64x32] += x[64x16] . F[16x32] + dH[64x16] . u[16x32]
 struct NrmGradLds {
     float x[64 * 17], dh[64 * 17], f[16 * 33], u[16 * 33];
@@ -675,7 +686,9 @@ __device__ __forceinline__ void nrm_grad_tile(NrmGradAcc& acc, NrmGradLds& gl, i
     }
 }
 
-// end of the kernel: one set of atomics per wave, with the gains of dec_grad_flush; the colour rows of the second layer get nothing
+// end of the kernel: one set of atomics per wave, with the gains of dec_grad_flush; the colour rows of the second layer get nothing.
+// SIGMA_BIAS = false: a caller without a first-order d sigma (planes_query_normals_bwd.hip) leaves d_dec_b1 alone altogether.
+template <bool SIGMA_BIAS = true>
 __device__ __forceinline__ void nrm_grad_flush(const NrmGradAcc& acc, const DecGrads& dg, float lr_mul, int lane) {
     const int j = lane & 15, g = lane >> 4;
     const float g0 = lr_mul * 0.17677669529663687f, g1 = lr_mul * 0.125f, gb = lr_mul;
@@ -700,8 +713,10 @@ __device__ __forceinline__ void nrm_grad_flush(const NrmGradAcc& acc, const DecG
                 unsafeAtomicAdd(dg.w1 + 16 * mt + 4 * g + r, vw * g1);          // sigma row of W1
             }
         }
-    const float vs = red16(acc.s_ds);
-    if (lane == 0) unsafeAtomicAdd(dg.b1, vs * gb);
+    if constexpr (SIGMA_BIAS) {
+        const float vs = red16(acc.s_ds);
+        if (lane == 0) unsafeAtomicAdd(dg.b1, vs * gb);
+    }
 }
 
 }  // namespace hfagp

@@ -3,6 +3,7 @@
 //   Composite / composite / midpoints_to_samples    the forward's compositing over the S-1 midpoints (the same bits)
 //   normals_load_ray        sorted depths and raw densities of a ray from the forward's state
 //   normals_pass_a          pass A: n_s and 1 / r_s of every sample (a in fp32 with either decoder)
+//   point_density_grad      g and 1 / r of one point per lane from a (the point queries: planes_query_normals[_bwd].hip)
 //   normals_weight_adjoint  the compositing adjoint with the normals as colours: d sigma_s by sorted position
 //   normals_gamma_q         gamma_q = coord_scale dL/dg of a sample
 //   normals_second_taps     the bilinear taps w_k and their derivative weights w'_k, all three planes
@@ -116,6 +117,24 @@ __device__ __forceinline__ void normals_pass_a(const RayParams& p, int b, const 
             ri[s] = rs;
         }
     }
+}
+
+// ---- a point as a ray sample (planes_query_normals.hip and its backward): pass A's lines from a to g and 1 / r for ONE point
+// per lane at the normalised position q.  av = a = W0'^T (wsig * sigmoid(hp)) of this lane's channels (w0t_mul); gw = g =
+// coord_scale J^T a in world units on all four lanes of the point; returns 1 / r = rsqrt(g.g + 1e-12), so n = -(1 / r) g.
+__device__ __forceinline__ float point_density_grad(const HfagpRaymarchArgs& a, int b, int g, const float q[3], const f32x4 av[2],
+                                                    float sx, float sy, float coord_scale, float gw[3]) {
+    float dq[3];
+    gather_position_grad(a, b, g, q, av, sx, sy, dq);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float v = dq[k];
+        v += __shfl_xor(v, 16);
+        v += __shfl_xor(v, 32);
+        gw[k] = v * coord_scale;
+    }
+    const float gg2 = fmaf(gw[2], gw[2], fmaf(gw[1], gw[1], gw[0] * gw[0]));
+    return __builtin_amdgcn_rsqf(gg2 + 1e-12f);
 }
 
 // ---- the compositing adjoint (raymarch.hip) with the normals as colours: G_e = G^ . (n_e + n_{e+1}) / 2 -> d sigma_s by sorted

@@ -812,7 +812,7 @@ class TriPlaneGenerator(nn.Module):
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                   return_planes: bool = False, geometry: bool = False, query: Optional[torch.Tensor] = None,
                   normals: bool = False, normal_grad: bool = False, normal_camera_grad: bool = False,
-                  **_unused) -> Dict[str, torch.Tensor]:
+                  query_normals: bool = False, **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
         HFA-GP), w.r.t. the generator parameters that require grad (after `tune_generator()`) and w.r.t. the camera label `c`
         when it requires grad (pose refinement; the importance depths are detached as in EG3D).
@@ -841,9 +841,26 @@ class TriPlaneGenerator(nn.Module):
         requires grad — pose refinement with normal-map supervision.  ops.raymarch_normals_bwd_camera adds the normal term's per-ray
         records to those of ops.raymarch_bwd_camera and one reduction gives `c.grad` of the whole loss; a loss that does not touch
         'image_normal', or a `c` without grad, launches nothing extra.  The backward reads the ray marcher's saved per-sample state: a batch whose state exceeds
-        RAY_STATE_CAP_BYTES raises RuntimeError (fitting batches are far below it)."""
+        RAY_STATE_CAP_BYTES raises RuntimeError (fitting batches are far below it).
+        `query_normals=True` (with `query=`): the dict also has 'query_sigma_grad' [B,M,3], ∂σ/∂x of the raw density at the points in
+        world units, and 'query_normal' [B,M,3], n = −∇σ·rsqrt(‖∇σ‖² + 1e-12) — the bits of `sample_mixed(normals=True)` — from the
+        same single launch (ops.planes_query_normals), differentiable w.r.t. `ws` and the generator parameters that require grad:
+        normal smoothness, gradient-norm penalties and normal agreement with a scan join the renderer's plane and decoder gradients
+        (ops.planes_query_normals_bwd, after the query's own backward) before the one backbone backward pass; a loss that does not
+        touch the two keys launches nothing extra.  It composes with `geometry=True` and `normals=True`.  The two outputs have no
+        gradient w.r.t. the points: under grad a `query` that requires grad raises NotImplementedError, and so does the combination
+        with `normal_grad=True` / `normal_camera_grad=True`."""
         self._check_inputs(ws, c, noise_mode)
         normal_grad = normal_grad or normal_camera_grad
+        if query_normals:
+            if query is None:
+                raise ValueError("TriPlaneGenerator.synthesis: query_normals=True needs query=coords")
+            if normal_grad:
+                raise NotImplementedError("TriPlaneGenerator.synthesis: query_normals=True together with normal_grad=True / "
+                                          "normal_camera_grad=True is not implemented")
+            if torch.is_grad_enabled() and query.requires_grad:
+                raise NotImplementedError("TriPlaneGenerator.synthesis: 'query_sigma_grad' / 'query_normal' have no gradient w.r.t. the "
+                                          "points (it needs the mixed second derivative of the gather); detach `query`")
         if normals or normal_grad:    # one pass of the body below with the request set (the state of the ray marcher is shared)
             if normal_grad and torch.is_grad_enabled():
                 self._check_normal_grad(ws, c, normal_camera_grad)
@@ -851,7 +868,7 @@ class TriPlaneGenerator(nn.Module):
             self._want_normal_grad = bool(normal_grad)
             self._want_normal_camera_grad = bool(normal_camera_grad)
             try:
-                out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query)
+                out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query, query_normals=query_normals)
             finally:
                 self._want_normals = self._want_normal_grad = self._want_normal_camera_grad = False
             if "image_normal" not in out:         # (a differentiable one is an output of the autograd function itself)
@@ -870,6 +887,9 @@ class TriPlaneGenerator(nn.Module):
                 zero = 0.0 * query.sum() if query.requires_grad else 0.0
                 out["query_sigma"] = torch.zeros(ws.shape[0], query.shape[1], 1, device=ws.device) + zero
                 out["query_rgb"] = torch.zeros(ws.shape[0], query.shape[1], 32, device=ws.device) + zero
+                if query_normals:
+                    for k in ("query_sigma_grad", "query_normal"):
+                        out[k] = torch.zeros(ws.shape[0], query.shape[1], 3, device=ws.device)
                 return out
         if ws.shape[0] == 0:          # empty batch (ragged last batch of a frame shard): nothing to launch
             cfg, dev = self.cfg, ws.device
@@ -897,6 +917,15 @@ class TriPlaneGenerator(nn.Module):
                 if query is not None:
                     out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
                 out["image_normal"] = normal
+            elif query is not None and query_normals:
+                from .autograd import SynthesisQueryNormalFn
+                img, rgb_raw, depth, mask, q_sigma, q_rgb, q_grad, q_normal = SynthesisQueryNormalFn.apply(
+                    ws, c_in, u_strat, u_imp, query, geometry, self, *params)
+                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
+                if geometry:
+                    out["image_mask"] = mask
+                out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
+                out["query_sigma_grad"], out["query_normal"] = q_grad, q_normal
             elif query is not None:
                 from .autograd import SynthesisQueryFn
                 img, rgb_raw, depth, mask, q_sigma, q_rgb = SynthesisQueryFn.apply(ws, c_in, u_strat, u_imp, query, geometry, self,
@@ -919,7 +948,12 @@ class TriPlaneGenerator(nn.Module):
         with torch.no_grad():
             img, rgb_raw, depth, planes, feat_img, *mask = self._forward_impl(
                 ws.detach().float().contiguous(), c.detach().float().contiguous(), u_strat, u_imp, None, geometry)
-            if query is not None:
+            if query is not None and query_normals:
+                q = self._timed("planes_query_normals", float(ws.shape[0]), ops.planes_query_normals, planes,
+                                query.detach().float().contiguous(), planes_absmax=getattr(self, "_planes_absmax", None),
+                                **self._query_kwargs())
+                q_sigma, q_rgb = q["sigma"], q["rgb"]
+            elif query is not None:
                 q_sigma, q_rgb = ops.planes_query(planes, query.detach().float().contiguous(),
                                                   planes_absmax=getattr(self, "_planes_absmax", None), **self._query_kwargs())
         out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
@@ -927,6 +961,8 @@ class TriPlaneGenerator(nn.Module):
             out["image_mask"] = mask[0]
         if query is not None:
             out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
+            if query_normals:
+                out["query_sigma_grad"], out["query_normal"] = q["grad"], q["normal"]
         if return_planes:
             out["planes"] = planes
             out["feature_image"] = feat_img
@@ -984,7 +1020,7 @@ class TriPlaneGenerator(nn.Module):
 
     def sample_mixed(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], ws: torch.Tensor,
                      truncation_psi=1, truncation_cutoff=None, update_emas=False, *, differentiable: bool = False,
-                     **synthesis_kwargs) -> Dict[str, torch.Tensor]:
+                     normals: bool = False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:
         """EG3D TriPlaneGenerator.sample_mixed: the raw decoder outputs at `coordinates` [B or 1, M, 3] (world units) of the
         tri-planes of `ws` → {'rgb': [B,M,32], 'sigma': [B,M,1]} (sigma before the renderer's softplus).  `directions` is
         shape-checked and ignored (OSGDecoder does not read it); the truncation arguments are EG3D's and unused here, as
@@ -993,7 +1029,12 @@ class TriPlaneGenerator(nn.Module):
         parameters that require grad and `coordinates` when it requires grad, at the price of a backbone backward pass of its
         own — a loss that also renders should use `synthesis(query=)`, which shares the image's pass.  Inside a trainer step
         scope (a gradient sink, or gradients accumulated in place) the stand-alone form raises: a second pass would hand every
-        parameter to the sink twice."""
+        parameter to the sink twice.
+        `normals=True`: the dict also has 'sigma_grad' [B,M,3], ∂σ/∂x of the raw density in world units, and 'normal' [B,M,3],
+        n = −∇σ·rsqrt(‖∇σ‖² + 1e-12) (from dense to empty; exact zeros outside every plane), from the same single launch
+        (ops.planes_query_normals; 'sigma' / 'rgb' keep their bits).  With `differentiable=True` both are differentiable w.r.t. `ws`
+        and the generator parameters that require grad (ops.planes_query_normals_bwd), NOT w.r.t. the points: under grad,
+        `coordinates` that require grad raise NotImplementedError."""
         noise_mode = synthesis_kwargs.get("noise_mode", "const")
         if noise_mode != "const":
             raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
@@ -1004,11 +1045,20 @@ class TriPlaneGenerator(nn.Module):
         params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
         grad = differentiable and torch.is_grad_enabled() and (ws.requires_grad or coordinates.requires_grad or
                                                                any(p.requires_grad for p in params))
+        if normals:
+            if torch.is_grad_enabled() and coordinates.requires_grad:
+                raise NotImplementedError("TriPlaneGenerator.sample_mixed(normals=True): 'sigma_grad' / 'normal' have no gradient w.r.t. "
+                                          "the points (it needs the mixed second derivative of the gather); detach `coordinates`")
+            if not coordinates.is_cuda:
+                raise RuntimeError("TriPlaneGenerator.sample_mixed: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
         self._query_guard("sample_mixed", ws, *(() if differentiable else (coordinates,)), differentiable=differentiable)
         b, m = ws.shape[0], coordinates.shape[1]
         if b == 0 or m == 0:
             zero = 0.0 * ws.sum() + 0.0 * coordinates.sum() if grad else 0.0       # keeps the autograd edges
-            return {"rgb": torch.zeros(b, m, 32, device=ws.device) + zero, "sigma": torch.zeros(b, m, 1, device=ws.device) + zero}
+            out = {"rgb": torch.zeros(b, m, 32, device=ws.device) + zero, "sigma": torch.zeros(b, m, 1, device=ws.device) + zero}
+            if normals:
+                out.update(sigma_grad=torch.zeros(b, m, 3, device=ws.device) + zero, normal=torch.zeros(b, m, 3, device=ws.device) + zero)
+            return out
         if grad:
             if getattr(self, "_grad_sink", None) is not None or getattr(self, "_grad_inplace", False):
                 raise RuntimeError("TriPlaneGenerator.sample_mixed(differentiable=True) inside a trainer step scope: its backward is "
@@ -1016,11 +1066,19 @@ class TriPlaneGenerator(nn.Module):
                                    "evaluate the points with `synthesis(..., query=coordinates)` instead")
             if not coordinates.is_cuda:
                 raise RuntimeError("TriPlaneGenerator.sample_mixed: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
+            if normals:
+                from .autograd import SampleMixedNormalFn
+                sigma, rgb, sigma_grad, normal = SampleMixedNormalFn.apply(ws, coordinates, self, *params)
+                return {"rgb": rgb, "sigma": sigma, "sigma_grad": sigma_grad, "normal": normal}
             from .autograd import SampleMixedFn
             sigma, rgb = SampleMixedFn.apply(ws, coordinates, self, *params)
             return {"rgb": rgb, "sigma": sigma}
         with torch.no_grad():
             planes, pam = self._query_planes(ws)
+            if normals:
+                q = self._timed("planes_query_normals", float(b), ops.planes_query_normals, planes,
+                                coordinates.detach().float().contiguous(), planes_absmax=pam, **self._query_kwargs())
+                return {"rgb": q["rgb"], "sigma": q["sigma"], "sigma_grad": q["grad"], "normal": q["normal"]}
             sigma, rgb = ops.planes_query(planes, coordinates.detach().float().contiguous(), planes_absmax=pam,
                                           **self._query_kwargs())
         return {"rgb": rgb, "sigma": sigma}
@@ -1066,13 +1124,15 @@ class TriPlaneGenerator(nn.Module):
                              out=vol[:, x0:x0 + xc], **kw)
 
     def extract_mesh(self, ws: torch.Tensor, resolution: int = 512, level: float = 10.0, cube_length: Optional[float] = None,
-                     max_points: Optional[int] = None, colors: bool = False):
+                     max_points: Optional[int] = None, colors: bool = False, normals: bool = False):
         """Surface meshes of the heads of `ws`: `density_grid`, EG3D's border trim (voxels within int(30 N / 256) of a face
         set to -1000; no flip), then marching cubes at `level` (ops.marching_cubes) with the lattice spacing
         cube_length / (N - 1) and origin -cube_length / 2, so vertices are in WORLD units (the frame `sample_mixed` takes).
         Returns one dict per identity: {'vertices' [V, 3] float32, 'faces' [F, 3] int32}, plus 'colors' [V, 3] uint8 when
         `colors`: the first three decoder features at the vertices (ops.planes_query, as `sample_mixed`), quantised as
-        render.to_uint8 quantises image_raw.  One backbone pass.  Forward only."""
+        render.to_uint8 quantises image_raw; plus 'normals' [V, 3] float32 when `normals`: the analytic unit normal
+        −∇σ·rsqrt(‖∇σ‖² + 1e-12) of the density field at the vertices (one ops.planes_query_normals call on the planes already
+        computed), pointing from dense to empty — the side marching cubes winds its faces toward.  One backbone pass.  Forward only."""
         from .render import _border_eg3d, to_uint8
         n = int(resolution)
         if n < 2:
@@ -1096,6 +1156,9 @@ class TriPlaneGenerator(nn.Module):
                     if verts.shape[0]:
                         rgb = ops.planes_query(planes[i:i + 1], verts[None], planes_absmax=pam, **self._query_kwargs())[1][0]
                     mesh["colors"] = to_uint8(rgb[:, :3])
+                if normals:
+                    mesh["normals"] = ops.planes_query_normals(planes[i:i + 1], verts[None], want=("normal",), planes_absmax=pam,
+                                                               **self._query_kwargs())["normal"][0]
                 out.append(mesh)
         return out
 

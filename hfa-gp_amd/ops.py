@@ -978,6 +978,92 @@ def planes_query_bwd(planes: torch.Tensor, coords: torch.Tensor, g_sigma: Option
     return d_planes, d_coords, dec
 
 
+_QUERY_NORMALS_OUT = ("sigma", "rgb", "grad", "normal")
+
+
+def planes_query_normals(planes: torch.Tensor, coords: torch.Tensor, *, want=_QUERY_NORMALS_OUT, dec_w0: torch.Tensor,
+                         dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, box_warp: float, plane_axes,
+                         decoder_lr_mul: float, decoder_precision: str, planes_absmax: Optional[torch.Tensor] = None) -> dict:
+    """`planes_query` at explicit points with the density gradient and the unit surface normal (hfagp_planes_query_normals), one
+    launch → a dict with the keys of ``want`` (any non-empty subset of 'sigma', 'rgb', 'grad', 'normal'):
+
+      * 'sigma' [B,M,1], 'rgb' [B,M,32]: the bits of `planes_query`;
+      * 'grad' [B,M,3]: g = ∂σ/∂x of the raw density in WORLD units (zeros padding, align_corners=False; on an integer pixel
+        coordinate the one-sided derivative of the cell the forward's floor() picked);
+      * 'normal' [B,M,3]: n = −g·rsqrt(g·g + 1e-12), from dense to empty.
+    A point outside every plane gets exact zeros in 'grad' and 'normal'.  No atomics: two calls return the same bits.  The results
+    carry no gradient (the backward of 'grad' / 'normal' is `planes_query_normals_bwd`, that of 'sigma' / 'rgb' `planes_query_bwd`).
+    ``coords`` [Bc,M,3], Bc = 1 or B; the other keywords are `planes_query`'s."""
+    who = "planes_query_normals"
+    b, h, w = _planes_dims(who, planes)
+    dev = planes.device
+    want = tuple(want)
+    if not want or any(k not in _QUERY_NORMALS_OUT for k in want):
+        raise ValueError(f"{who}: want must be a non-empty subset of {_QUERY_NORMALS_OUT}, got {want}")
+    if coords is None:
+        raise ValueError(f"{who}: explicit coords only (no grid mode)")
+    m = _query_points(who, coords, b)
+    width = {"sigma": 1, "rgb": 32, "grad": 3, "normal": 3}
+    out = {k: torch.empty(b, m, width[k], device=dev, dtype=torch.float32) for k in _QUERY_NORMALS_OUT if k in want}
+    if b == 0 or m == 0:
+        return out
+    a = L.PlanesQueryArgs()
+    a.coords, a.Bc, a.M = _ptr(coords), coords.shape[0], m
+    _fill_decoder(who, a, planes, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_precision, planes_absmax)
+    a.planes, a.sigma, a.rgb = _ptr(planes), _ptr(out.get("sigma")), _ptr(out.get("rgb"))
+    a.B, a.H, a.W, a.plane_axes = b, h, w, _plane_axes_id(plane_axes)
+    a.box_warp, a.decoder_lr_mul = box_warp, decoder_lr_mul
+    L.check(L.lib().hfagp_planes_query_normals(C.byref(a), _ptr(out.get("grad")), _ptr(out.get("normal")), _stream()), who)
+    return out
+
+
+def planes_query_normals_bwd(planes: torch.Tensor, coords: torch.Tensor, g_grad: Optional[torch.Tensor],
+                             g_normal: Optional[torch.Tensor], *, dec_w0: torch.Tensor, dec_b0: torch.Tensor, dec_w1: torch.Tensor,
+                             dec_b1: torch.Tensor, box_warp: float, plane_axes, decoder_lr_mul: float, decoder_precision: str,
+                             planes_absmax: Optional[torch.Tensor] = None, d_planes=None, decoder_grads: bool = False, dec_out=None):
+    """Backward of the 'grad' / 'normal' outputs of `planes_query_normals(planes, coords, ...)` (hfagp_planes_query_normals_bwd) →
+    ``(d_planes, dec)``.  ``g_grad`` and ``g_normal`` [B,M,3]: dL/d grad and dL/d normal, either may be None.  The second derivative
+    of the tri-plane gather plus decoder (include/hfagp.h has the formulas); the gradients of 'sigma' / 'rgb' are `planes_query_bwd`'s
+    — a caller with both runs both into the same buffers.  There is no gradient w.r.t. the points.
+
+      * ``d_planes``: a [B,3,H,W,32] tensor the plane gradient is ACCUMULATED into (returned), None = fresh zeros, False = not
+        wanted (None is returned; needs ``decoder_grads``).  A tensor shared with `raymarch_bwd` must have been through that call
+        FIRST: on mirrored planes it overwrites plane 2, and this kernel adds to all three planes at their true texels.
+      * ``decoder_grads`` / ``dec_out``: as `planes_query_bwd`.  The colour rows of dec_w1 and all of dec_b1 receive nothing.
+    A point whose two upstream vectors are exactly zero touches nothing.  The other keywords are the forward's; pass its
+    ``planes_absmax``."""
+    who = "planes_query_normals_bwd"
+    b, h, w = _planes_dims(who, planes)
+    if coords is None:
+        raise ValueError(f"{who}: explicit coords only (no grid mode)")
+    m = _query_points(who, coords, b)
+    if g_grad is None and g_normal is None:
+        raise ValueError(f"{who}: pass g_grad, g_normal or both")
+    for name, t in (("g_grad", g_grad), ("g_normal", g_normal)):
+        if t is not None and _chk(t, f"{who}: {name}").shape != (b, m, 3):
+            raise RuntimeError(f"{who}: {name} must be [B, M, 3] = [{b}, {m}, 3], got {tuple(t.shape)}")
+    if d_planes is False:
+        d_planes = None
+        if not decoder_grads:
+            raise ValueError(f"{who}: nothing to compute (d_planes=False without decoder_grads)")
+    elif d_planes is None:
+        d_planes = torch.zeros_like(planes)
+    elif _chk(d_planes, f"{who}: d_planes").shape != planes.shape:
+        raise RuntimeError(f"{who}: d_planes must be shaped like planes {tuple(planes.shape)}, got {tuple(d_planes.shape)}")
+    a = L.PlanesQueryBwdArgs()
+    params = (dec_w0, dec_b0, dec_w1, dec_b1)
+    dec = _dec_grad_out(who, a, params, decoder_grads, dec_out)
+    if b == 0 or m == 0:
+        return d_planes, dec
+    _fill_decoder(who, a, planes, params, decoder_precision, planes_absmax)
+    a.planes, a.coords, a.Bc, a.M = _ptr(planes), _ptr(coords), coords.shape[0], m
+    a.d_planes = _ptr(d_planes)
+    a.B, a.H, a.W, a.plane_axes = b, h, w, _plane_axes_id(plane_axes)
+    a.box_warp, a.decoder_lr_mul = box_warp, decoder_lr_mul
+    L.check(L.lib().hfagp_planes_query_normals_bwd(C.byref(a), _ptr(g_grad), _ptr(g_normal), _stream()), who)
+    return d_planes, dec
+
+
 def marching_cubes(volume: torch.Tensor, level: float, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     """Iso-surface ``volume > level`` of a float32 [n0, n1, n2] volume (hfagp_marching_cubes_count / _emit) → ``(verts [V, 3]
     float32, faces [F, 3] int32)`` on the volume's device.  Vertices ``origin + spacing * p`` at the crossed lattice edges,

@@ -124,10 +124,11 @@ def _border_eg3d(v: torch.Tensor) -> torch.Tensor:
     return v
 
 
-def save_ply(path, verts, faces, colors=None) -> None:
+def save_ply(path, verts, faces, colors=None, normals=None) -> None:
     """Write a triangle mesh as binary little-endian PLY in the layout plyfile writes for EG3D's shape export: `element vertex`
-    with float x / y / z (and uchar red / green / blue when `colors` [V, 3] uint8 is given), `element face` with
-    `property list uchar int vertex_indices`.  verts [V, 3], faces [F, 3]: numpy arrays or tensors."""
+    with float x / y / z (then float nx / ny / nz when `normals` [V, 3] is given, then uchar red / green / blue when `colors`
+    [V, 3] uint8 is given: the order plyfile and MeshLab use), `element face` with `property list uchar int vertex_indices`.
+    verts [V, 3], faces [F, 3]: numpy arrays or tensors.  Without `normals` the file is what it was before the keyword existed."""
     def host(a):
         return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     v, f = host(verts), host(faces)
@@ -135,6 +136,12 @@ def save_ply(path, verts, faces, colors=None) -> None:
         raise ValueError(f"save_ply: expected verts [V, 3] and faces [F, 3], got {v.shape} and {f.shape}")
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     props = ["property float x", "property float y", "property float z"]
+    if normals is not None:
+        nrm = host(normals)
+        if nrm.shape != v.shape or nrm.dtype.kind != "f":
+            raise ValueError(f"save_ply: normals must be floating point [V, 3], got {nrm.dtype} {nrm.shape}")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        props += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         c = host(colors)
         if c.shape != v.shape or c.dtype != np.uint8:
@@ -144,6 +151,9 @@ def save_ply(path, verts, faces, colors=None) -> None:
     vert = np.empty(v.shape[0], dtype=fields)
     for i, name in enumerate("xyz"):
         vert[name] = v[:, i]
+    if normals is not None:
+        for i, name in enumerate(("nx", "ny", "nz")):
+            vert[name] = nrm[:, i]
     if colors is not None:
         for i, name in enumerate(("red", "green", "blue")):
             vert[name] = c[:, i]

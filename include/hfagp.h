@@ -26,6 +26,8 @@
  *   hfagp_qr_gram_fwd / hfagp_qr_refine_fwd <- torch.qr(bases.T) of get_latent (code/networks/headnerf.py:91,187,246)
  *   hfagp_planes_query      <- TriPlaneGenerator.sample / sample_mixed (sample_from_planes + OSGDecoder at given points) and the
  *                              density volume of gen_samples.py --shapes (create_samples lattice), one launch (ABI 13)
+ *   hfagp_planes_query_normals[_bwd] <- (no reference counterpart: autograd of sample_mixed's sigma w.r.t. the points, i.e. the
+ *                              density gradient and surface normal at a point, and what a loss on them back-propagates)
  *   hfagp_marching_cubes_count / _emit (+ _workspace_bytes) <- the .ply mesh of gen_samples.py --shapes
  *                              (skimage.measure.marching_cubes + plyfile in EG3D's shape_utils), on the GPU (ABI 14)
  *   hfagp_raymarch_normals  <- (no reference counterpart: the per-ray surface normal map of EG3D-family geometry renders — the
@@ -261,6 +263,47 @@ typedef struct {
 } HfagpPlanesQueryBwdArgs;
 
 int hfagp_planes_query_bwd(const HfagpPlanesQueryBwdArgs* a, void* stream);
+
+/* Density gradient and unit surface normal at explicit points (additive to ABI 15): hfagp_planes_query with two more outputs, one
+ * launch.  A point is a ray sample of hfagp_raymarch_normals with compositing weight 1 and no depth.  Per point, with
+ * q = fp32(2 / box_warp) p, F the plane mean of the three bilinear gathers, hp = W0' F + b0' (the lr_mul gains folded in):
+ *   sigma, rgb   exactly as hfagp_planes_query computes them (split fp16 given planes_absmax, exact fp32 without it): its bits
+ *   a = d sigma / dF = W0'^T (wsig * sigmoid(hp))   on the exact fp32 matrix instructions with EITHER decoder, so that this entry
+ *                and hfagp_planes_query_normals_bwd form the same n
+ *   grad   = g = (2 / box_warp) J^T a   the WORLD-space gradient of the raw density; J = dF / dq with zeros padding and
+ *                align_corners = False; where a pixel coordinate is an integer, the one-sided derivative of the cell the
+ *                forward's floor() picked
+ *   normal = n = -g * rsqrt(g.g + 1e-12)   the unit normal from dense to empty
+ * Outputs, each optional (at least one): a->sigma [B][M], a->rgb [B][M][32], grad [B][M][3], normal [B][M][3]; identity b's start
+ * at b * out_stride elements (x 32, x 3, x 3; out_stride 0 = M).  A point outside every plane gets exact zeros in grad and normal.
+ * One writer per point, no atomics: two calls give the same bits.  The grid fields of `a` are not read.
+ * HFAGP_EBADARG, nothing launched: a, the planes or a decoder tensor NULL; no output given; bad B / H / W / M / Bc / plane_axes /
+ * box_warp / out_stride.  HFAGP_EUNSUPPORTED, nothing launched: a->coords NULL (no grid mode); H * W > 2^25.                   */
+int hfagp_planes_query_normals(const HfagpPlanesQueryArgs* a, float* grad /* [B][M][3] or NULL */,
+                               float* normal /* [B][M][3] or NULL */, void* stream);
+
+/* Backward of the grad / normal outputs of hfagp_planes_query_normals (additive to ABI 15): from g_grad = dL/d grad and / or
+ * g_normal = dL/d normal, both [B][M][3] (at least one), to the plane gradient and the decoder-parameter gradients, one launch.
+ * The gradients of sigma / rgb are NOT formed here: they stay with hfagp_planes_query_bwd, and a caller with both launches both
+ * entries into the same buffers.  The forward is recomputed per point (a, g, n as the forward entry forms them); then, with
+ * r = sqrt(g.g + 1e-12), it is the "through the normals" branch of hfagp_raymarch_normals_bwd with omega = 1 and d sigma_s = 0:
+ *   gamma = dL/dg = g_grad - (1 / r)(g_normal - n (n . g_normal));   per tap k of every plane, with w_k its bilinear weight,
+ *   w'_k = (2 / box_warp) gamma . grad_q w_k (0 for a tap outside the plane),   u = sum_planes sum_k texel w'_k / 3,   v = W0' u,
+ *   e = wsig * sigmoid(hp) * (1 - sigmoid(hp)) * v,   dF = W0'^T e.
+ *   a->d_planes    += (w_k / 3) dF + (w'_k / 3) a at every tap, all three planes at their true texels (fp32 atomics): as
+ *                     hfagp_planes_query_bwd, call it AFTER hfagp_raymarch_bwd on a shared buffer, which overwrites plane 2 on
+ *                     mirrored planes.
+ *   a->d_dec_w0    += (e F^T + dH u^T) * gain, dH = wsig * sigmoid(hp);   a->d_dec_b0 += e * gain;
+ *   a->d_dec_w1[0] += sigmoid(hp) * v * gain;   the colour rows of d_dec_w1 and ALL of d_dec_b1 receive nothing.  The four go
+ *                     together (all or none), one set of atomics per wavefront; gains as hfagp_raymarch_bwd.
+ * At least one of d_planes and the decoder gradients is given.  The second-order products (and a) run on the exact fp32 matrix
+ * instructions with either decoder; hp as the forward ran it (pass the planes_absmax the forward call got).  A point whose two
+ * upstream vectors are exactly 0 touches nothing.  There is no gradient w.r.t. the points for these two outputs.
+ * HFAGP_EBADARG, nothing launched: a, the planes or a decoder tensor NULL; a->g_sigma, a->g_rgb or a->d_coords not NULL; g_grad
+ * and g_normal both NULL; only some of the four decoder outputs given; no output given; bad B / H / W / M / Bc / plane_axes /
+ * box_warp.  HFAGP_EUNSUPPORTED, nothing launched: a->coords NULL (no grid mode); H * W > 2^25.                                */
+int hfagp_planes_query_normals_bwd(const HfagpPlanesQueryBwdArgs* a /* g_sigma, g_rgb, d_coords must be NULL */,
+                                   const float* g_grad, const float* g_normal, void* stream);
 
 /* ------------------------------------------------------------------ marching cubes (ABI 14)
  * The iso-surface of a fp32 volume V[n0][n1][n2] (last axis fastest, each extent >= 2) as a welded triangle mesh.

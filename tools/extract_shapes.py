@@ -14,7 +14,8 @@ set to -1000) and written with the lattice spacing box_warp / (resolution - 1) a
 `--format ply` (or `both`) writes the surface as `<name>.ply` instead (or as well), in EG3D's vertex units: marching cubes
 at `--level` (EG3D: 10) on the GPU over the same volume transposed (`render.shape_mesh_eg3d`), as `gen_samples.py --shapes
 --shape-format .ply` writes it.  `--colors` adds per-vertex RGB: the first three decoder features at each vertex, mapped back
-to world units.
+to world units.  `--normals` adds per-vertex unit normals (`property float nx ny nz`): the analytic −∇σ/‖∇σ‖ of the density field at
+each vertex (`sample_mixed(normals=True)`), rotated into the same EG3D lattice frame as the vertices, pointing from dense to empty.
 """
 from __future__ import annotations
 
@@ -57,6 +58,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--format", default="mrc", choices=("mrc", "ply", "both"), help="density volume, surface mesh, or both")
     p.add_argument("--level", type=float, default=10.0, help="iso level of the .ply surface (EG3D: 10)")
     p.add_argument("--colors", action="store_true", help="per-vertex colours in the .ply")
+    p.add_argument("--normals", action="store_true",
+                   help="per-vertex unit normals (nx ny nz) in the .ply, for --format ply|both: the analytic density-field normal, in the "
+                        "frame of the .ply's vertices (EG3D's lattice frame: world (x, y, z) -> (z, y, -x)), from dense to empty")
     p.add_argument("--outdir", required=True, help="output directory")
     return p
 
@@ -76,6 +80,14 @@ def eg3d_to_world(verts, n: int, cube: float):
     voxel = cube / (n - 1)
     a, b, c = verts.unbind(-1)
     return torch.stack([(n - 1 - c) * voxel, b * voxel, a * voxel], -1) - cube / 2
+
+
+def world_to_eg3d_dir(d):
+    """A world-space direction (x, y, z) in the frame of the EG3D .ply vertices (a, b, c): the axis permutation and flip of
+    `eg3d_to_world` inverted, without its scale and offset: (a, b, c) = (z, y, -x)"""
+    import torch
+    x, y, z = d.unbind(-1)
+    return torch.stack([z, y, -x], -1)
 
 
 def main(argv=None) -> int:
@@ -109,12 +121,16 @@ def main(argv=None) -> int:
                 print(path)
             if args.format in ("ply", "both"):
                 verts, faces = shape_mesh_eg3d(grid, level=args.level)
-                colors = None
-                if args.colors:
+                colors = normals = None
+                if args.colors or args.normals:
                     world = eg3d_to_world(verts, args.resolution, cfg.box_warp)
-                    colors = to_uint8(gen.sample_mixed(world[None], None, ws)["rgb"][0, :, :3])
+                    q = gen.sample_mixed(world[None], None, ws, normals=args.normals)
+                    if args.colors:
+                        colors = to_uint8(q["rgb"][0, :, :3])
+                    if args.normals:
+                        normals = world_to_eg3d_dir(q["normal"][0])
                 path = os.path.join(args.outdir, name + ".ply")
-                save_ply(path, verts, faces, colors)
+                save_ply(path, verts, faces, colors, normals)
                 print(path)
     return 0
 
