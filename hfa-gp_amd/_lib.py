@@ -180,6 +180,14 @@ class RaymarchGeomGrads(C.Structure):
     _fields_ = [("g_depth", C.c_void_p), ("g_wsum", C.c_void_p), ("depth_range", C.c_void_p)]
 
 
+class RayListArgs(C.Structure):
+    _fields_ = [("base", RaymarchArgs), ("ray_origins", C.c_void_p), ("ray_directions", C.c_void_p), ("R", C.c_int32)]
+
+
+class RayListBwdArgs(C.Structure):
+    _fields_ = [("bwd", RaymarchBwdArgs), ("ray_origins", C.c_void_p), ("ray_directions", C.c_void_p), ("R", C.c_int32)]
+
+
 # every symbol include/hfagp.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "hfagp_abi_version": (C.c_int, []),
@@ -230,6 +238,10 @@ SYMBOLS = {
     "hfagp_raymarch_bwd_geom": (C.c_int, [C.POINTER(RaymarchBwdArgs), C.POINTER(RaymarchGeomGrads), C.c_void_p]),
     "hfagp_raymarch_bwd_rows_bytes": (C.c_size_t, [C.POINTER(RaymarchArgs)]),
     "hfagp_raymarch_bwd_camera": (C.c_int, [C.POINTER(RaymarchBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hfagp_raymarch_rays_fwd": (C.c_int, [C.POINTER(RayListArgs), C.c_void_p]),
+    "hfagp_raymarch_rays_bwd": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RaymarchGeomGrads), C.c_void_p]),
+    "hfagp_raymarch_rays_bwd_rows_bytes": (C.c_size_t, [C.POINTER(RayListArgs)]),
+    "hfagp_raymarch_rays_bwd_rays": (C.c_int, [C.POINTER(RayListBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hfagp_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
     "hfagp_adam_chunk": (C.c_int32, []),
     "hfagp_weight_prep_batch": (C.c_int, [C.POINTER(WeightPrepItem), C.c_int32, C.c_void_p]),

@@ -695,3 +695,77 @@ class SampleMixedNormalFn(torch.autograd.Function):
         ctx.tape = ctx.planes = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
         return (d_ws, None, None) + pgrads
+
+
+class RenderRaysFn(torch.autograd.Function):
+    """`TriPlaneGenerator.render_rays` under grad: inputs ws, ray_origins, ray_directions, u_strat, u_imp, gen, *parameters; outputs
+    feature [B,R,32], depth [B,R] (clamped to the call's global sample range), mask [B,R].  A backbone forward with a tape, then one
+    list launch (ops.raymarch_rays); backward = ops.raymarch_rays_bwd into d_planes (with the decoder gradients when parameters
+    require grad), ops.raymarch_rays_bwd_rays only when the rays require grad, then the backbone backward `synthesis` runs."""
+    @staticmethod
+    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, *params):
+        from .generator import RAY_STATE_CAP_BYTES
+        ws_c = ws.detach().float().contiguous()
+        o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
+        b, r = o.shape[0], o.shape[1]
+        tape = []
+        with torch.no_grad():
+            planes = gen.backbone_planes(ws_c, tape)
+            pam = getattr(gen, "_planes_absmax", None)
+            sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+            # (the per-sample results for the compositing adjoint, as a differentiated `synthesis` keeps them; skipped above the cap)
+            state = ops.raymarch_rays_state(b, r, sc, sf, planes.device) if b * r * (sc + sf) * 140 <= RAY_STATE_CAP_BYTES else None
+            feat, depth, wsum, tmm = gen._timed("raymarch_rays", float(b), ops.raymarch_rays, planes, o, d, u_strat, u_imp,
+                                                planes_absmax=pam, state=state, **gen._rays_kwargs())
+            depth_range = ops.depth_range(tmm)
+            depth = ops.depth_clamp_(depth, tmm)
+        ctx.gen, ctx.tape, ctx.ws_c, ctx.planes, ctx.pam, ctx.state = gen, tape, ws_c, planes, pam, state
+        ctx.rays, ctx.uniforms, ctx.depth_range = (o, d), (u_strat, u_imp), depth_range
+        ctx.params = params
+        ctx.pg = any(p.requires_grad for p in params)
+        ctx.ws_shape, ctx.ray_dtypes = ws.shape, (ray_origins.dtype, ray_directions.dtype)
+        ctx.set_materialize_grads(False)
+        return feat, depth, wsum
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_feat, g_depth, g_wsum):
+        gen = ctx.gen
+        if ctx.tape is None:
+            raise RuntimeError("TriPlaneGenerator.render_rays: backward called a second time — the saved activations are released "
+                               "by the first backward pass (retain_graph is not supported)")
+        none = (None,) * (6 + len(ctx.params))
+        if g_feat is None and g_depth is None and g_wsum is None:
+            return none
+        planes = ctx.planes
+        b, dev = planes.shape[0], planes.device
+        (o, d), (u_strat, u_imp) = ctx.rays, ctx.uniforms
+        r = o.shape[1]
+        d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
+        bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
+        g_feat = None if g_feat is None else g_feat.float().contiguous()
+        geom = {}
+        if g_depth is not None:
+            geom.update(g_depth=g_depth.float().reshape(b, r).contiguous(), depth_range=ctx.depth_range)
+        if g_wsum is not None:
+            geom.update(g_wsum=g_wsum.float().reshape(b, r).contiguous())
+        need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        rec_out = [] if need_rays else None
+        rb = gen._timed("raymarch_rays_bwd", float(b), ops.raymarch_rays_bwd, g_feat, planes, o, d, u_strat, u_imp,
+                        decoder_grads=ctx.pg, planes_absmax=ctx.pam, state=ctx.state, rec_out=rec_out, **geom, **gen._rays_kwargs())
+        d_o = d_d = None
+        if need_rays:        # the per-ray record of the camera gradient is itself the answer; autograd carries it on to the camera model
+            d_o, d_d = gen._timed("raymarch_rays_bwd_rays", float(b), ops.raymarch_rays_bwd_rays, g_feat, planes, rec_out[0], o, d,
+                                  u_strat, u_imp, planes_absmax=ctx.pam, **gen._rays_kwargs())
+            d_o = d_o.to(ctx.ray_dtypes[0]) if ctx.needs_input_grad[1] else None
+            d_d = d_d.to(ctx.ray_dtypes[1]) if ctx.needs_input_grad[2] else None
+        if ctx.pg:
+            d_planes, dec = rb
+            for prm, g in zip(gen.decoder_params(), dec):
+                bw._acc(prm, g)
+        else:
+            d_planes = rb
+        _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
+        ctx.tape = ctx.planes = ctx.state = None
+        pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
+        return (d_ws, d_o, d_d, None, None, None) + pgrads

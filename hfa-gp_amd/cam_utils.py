@@ -82,3 +82,32 @@ def cam_sampler(batch: int, device, horizontal_mean=0.5, vertical_mean=0.5, hori
                                         vertical_mean=vertical_mean * math.pi, horizontal_stddev=horizontal_stddev,
                                         vertical_stddev=vertical_stddev, mode="gaussian")
     return make_label(create_cam2world_matrix(-pts, pts, device=device))
+
+
+def ray_grid(c: torch.Tensor, res: int, window=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """EG3D's RaySampler for a label, in plain torch: c [B,25] → (origins, directions), each [B, res*res, 3], pixel centres of a
+    res x res image in row order, unit directions — the rays `synthesis` marches when res is the rendering resolution, and the rays
+    `TriPlaneGenerator.render_rays` takes at any res.  ``window`` = (u0, v0, u1, v1) in normalised image coordinates (u along a
+    row, v down the rows; the whole image is (0, 0, 1, 1)): the res x res pixel centres of that rectangle instead — a crop, or a zoom
+    at a higher ray density.  Differentiable w.r.t. c."""
+    n = c.shape[0]
+    c2w, intr = c[:, :16].reshape(n, 4, 4), c[:, 16:25].reshape(n, 3, 3)
+    cam = c2w[:, :3, 3]
+    fx, fy = intr[:, 0, 0], intr[:, 1, 1]
+    cx, cy = intr[:, 0, 2], intr[:, 1, 2]
+    sk = intr[:, 0, 1]
+    ar = torch.arange(res, dtype=c.dtype, device=c.device)
+    uv = torch.stack(torch.meshgrid(ar, ar, indexing="ij")) * (1.0 / res) + (0.5 / res)
+    uv = uv.flip(0).reshape(2, -1).transpose(1, 0)[None].repeat(n, 1, 1)
+    xc, yc = uv[:, :, 0], uv[:, :, 1]
+    if window is not None:
+        u0, v0, u1, v1 = (float(t) for t in window)
+        xc, yc = u0 + xc * (u1 - u0), v0 + yc * (v1 - v0)
+    zc = torch.ones_like(xc)
+    xl = (xc - cx[:, None] + cy[:, None] * sk[:, None] / fy[:, None] - sk[:, None] * yc / fy[:, None]) / fx[:, None] * zc
+    yl = (yc - cy[:, None]) / fy[:, None] * zc
+    pts = torch.stack((xl, yl, zc, torch.ones_like(zc)), dim=-1)
+    world = torch.bmm(c2w, pts.permute(0, 2, 1)).permute(0, 2, 1)[:, :, :3]
+    dirs = torch.nn.functional.normalize(world - cam[:, None, :], dim=2)
+    origins = cam[:, None, :].repeat(1, dirs.shape[1], 1)
+    return origins, dirs.contiguous()          # (both contiguous: ops.raymarch_rays takes them as they are)

@@ -39,6 +39,7 @@ units+=(raymarch_normals_bwd)
 units+=(raymarch_normals_camera)
 units+=(planes_query_normals)
 units+=(planes_query_normals_bwd)
+units+=(raymarch_rays)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

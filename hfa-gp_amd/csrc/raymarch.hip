@@ -52,8 +52,10 @@ struct WaveLds {
 // LEGACY_TAPS: every lane of a gather quad computes the taps of all three planes (sample_taps) instead of one plane per lane
 // exchanged by DPP (raymarch_common.h sample_taps_quad) — the form before the exchange, kept selectable for A/B timing and the
 // bit-identity tests (developer switch HFAGP_DEV_RAY_TAPS_LEGACY=1, launch_raymarch).
-template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false>
-__global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
+// LIST: the rays are the caller's list (RayParams::ray_o / ray_d, R per frame) instead of the pinhole grid of the frame's label;
+// the one difference is the fetch (raymarch_common.h ray_fetch), so the body is shared and the two kernels below instantiate it.
+template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE, bool LEGACY_TAPS, bool LIST>
+__device__ __forceinline__ void raymarch_body(const RayParams& p) {
     static_assert(!FROM_STATE || GRADS, "the saved state is consumed by the backward pass");
     using L = WaveLds<NC, NF>;
     constexpr int SC = L::SC, SF = L::SF, S = L::S;
@@ -62,7 +64,7 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
     L& lds = reinterpret_cast<L*>(smem)[wave];
     const HfagpRaymarchArgs& a = p.a;
     const int j = lane & 15, g = lane >> 4;
-    const int R = a.res * a.res;
+    const int R = LIST ? p.R : a.res * a.res;
 
     constexpr bool kL1Lds = DEC16 && !FROM_STATE;   // layer 1 of the 16-bit decoder from LDS (raymarch_common.h decoder_fwd16_l1)
     typename std::conditional<DEC16, Dec16Regs, DecoderRegs>::type dec;
@@ -93,12 +95,7 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
     float o_l[3] = {0.f, 0.f, 0.f}, d_l[3] = {0.f, 0.f, 0.f};
     {
         const long long sl = (long long)seq0 + (long long)lane * sch.stride;
-        if (sl < sch.end) {
-            int pi, pj;
-            ray_of((int)sl, a.res, b_l, pi, pj);
-            ray_l = b_l * R + pi * a.res + pj;                 // index into the [B][R] tensors
-            if constexpr (!FROM_STATE) ray_setup(a, b_l, pi, pj, o_l, d_l);
-        }
+        if (sl < sch.end) ray_fetch<LIST, !FROM_STATE>(p, (int)sl, R, b_l, ray_l, o_l, d_l);      // ray_l: index into the [B][R] tensors
     }
     const int nbatch = __builtin_amdgcn_readfirstlane(min(64, ((int)sch.end - seq0 + sch.stride - 1) / sch.stride));
     #pragma unroll 1
@@ -472,29 +469,42 @@ __global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
 }
 
 template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false>
+__global__ void __launch_bounds__(256, 2) raymarch_kernel(const RayParams p) {
+    raymarch_body<NC, NF, GRADS, DEC16, FROM_STATE, LEGACY_TAPS, false>(p);
+}
+
+// the same kernel on a ray list (hfagp_raymarch_rays_fwd / pass 1 of hfagp_raymarch_rays_bwd)
+template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false>
+__global__ void __launch_bounds__(256, 2) raymarch_rays_kernel(const RayParams p) {
+    raymarch_body<NC, NF, GRADS, DEC16, FROM_STATE, false, true>(p);
+}
+
+template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false, bool LIST = false>
 static int launch(const RayParams& p, hipStream_t s) {
     const size_t lds = 4 * sizeof(WaveLds<NC, NF>) + ((DEC16 && !FROM_STATE) ? kDecL1Floats * sizeof(float) : 0);
     int blocks = (p.total_rays + 3) / 4;
     const int cap = kNumCU * 2 * 4;          // 2 resident workgroups per CU, a few rounds each
     if (blocks > cap) blocks = cap;
+    void (*kernel)(const RayParams);
+    if constexpr (LIST) kernel = &raymarch_rays_kernel<NC, NF, GRADS, DEC16, FROM_STATE>;
+    else kernel = &raymarch_kernel<NC, NF, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>;
     if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&raymarch_kernel<NC, NF, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             set_error("raymarch: cannot raise dynamic LDS to %zu bytes: %s", lds, hipGetErrorString(e));
             return HFAGP_ELAUNCH;
         }
     }
-    raymarch_kernel<NC, NF, GRADS, DEC16, FROM_STATE, LEGACY_TAPS><<<blocks, 256, lds, s>>>(p);
+    kernel<<<blocks, 256, lds, s>>>(p);
     return check_launch(GRADS ? "raymarch_bwd/samples" : "raymarch_fwd");
 }
 
-template <bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false>
+template <bool GRADS, bool DEC16, bool FROM_STATE = false, bool LEGACY_TAPS = false, bool LIST = false>
 static int launch_n(const RayParams& p, hipStream_t s) {
     const int n = p.a.Sc / 16;
-    return n == 3   ? launch<3, 3, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>(p, s)
-           : n == 2 ? launch<2, 2, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>(p, s)
-                    : launch<1, 1, GRADS, DEC16, FROM_STATE, LEGACY_TAPS>(p, s);
+    return n == 3   ? launch<3, 3, GRADS, DEC16, FROM_STATE, LEGACY_TAPS, LIST>(p, s)
+           : n == 2 ? launch<2, 2, GRADS, DEC16, FROM_STATE, LEGACY_TAPS, LIST>(p, s)
+                    : launch<1, 1, GRADS, DEC16, FROM_STATE, LEGACY_TAPS, LIST>(p, s);
 }
 
 template <bool LEGACY_TAPS>
@@ -505,6 +515,11 @@ static int launch_gather(const RayParams& p, bool grads, bool dec16, hipStream_t
 
 int launch_raymarch(const RayParams& p, bool grads, hipStream_t s) {
     const bool dec16 = p.a.planes_absmax != nullptr;
+    if (p.ray_o) {                                // a ray list: the same variants but the developer's tap form
+        if (grads && p.a.state) return launch_n<true, false, true, false, true>(p, s);
+        if (grads) return dec16 ? launch_n<true, true, false, false, true>(p, s) : launch_n<true, false, false, false, true>(p, s);
+        return dec16 ? launch_n<false, true, false, false, true>(p, s) : launch_n<false, false, false, false, true>(p, s);
+    }
     if (grads && p.a.state) return launch_n<true, false, true>(p, s);        // (no gather and no decoder in this variant)
     // Developer switch HFAGP_DEV_RAY_TAPS_LEGACY=1: all three planes' taps on every lane of a gather quad (read at every call, so one
     // process can time and compare both forms).

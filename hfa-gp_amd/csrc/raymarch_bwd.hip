@@ -42,7 +42,8 @@ template <bool PG> struct BwdWaves { static constexpr int value = PG ? 4 : 6; };
 // one wave per SIMD with 512 registers and the pipeline.
 template <bool PG, bool SCATTER, bool WIDE = false> struct TileWaves { static constexpr int value = SCATTER ? BwdWaves<PG>::value : WIDE ? 8 : 4; };
 
-template <int S, bool PG, bool MIRROR, bool DEC16, bool SCATTER = true, bool WIDE = false>
+// LIST: the rays of a caller's list instead of the pinhole grid (raymarch_common.h ray_fetch); nothing else differs.
+template <int S, bool PG, bool MIRROR, bool DEC16, bool SCATTER = true, bool WIDE = false, bool LIST = false>
 __global__ void __launch_bounds__((TileWaves<PG, SCATTER, WIDE>::value * 64), (PG ? 1 : 2))
 raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const DecGrads dg, const RowsOut ro) {
     // (SCATTER = false, PG = false: dL/dF to the sorted slots alone — the generator-frozen pass of the sort + gather form)
@@ -61,7 +62,7 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
     TileLds& lds = lds_all[SCATTER ? wave : 0];     // never dereferenced unless SCATTER
     const HfagpRaymarchArgs& a = p.a;
     const int j = lane & 15, g = lane >> 4;
-    const int R = a.res * a.res;
+    const int R = LIST ? p.R : a.res * a.res;
     constexpr int NT = S / 16;
 
     if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
@@ -88,10 +89,9 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
         RecPre r;
         const int tt = __builtin_amdgcn_readfirstlane((int)(tile % NT));
         r.tt = tt;
-        int pi, pj;
-        ray_of(__builtin_amdgcn_readfirstlane((int)(tile / NT)), a.res, r.b, pi, pj);
-        r.ray = __builtin_amdgcn_readfirstlane(r.b * R + pi * a.res + pj);
-        ray_setup(a, r.b, pi, pj, r.o3, r.d3);
+        int ray_v;
+        ray_fetch<LIST>(p, __builtin_amdgcn_readfirstlane((int)(tile / NT)), R, r.b, ray_v, r.o3, r.d3);
+        r.ray = __builtin_amdgcn_readfirstlane(ray_v);
         r.rec = *reinterpret_cast<const float4*>(p.rec + ((size_t)r.ray * S + 16 * tt + j) * 4);
         r.zq = p.rec[((size_t)r.ray * S + 16 * tt + (lane >> 2)) * 4];
 #pragma unroll
@@ -174,10 +174,9 @@ raymarch_bwd_tiles_kernel(const RayParams p, float* __restrict__ d_planes, const
         } else {
         tt = WIDE ? tw : __builtin_amdgcn_readfirstlane((int)(tile % NT));        // wave-uniform -> scalar registers
         if (!WIDE || tw == 0) {
-            int pi, pj;
-            ray_of(__builtin_amdgcn_readfirstlane((int)(WIDE ? it : tile / NT)), a.res, bw, pi, pj);
-            rayw = __builtin_amdgcn_readfirstlane(bw * R + pi * a.res + pj);
-            ray_setup(a, bw, pi, pj, o3w, d3w);
+            int ray_v;
+            ray_fetch<LIST>(p, __builtin_amdgcn_readfirstlane((int)(WIDE ? it : tile / NT)), R, bw, ray_v, o3w, d3w);
+            rayw = __builtin_amdgcn_readfirstlane(ray_v);
 #pragma unroll
             for (int ot = 0; ot < 2; ++ot) gfw[ot] = load_g_feat4(p, (size_t)rayw * 32 + 16 * ot + 4 * g);
             zqw = p.rec[((size_t)rayw * S + 16 * tt + (lane >> 2)) * 4];
@@ -486,7 +485,7 @@ raymarch_bwd_cols_kernel(const RayParams p, float* __restrict__ d_planes, const 
 // The scratch round trip is 0.4 GB per frame of streaming traffic; taken when the caller provides HfagpRaymarchBwdArgs::df_scratch.
 constexpr int kDfWaves = 4;      // two workgroups per CU (254 VGPRs: two waves per SIMD, as the forward kernel)
 
-template <int S, bool DEC16, bool SORTED>
+template <int S, bool DEC16, bool SORTED, bool LIST = false>
 __global__ void __launch_bounds__(kDfWaves * 64, SORTED ? 3 : 2)
 raymarch_bwd_df_kernel(const RayParams p, float* __restrict__ df_out, const RowsOut ro) {
     __shared__ float w1t[4 * 8 * 64];
@@ -495,7 +494,7 @@ raymarch_bwd_df_kernel(const RayParams p, float* __restrict__ df_out, const Rows
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const HfagpRaymarchArgs& a = p.a;
     const int j = lane & 15, g = lane >> 4;
-    const int R = a.res * a.res;
+    const int R = LIST ? p.R : a.res * a.res;
     constexpr int NT = S / 16;
     if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
     if constexpr (DEC16) build_grad16_lds(a, w1t, w0t, lane, wave, kDfWaves);
@@ -505,11 +504,10 @@ raymarch_bwd_df_kernel(const RayParams p, float* __restrict__ df_out, const Rows
     // arithmetic and the ray's dL/dfeat once per ray instead of once per tile (~100 of ~800 vector instructions of a tile)
     const RaySchedule sch = ray_schedule((long long)p.total_rays, wave, kDfWaves);
     for (long long rp = sch.begin; rp < sch.end; rp += sch.stride) {
-        int b, pi, pj;
-        ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
-        const int ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+        int b, ray_v;
         float o3[3], d3[3];
-        ray_setup(a, b, pi, pj, o3, d3);
+        ray_fetch<LIST>(p, __builtin_amdgcn_readfirstlane((int)rp), R, b, ray_v, o3, d3);
+        const int ray = __builtin_amdgcn_readfirstlane(ray_v);
         float4 gfeat[2];
 #pragma unroll
         for (int ot = 0; ot < 2; ++ot) gfeat[ot] = load_g_feat4(p, (size_t)ray * 32 + 16 * ot + 4 * g);
@@ -744,16 +742,23 @@ __global__ void __launch_bounds__(256) mirror_plane_kernel(float* __restrict__ d
     dst[c4] = src[c4];
 }
 
+template <int S, bool DEC16, bool LIST>
+static void launch_tiles3(bool pg, bool mirror, unsigned blocks, const RayParams& p, float* d_planes, const DecGrads& dg,
+                          hipStream_t s) {
+    if (pg) {
+        if (mirror) raymarch_bwd_tiles_kernel<S, true, true, DEC16, true, false, LIST><<<blocks, BwdWaves<true>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
+        else raymarch_bwd_tiles_kernel<S, true, false, DEC16, true, false, LIST><<<blocks, BwdWaves<true>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
+    } else {
+        if (mirror) raymarch_bwd_tiles_kernel<S, false, true, DEC16, true, false, LIST><<<blocks, BwdWaves<false>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
+        else raymarch_bwd_tiles_kernel<S, false, false, DEC16, true, false, LIST><<<blocks, BwdWaves<false>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
+    }
+}
+
 template <int S, bool DEC16>
 static void launch_tiles2(bool pg, bool mirror, unsigned blocks, const RayParams& p, float* d_planes, const DecGrads& dg,
                           hipStream_t s) {
-    if (pg) {
-        if (mirror) raymarch_bwd_tiles_kernel<S, true, true, DEC16><<<blocks, BwdWaves<true>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
-        else raymarch_bwd_tiles_kernel<S, true, false, DEC16><<<blocks, BwdWaves<true>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
-    } else {
-        if (mirror) raymarch_bwd_tiles_kernel<S, false, true, DEC16><<<blocks, BwdWaves<false>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
-        else raymarch_bwd_tiles_kernel<S, false, false, DEC16><<<blocks, BwdWaves<false>::value * 64, 0, s>>>(p, d_planes, dg, RowsOut{});
-    }
+    if (p.ray_o) launch_tiles3<S, DEC16, true>(pg, mirror, blocks, p, d_planes, dg, s);
+    else launch_tiles3<S, DEC16, false>(pg, mirror, blocks, p, d_planes, dg, s);
 }
 
 // decoder-parameter gradients only (d planes is the column kernel's job)
@@ -763,6 +768,13 @@ static void launch_decoder_grads(unsigned blocks, const RayParams& p, float* d_p
     // two waves per SIMD reading the weight images from LDS (WIDE): 1.06 -> 0.93 ms per 2 frames against one 512-register wave
     // per SIMD with the software pipeline
     static const bool narrow = getenv("HFAGP_DEV_PG_NARROW") != nullptr;      // developer switch: A/B timing
+    if (p.ray_o) {                                // a ray list: the wide form
+        if (p.a.planes_absmax)
+            raymarch_bwd_tiles_kernel<S, true, true, true, false, true, true><<<blocks, 512, 0, s>>>(p, d_planes, dg, ro);
+        else
+            raymarch_bwd_tiles_kernel<S, true, true, false, false, true, true><<<blocks, 512, 0, s>>>(p, d_planes, dg, ro);
+        return;
+    }
     if (!narrow) {
         if (p.a.planes_absmax)
             raymarch_bwd_tiles_kernel<S, true, true, true, false, true><<<blocks, 512, 0, s>>>(p, d_planes, dg, ro);
@@ -782,6 +794,11 @@ static void launch_df_sorted(const RayParams& p, const RowsOut& ro, hipStream_t 
     const long long ntiles = (long long)p.total_rays * (S / 16);
     static const int per_cu = getenv("HFAGP_DEV_DF_BLOCKS") ? atoi(getenv("HFAGP_DEV_DF_BLOCKS")) : 6;      // developer: A/B timing
     const unsigned dblocks = (unsigned)std::min<long long>((ntiles + kDfWaves - 1) / kDfWaves, (long long)kNumCU * per_cu);
+    if (p.ray_o) {
+        if (p.a.planes_absmax) raymarch_bwd_df_kernel<S, true, true, true><<<dblocks, kDfWaves * 64, 0, s>>>(p, nullptr, ro);
+        else raymarch_bwd_df_kernel<S, false, true, true><<<dblocks, kDfWaves * 64, 0, s>>>(p, nullptr, ro);
+        return;
+    }
     if (p.a.planes_absmax) raymarch_bwd_df_kernel<S, true, true><<<dblocks, kDfWaves * 64, 0, s>>>(p, nullptr, ro);
     else raymarch_bwd_df_kernel<S, false, true><<<dblocks, kDfWaves * 64, 0, s>>>(p, nullptr, ro);
 }
@@ -860,13 +877,19 @@ extern "C" int hfagp_raymarch_bwd_geom(const HfagpRaymarchBwdArgs* a, const Hfag
     RayParams p;
     int rc = fill_ray_params(&a->fwd, p, "raymarch_bwd");
     if (rc != HFAGP_OK) return rc;
+    return raymarch_bwd_run(a, p, geom, (hipStream_t)stream);
+}
+
+// (raymarch_common.h) the passes of the backward on checked arguments: the grid of hfagp_raymarch_bwd_geom above, or the ray list
+// of hfagp_raymarch_rays_bwd (raymarch_rays.hip; p.ray_o) — the column variant is image-column-shaped and not offered for a list.
+int hfagp::raymarch_bwd_run(const HfagpRaymarchBwdArgs* a, RayParams& p, const HfagpRaymarchGeomGrads* geom, hipStream_t s) {
+    const float* g_depth = geom ? geom->g_depth : nullptr;
     p.g_feat = a->g_feat;
     p.g_depth = g_depth;
-    p.g_wsum = g_wsum;
+    p.g_wsum = geom ? geom->g_wsum : nullptr;
     p.depth_range = g_depth ? geom->depth_range : nullptr;
     p.rec = a->rec;
-    hipStream_t s = (hipStream_t)stream;
-    rc = launch_raymarch(p, true, s);
+    int rc = launch_raymarch(p, true, s);
     if (rc != HFAGP_OK) return rc;
     const int S = a->fwd.Sc + a->fwd.Sf;
     const long long ntiles = (long long)p.total_rays * (S / 16);
@@ -906,7 +929,7 @@ extern "C" int hfagp_raymarch_bwd_geom(const HfagpRaymarchBwdArgs* a, const Hfag
     }
     // frozen generator + mirrored square planes up to 256^2: the column variant (LDS line cache for plane (x,z))
     static const bool no_cols = getenv("HFAGP_DEV_NO_COLS") != nullptr;      // developer switch: A/B timing
-    if (mirror && a->fwd.H <= kColMaxRows && !no_cols) {
+    if (mirror && a->fwd.H <= kColMaxRows && !no_cols && !p.ray_o) {
         const int chunks_per_col = (a->fwd.res + kColRays - 1) / kColRays;
         const int nchunks = a->fwd.B * a->fwd.res * chunks_per_col;
         const size_t lds = cols_lds_bytes();

@@ -21,16 +21,17 @@ constexpr int kCamReduceThreads = 256;
 // (the decoder adjoint and the positional derivative of the gather: decoder_adjoint.h, shared with raymarch_bwd.hip,
 // planes_query_bwd.hip and raymarch_normals.hip)
 
-template <int S, bool DEC16>
-__global__ void __launch_bounds__(kCamWaves * 64, 2)
-raymarch_bwd_camera_kernel(const RayParams p, float* __restrict__ ray_grad) {
+// LIST: the rays of a caller's list (raymarch_common.h ray_fetch) and the record split into d_origins / d_directions [B][R][3] —
+// for a list the per-ray record IS the answer; the body is shared by the two kernels below.
+template <int S, bool DEC16, bool LIST>
+__device__ __forceinline__ void ray_grad_body(const RayParams& p, float* __restrict__ ray_grad, float* __restrict__ d_dir) {
     __shared__ float w1t[4 * 8 * 64];
     __shared__ float w0t[2 * 16 * 64];
     __shared__ float wfwd[kDecLdsRows * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const HfagpRaymarchArgs& a = p.a;
     const int j = lane & 15, g = lane >> 4;
-    const int R = a.res * a.res;
+    const int R = LIST ? p.R : a.res * a.res;
     constexpr int NT = S / 16;
     if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
     if constexpr (DEC16) build_grad16_lds(a, w1t, w0t, lane, wave, kCamWaves);
@@ -40,11 +41,10 @@ raymarch_bwd_camera_kernel(const RayParams p, float* __restrict__ ray_grad) {
     const float sx = (float)a.W * 0.5f * 0.3333333333333333f, sy = (float)a.H * 0.5f * 0.3333333333333333f;
     const RaySchedule sch = ray_schedule((long long)p.total_rays, wave, kCamWaves);
     for (long long rp = sch.begin; rp < sch.end; rp += sch.stride) {
-        int b, pi, pj;
-        ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
-        const int ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+        int b, ray_v;
         float o3[3], d3[3];
-        ray_setup(a, b, pi, pj, o3, d3);
+        ray_fetch<LIST>(p, __builtin_amdgcn_readfirstlane((int)rp), R, b, ray_v, o3, d3);
+        const int ray = __builtin_amdgcn_readfirstlane(ray_v);
         float4 gfeat[2];
 #pragma unroll
         for (int ot = 0; ot < 2; ++ot) gfeat[ot] = load_g_feat4(p, (size_t)ray * 32 + 16 * ot + 4 * g);
@@ -89,11 +89,29 @@ raymarch_bwd_camera_kernel(const RayParams p, float* __restrict__ ray_grad) {
             out[3 + k] = wave_sum(acc_d[k]) * p.coord_scale;
         }
         if (lane == 0) {
-            float* dst = ray_grad + (size_t)ray * 6;
+            if constexpr (LIST) {
 #pragma unroll
-            for (int k = 0; k < 6; ++k) dst[k] = out[k];
+                for (int k = 0; k < 3; ++k) { ray_grad[(size_t)ray * 3 + k] = out[k]; d_dir[(size_t)ray * 3 + k] = out[3 + k]; }
+            } else {
+                float* dst = ray_grad + (size_t)ray * 6;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) dst[k] = out[k];
+            }
         }
     }
+}
+
+template <int S, bool DEC16>
+__global__ void __launch_bounds__(kCamWaves * 64, 2)
+raymarch_bwd_camera_kernel(const RayParams p, float* __restrict__ ray_grad) {
+    ray_grad_body<S, DEC16, false>(p, ray_grad, nullptr);
+}
+
+// hfagp_raymarch_rays_bwd_rays: one writer per ray, no atomics, no reduction
+template <int S, bool DEC16>
+__global__ void __launch_bounds__(kCamWaves * 64, 2)
+raymarch_bwd_rays_kernel(const RayParams p, float* __restrict__ d_origins, float* __restrict__ d_directions) {
+    ray_grad_body<S, DEC16, true>(p, d_origins, d_directions);
 }
 
 // One workgroup per frame.  Thread t walks rays t, t + 256, ...; 17 partial sums (12 of cam2world rows 0-2, fx, skew, cx, fy, cy),
@@ -178,6 +196,22 @@ static void launch_camera(const RayParams& p, float* ray_grad, hipStream_t s) {
     const unsigned blocks = (unsigned)std::min<long long>((ntiles + kCamWaves - 1) / kCamWaves, (long long)kNumCU * 6);
     if (p.a.planes_absmax) raymarch_bwd_camera_kernel<S, true><<<blocks, kCamWaves * 64, 0, s>>>(p, ray_grad);
     else raymarch_bwd_camera_kernel<S, false><<<blocks, kCamWaves * 64, 0, s>>>(p, ray_grad);
+}
+
+template <int S>
+static void launch_rays(const RayParams& p, float* d_origins, float* d_directions, hipStream_t s) {
+    const long long ntiles = (long long)p.total_rays * (S / 16);
+    const unsigned blocks = (unsigned)std::min<long long>((ntiles + kCamWaves - 1) / kCamWaves, (long long)kNumCU * 6);
+    if (p.a.planes_absmax) raymarch_bwd_rays_kernel<S, true><<<blocks, kCamWaves * 64, 0, s>>>(p, d_origins, d_directions);
+    else raymarch_bwd_rays_kernel<S, false><<<blocks, kCamWaves * 64, 0, s>>>(p, d_origins, d_directions);
+}
+
+int launch_ray_list_grads(const RayParams& p, float* d_origins, float* d_directions, hipStream_t s) {
+    const int S = p.a.Sc + p.a.Sf;
+    if (S == 96) launch_rays<96>(p, d_origins, d_directions, s);
+    else if (S == 64) launch_rays<64>(p, d_origins, d_directions, s);
+    else launch_rays<32>(p, d_origins, d_directions, s);
+    return check_launch("raymarch_rays_bwd_rays");
 }
 
 // (raymarch_common.h) the reduction alone, for the other producer of ray_grad records: raymarch_normals_camera.hip

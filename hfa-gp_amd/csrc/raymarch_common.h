@@ -20,13 +20,22 @@ struct RayParams {
     const float* g_depth, *g_wsum;   // backward only, optional: [B][R] dL/d (clamped depth), dL/d opacity (hfagp.h HfagpRaymarchGeomGrads)
     const float* depth_range;        // with g_depth: 2 floats on the device, the batch-global clamp range of the depth
     float* rec;          // backward only: per-sample records [B*R][S][4] = (depth, omega, d sigma, -)
+    // ray list (hfagp.h HfagpRayListArgs; the *_rays_* kernels): the caller's rays [B][R][3], taken as given (directions are not
+    // normalised: a sample is o + t d).  Null for the pinhole grid, whose kernels never read these three.
+    const float* ray_o, *ray_d;
+    int R;               // rays per frame: res * res for the grid
 };
 
-inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char* who) {
-    HFAGP_REQUIRE(a->planes && a->cam2world && a->intrinsics && a->u_strat && a->u_imp && a->dec_w0 && a->dec_b0 &&
+// rays = null: the pinhole grid of a->cam2world / a->intrinsics / a->res.  Else the ray list {origins, directions} of R rays per
+// frame, and those three members of *a are ignored (they may be NULL / 0).
+struct RayList { const float* o; const float* d; int R; };
+inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char* who, const RayList* rays = nullptr) {
+    HFAGP_REQUIRE(a->planes && (rays || (a->cam2world && a->intrinsics)) && a->u_strat && a->u_imp && a->dec_w0 && a->dec_b0 &&
                       a->dec_w1 && a->dec_b1,
                   HFAGP_EBADARG, "%s: null pointer", who);
-    HFAGP_REQUIRE(a->B > 0 && a->H > 1 && a->W > 1 && a->res > 0, HFAGP_EBADARG, "%s: bad dims", who);
+    HFAGP_REQUIRE(!rays || (rays->o && rays->d), HFAGP_EBADARG, "%s: null pointer (ray_origins / ray_directions)", who);
+    HFAGP_REQUIRE(!rays || rays->R > 0, HFAGP_EBADARG, "%s: R = %d rays per frame", who, rays ? rays->R : 0);
+    HFAGP_REQUIRE(a->B > 0 && a->H > 1 && a->W > 1 && (rays || a->res > 0), HFAGP_EBADARG, "%s: bad dims", who);
     HFAGP_REQUIRE(a->box_warp > 0.f && a->ray_end > a->ray_start, HFAGP_EBADARG, "%s: bad ray range", who);
     HFAGP_REQUIRE(a->Sc == a->Sf && (a->Sc == 16 || a->Sc == 32 || a->Sc == 48), HFAGP_EUNSUPPORTED,
                   "%s: unsupported sample counts Sc=%d Sf=%d (supported: 16+16, 32+32, 48+48)", who, a->Sc, a->Sf);
@@ -34,16 +43,25 @@ inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char*
     p.lin_step = ((float)a->ray_end - (float)a->ray_start) / (float)(a->Sc - 1);
     p.delta = (float)((a->ray_end - a->ray_start) / (double)(a->Sc - 1));
     p.coord_scale = (float)(2.0 / (double)a->box_warp);
-    const long long total = (long long)a->B * a->res * a->res;
+    const long long per_frame = rays ? (long long)rays->R : (long long)a->res * a->res;
+    const long long total = (long long)a->B * per_frame;
     HFAGP_REQUIRE(total < (1ll << 31), HFAGP_EUNSUPPORTED, "%s: too many rays", who);
     p.total_rays = (int)total;
+    p.ray_o = rays ? rays->o : nullptr;
+    p.ray_d = rays ? rays->d : nullptr;
+    p.R = (int)per_frame;
+    if (rays) { p.a.cam2world = p.a.intrinsics = nullptr; p.a.res = 0; }
     p.g_feat = nullptr;
     p.g_depth = p.g_wsum = p.depth_range = nullptr;
     p.rec = nullptr;
     return HFAGP_OK;
 }
 
-int launch_raymarch(const RayParams& p, bool grads, hipStream_t s);   // raymarch.hip
+int launch_raymarch(const RayParams& p, bool grads, hipStream_t s);   // raymarch.hip (grid or list: p.ray_o)
+// raymarch_bwd.hip: everything of hfagp_raymarch_bwd_geom after the arguments became `p` (pass 1, then one of the pass-2 forms)
+int raymarch_bwd_run(const HfagpRaymarchBwdArgs* a, RayParams& p, const HfagpRaymarchGeomGrads* geom, hipStream_t s);
+// raymarch_camera.hip: the per-ray kernel on a list -> d_origins, d_directions [B][R][3]
+int launch_ray_list_grads(const RayParams& p, float* d_origins, float* d_directions, hipStream_t s);
 // raymarch_camera.hip: camera_reduce_kernel on ray_grad [B][R][6] -> d_cam2world [B][16], d_intrinsics [B][9]
 void launch_camera_reduce(const HfagpRaymarchArgs& a, const float* ray_grad, float* d_cam2world, float* d_intrinsics, hipStream_t s);
 
@@ -58,7 +76,7 @@ struct RowsOut {
     unsigned* dfs;       // [slots][32] bf16 hi << 16 | bf16 lo
     int P;               // planes scattered (2: planes 1 and 2 mirror each other)
 };
-size_t rows_scratch_bytes(const HfagpRaymarchArgs& a);                                         // 0: variant does not apply
+size_t rows_scratch_bytes(const HfagpRaymarchArgs& a, long long rays_per_frame);              // 0: variant does not apply
 int rows_prepare(const RayParams& p, void* scratch, size_t bytes, RowsOut& out, hipStream_t s);    // S1, scan, S2
 int rows_gather(const RayParams& p, void* scratch, float* d_planes, hipStream_t s);               // G
 
@@ -168,6 +186,28 @@ __device__ __forceinline__ void ray_setup(const HfagpRaymarchArgs& a, int b, int
     const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(d3[0], d3[0]), __fmul_rn(d3[1], d3[1])),
                                                  __fmul_rn(d3[2], d3[2]))), 1e-12f);
     d3[0] = __fdiv_rn(d3[0], nrm); d3[1] = __fdiv_rn(d3[1], nrm); d3[2] = __fdiv_rn(d3[2], nrm);
+}
+
+// Ray number i of the launch's sequence -> frame, index into the [B][R] tensors and (SETUP) origin and direction: the ONE fetch of
+// every ray-march kernel.  LIST = false: the pinhole grid (ray_of + ray_setup; R = res * res).  LIST = true: ray i of the caller's
+// list as it stands — six loads, nothing is normalised.
+template <bool LIST, bool SETUP = true>
+__device__ __forceinline__ void ray_fetch(const RayParams& p, int i, int R, int& b, int& ray, float o3[3], float d3[3]) {
+    if constexpr (LIST) {
+        b = i / R;
+        ray = i;
+        if constexpr (SETUP) {
+            const float* po = p.ray_o + (size_t)i * 3;
+            const float* pd = p.ray_d + (size_t)i * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) { o3[k] = po[k]; d3[k] = pd[k]; }
+        }
+    } else {
+        int pi, pj;
+        ray_of(i, p.a.res, b, pi, pj);
+        ray = b * R + pi * p.a.res + pj;
+        if constexpr (SETUP) ray_setup(p.a, b, pi, pj, o3, d3);
+    }
 }
 
 // ---------------------------------------------------------------- tri-plane gather

@@ -1,0 +1,50 @@
+// The ray marcher on caller-given ray lists (hfagp.h HfagpRayListArgs): the entry points.  The kernels are the list instantiations
+// of the grid's — raymarch_rays_kernel (raymarch.hip), raymarch_bwd_tiles_kernel / raymarch_bwd_df_kernel <.., LIST>
+// (raymarch_bwd.hip), raymarch_bwd_bins_kernel <.., LIST> (raymarch_rows.hip), raymarch_bwd_rays_kernel (raymarch_camera.hip) — which
+// differ from them in the ray fetch alone (raymarch_common.h ray_fetch).  Here: argument checks and the hand-over to the launchers
+// those units share with their grid entry points.
+#include "raymarch_common.h"
+
+using namespace hfagp;
+
+extern "C" int hfagp_raymarch_rays_fwd(const HfagpRayListArgs* a, void* stream) {
+    HFAGP_REQUIRE(a, HFAGP_EBADARG, "raymarch_rays_fwd: null pointer");
+    const HfagpRaymarchArgs* f = &a->base;
+    HFAGP_REQUIRE(f->feat && f->depth && f->wsum && f->tminmax, HFAGP_EBADARG, "raymarch_rays_fwd: null pointer");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(f, p, "raymarch_rays_fwd", &rays);
+    if (rc != HFAGP_OK) return rc;
+    return launch_raymarch(p, false, (hipStream_t)stream);
+}
+
+extern "C" int hfagp_raymarch_rays_bwd(const HfagpRayListBwdArgs* a, const HfagpRaymarchGeomGrads* geom, void* stream) {
+    HFAGP_REQUIRE(a && a->bwd.d_planes && a->bwd.rec, HFAGP_EBADARG, "raymarch_rays_bwd: null pointer");
+    const float* g_depth = geom ? geom->g_depth : nullptr;
+    const float* g_wsum = geom ? geom->g_wsum : nullptr;
+    HFAGP_REQUIRE(a->bwd.g_feat || g_depth || g_wsum, HFAGP_EBADARG,
+                  "raymarch_rays_bwd: no upstream gradient (g_feat, g_depth and g_wsum are all null)");
+    HFAGP_REQUIRE(!g_depth || geom->depth_range, HFAGP_EBADARG, "raymarch_rays_bwd: g_depth needs depth_range");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->bwd.fwd, p, "raymarch_rays_bwd", &rays);
+    if (rc != HFAGP_OK) return rc;
+    return raymarch_bwd_run(&a->bwd, p, geom, (hipStream_t)stream);
+}
+
+extern "C" size_t hfagp_raymarch_rays_bwd_rows_bytes(const HfagpRayListArgs* a) {
+    if (!a || a->base.B <= 0 || a->base.H <= 1 || a->base.W <= 1 || a->R <= 0) return 0;
+    if ((long long)a->base.B * a->R >= (1ll << 31)) return 0;
+    return rows_scratch_bytes(a->base, a->R);
+}
+
+extern "C" int hfagp_raymarch_rays_bwd_rays(const HfagpRayListBwdArgs* a, float* d_origins, float* d_directions, void* stream) {
+    HFAGP_REQUIRE(a && a->bwd.rec && d_origins && d_directions, HFAGP_EBADARG, "raymarch_rays_bwd_rays: null pointer");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->bwd.fwd, p, "raymarch_rays_bwd_rays", &rays);
+    if (rc != HFAGP_OK) return rc;
+    p.g_feat = a->bwd.g_feat;
+    p.rec = a->bwd.rec;
+    return launch_ray_list_grads(p, d_origins, d_directions, (hipStream_t)stream);
+}

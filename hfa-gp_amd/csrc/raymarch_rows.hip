@@ -51,7 +51,7 @@ struct RowsDev {
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // carve the scratch buffer; returns the bytes needed (base may be null), 0 when the variant does not apply
-static size_t rows_layout(const HfagpRaymarchArgs& a, unsigned char* base, RowsDev& d) {
+static size_t rows_layout(const HfagpRaymarchArgs& a, long long rays_per_frame, unsigned char* base, RowsDev& d) {
     const bool mirror = a.plane_axes == 0 && a.H == a.W;
     d.P = mirror ? 2 : 3;
     d.XB = (a.W + kRowsStrip - 1) / kRowsStrip;
@@ -60,7 +60,7 @@ static size_t rows_layout(const HfagpRaymarchArgs& a, unsigned char* base, RowsD
     if (nbf > kRowsMaxBins) return 0;
     d.NBF = (int)nbf;
     const long long nb = nbf * a.B;
-    const long long samples = (long long)a.B * a.res * a.res * (a.Sc + a.Sf);
+    const long long samples = (long long)a.B * rays_per_frame * (a.Sc + a.Sf);
     const long long cap = 2ll * d.P * samples + 16ll * nb;
     if (nb > (1ll << 24) || cap >= (1ll << 31)) return 0;
     d.NB = (int)nb;
@@ -101,7 +101,9 @@ __device__ __forceinline__ RowsKey rows_key(const HfagpRaymarchArgs& a, const Ro
 
 // S1 (PLACE = false) / S2 (PLACE = true): a workgroup = 32 rays of one image column (their samples fall into few bins:
 // one or two strips of every plane), thread = (ray, every 8th sample)
-template <int S, bool PLACE>
+// LIST: a workgroup = 32 consecutive rays of one frame's list (chunks_per_col = chunks per frame); the counting sort is correct for
+// any grouping, the grouping only decides how many bins a workgroup touches.
+template <int S, bool PLACE, bool LIST = false>
 __global__ void __launch_bounds__(256)
 raymarch_bwd_bins_kernel(const RayParams p, const RowsDev r, const int chunks_per_col) {
     extern __shared__ unsigned rows_smem[];
@@ -110,14 +112,21 @@ raymarch_bwd_bins_kernel(const RayParams p, const RowsDev r, const int chunks_pe
     const HfagpRaymarchArgs& a = p.a;
     const int chunk = blockIdx.x;
     const int col_id = chunk / chunks_per_col, piece = chunk % chunks_per_col;
-    const int b = col_id / a.res, pj = col_id % a.res;
+    const int b = LIST ? col_id : col_id / a.res, pj = LIST ? 0 : col_id % a.res;
     const int pi = piece * kRowsRays + (threadIdx.x >> 3), sub = threadIdx.x & 7;
-    const bool active = pi < a.res;
+    const bool active = pi < (LIST ? p.R : a.res);
     for (int i = threadIdx.x; i < r.NBF; i += 256) hist[i] = 0;
     __syncthreads();
     float o3[3], d3[3];
-    ray_setup(a, b, min(pi, a.res - 1), pj, o3, d3);
-    const size_t ray = (size_t)b * a.res * a.res + (size_t)min(pi, a.res - 1) * a.res + pj;
+    size_t ray;
+    if constexpr (LIST) {
+        int bb, rr;
+        ray_fetch<true>(p, b * p.R + min(pi, p.R - 1), p.R, bb, rr, o3, d3);      // (frame b: the chunk never leaves it)
+        ray = (size_t)rr;
+    } else {
+        ray_setup(a, b, min(pi, a.res - 1), pj, o3, d3);
+        ray = (size_t)b * a.res * a.res + (size_t)min(pi, a.res - 1) * a.res + pj;
+    }
     // the thread's S / 8 depths: all loads go out together and stay in registers for the second pass of S2
     const float* depth = p.rec + (ray * S + sub) * 4;
     float dep[S / 8];
@@ -334,21 +343,21 @@ raymarch_bwd_rows_kernel(const RowsDev r, float* __restrict__ d_planes, const in
     }
 }
 
-size_t rows_scratch_bytes(const HfagpRaymarchArgs& a) {
+size_t rows_scratch_bytes(const HfagpRaymarchArgs& a, long long rays_per_frame) {
     RowsDev d;
-    return rows_layout(a, nullptr, d);
+    return rows_layout(a, rays_per_frame, nullptr, d);
 }
 
-template <int S>
+template <int S, bool LIST>
 static void launch_bins(const RayParams& p, const RowsDev& d, int nchunks, int chunks_per_col, hipStream_t s) {
-    raymarch_bwd_bins_kernel<S, false><<<nchunks, 256, (size_t)d.NBF * 4, s>>>(p, d, chunks_per_col);
+    raymarch_bwd_bins_kernel<S, false, LIST><<<nchunks, 256, (size_t)d.NBF * 4, s>>>(p, d, chunks_per_col);
     raymarch_bwd_scan_kernel<<<1, 1024, 0, s>>>(d);
-    raymarch_bwd_bins_kernel<S, true><<<nchunks, 256, (size_t)d.NBF * 8, s>>>(p, d, chunks_per_col);
+    raymarch_bwd_bins_kernel<S, true, LIST><<<nchunks, 256, (size_t)d.NBF * 8, s>>>(p, d, chunks_per_col);
 }
 
 int rows_prepare(const RayParams& p, void* scratch, size_t bytes, RowsOut& out, hipStream_t s) {
     RowsDev d;
-    const size_t need = rows_layout(p.a, reinterpret_cast<unsigned char*>(scratch), d);
+    const size_t need = rows_layout(p.a, p.R, reinterpret_cast<unsigned char*>(scratch), d);
     HFAGP_REQUIRE(need != 0 && bytes >= need, HFAGP_EBADARG, "raymarch_bwd: rows_scratch of %zu bytes, %zu needed", bytes, need);
     static bool raised = false;
     if (!raised) {
@@ -356,7 +365,10 @@ int rows_prepare(const RayParams& p, void* scratch, size_t bytes, RowsOut& out, 
         hipError_t e = hipSuccess;
         const void* fns[] = {reinterpret_cast<const void*>(&raymarch_bwd_bins_kernel<96, true>),
                              reinterpret_cast<const void*>(&raymarch_bwd_bins_kernel<64, true>),
-                             reinterpret_cast<const void*>(&raymarch_bwd_bins_kernel<32, true>)};
+                             reinterpret_cast<const void*>(&raymarch_bwd_bins_kernel<32, true>),
+                             reinterpret_cast<const void*>(&raymarch_bwd_bins_kernel<96, true, true>),
+                             reinterpret_cast<const void*>(&raymarch_bwd_bins_kernel<64, true, true>),
+                             reinterpret_cast<const void*>(&raymarch_bwd_bins_kernel<32, true, true>)};
         for (const void* f : fns)
             if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) {
@@ -371,11 +383,19 @@ int rows_prepare(const RayParams& p, void* scratch, size_t bytes, RowsOut& out, 
         return HFAGP_ELAUNCH;
     }
     const int S = p.a.Sc + p.a.Sf;
-    const int chunks_per_col = (p.a.res + kRowsRays - 1) / kRowsRays;
-    const int nchunks = p.a.B * p.a.res * chunks_per_col;
-    if (S == 96) launch_bins<96>(p, d, nchunks, chunks_per_col, s);
-    else if (S == 64) launch_bins<64>(p, d, nchunks, chunks_per_col, s);
-    else launch_bins<32>(p, d, nchunks, chunks_per_col, s);
+    if (p.ray_o) {                               // a ray list: chunks of 32 consecutive rays of a frame
+        const int chunks_per_frame = (p.R + kRowsRays - 1) / kRowsRays;
+        const long long nchunks = (long long)p.a.B * chunks_per_frame;            // (< 2^31 / 32: total_rays < 2^31, B < 2^24)
+        if (S == 96) launch_bins<96, true>(p, d, (int)nchunks, chunks_per_frame, s);
+        else if (S == 64) launch_bins<64, true>(p, d, (int)nchunks, chunks_per_frame, s);
+        else launch_bins<32, true>(p, d, (int)nchunks, chunks_per_frame, s);
+    } else {
+        const int chunks_per_col = (p.a.res + kRowsRays - 1) / kRowsRays;
+        const int nchunks = p.a.B * p.a.res * chunks_per_col;
+        if (S == 96) launch_bins<96, false>(p, d, nchunks, chunks_per_col, s);
+        else if (S == 64) launch_bins<64, false>(p, d, nchunks, chunks_per_col, s);
+        else launch_bins<32, false>(p, d, nchunks, chunks_per_col, s);
+    }
     out.pos = d.pos;
     out.dfs = d.dfs;
     out.P = d.P;
@@ -384,7 +404,7 @@ int rows_prepare(const RayParams& p, void* scratch, size_t bytes, RowsOut& out, 
 
 int rows_gather(const RayParams& p, void* scratch, float* d_planes, hipStream_t s) {
     RowsDev d;
-    rows_layout(p.a, reinterpret_cast<unsigned char*>(scratch), d);
+    rows_layout(p.a, p.R, reinterpret_cast<unsigned char*>(scratch), d);
     raymarch_bwd_rows_kernel<<<(unsigned)((d.max_units + 3) / 4), 256, 0, s>>>(d, d_planes, p.a.H, p.a.W);
     return check_launch("raymarch_bwd/rows");
 }
@@ -395,5 +415,5 @@ using namespace hfagp;
 
 extern "C" size_t hfagp_raymarch_bwd_rows_bytes(const HfagpRaymarchArgs* fwd) {
     if (!fwd || fwd->B <= 0 || fwd->H <= 1 || fwd->W <= 1 || fwd->res <= 0) return 0;
-    return rows_scratch_bytes(*fwd);
+    return rows_scratch_bytes(*fwd, (long long)fwd->res * fwd->res);
 }

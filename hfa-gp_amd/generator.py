@@ -1083,6 +1083,70 @@ class TriPlaneGenerator(nn.Module):
                                           **self._query_kwargs())
         return {"rgb": rgb, "sigma": sigma}
 
+    # ------------------------------------------------------------------ explicit ray lists (EG3D ImportanceRenderer.forward's rays)
+    def _rays_kwargs(self) -> dict:
+        """`_render_args` without the camera: what ops.raymarch_rays* take next to the planes, the rays and the uniforms."""
+        cfg = self.cfg
+        return dict(zip(ops._DEC, self.decoder_params()), ray_start=cfg.ray_start, ray_end=cfg.ray_end, box_warp=cfg.box_warp,
+                    decoder_lr_mul=cfg.decoder_lr_mul, plane_axes=ops._plane_axes_id(cfg.plane_axes), white_back=cfg.white_back,
+                    decoder_precision=cfg.decoder_precision)
+
+    def render_rays(self, ws: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
+                    u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
+                    noise_mode: str = "const") -> Dict[str, torch.Tensor]:
+        """The renderer of `synthesis` on caller-given rays: ray_origins / ray_directions [B,R,3] in world units, R arbitrary — a
+        crop or zoomed window (`cam_utils.ray_grid(c, res, window=)`), several cameras of one identity as one longer list in that
+        frame (`torch.cat` along dim 1), random ray batches, or any camera model written in torch.  Directions are taken as given,
+        not normalised: a sample is o + t·d with t in the config's [ray_start, ray_end], as EG3D's renderer takes them.
+        → {'feature' [B,R,32], 'rgb' [B,R,3] (the first three features), 'depth' [B,R] (clamped to this call's global sample range,
+        as 'image_depth' is), 'mask' [B,R] (opacity)}.  One backbone pass, one launch (ops.raymarch_rays); no super-resolution.
+        Under grad the four are differentiable w.r.t. `ws`, the generator parameters that require grad and the rays (so a label
+        `c` gets its gradient through `ray_grid` from torch autograd), at the price of a backbone backward pass of its own; inside a
+        trainer step scope it raises, as `sample_mixed(differentiable=True)` does.  `u_strat` [B,R,Sc] / `u_imp` [B·R,Sf]: the
+        uniforms of the two sampling passes (drawn here when None).  R = 0 or B = 0: empty tensors, nothing is launched."""
+        if noise_mode != "const":
+            raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
+        for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
+            if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] != ws.shape[0]:
+                raise ValueError(f"expected {name} [B, R, 3] for ws of batch {ws.shape[0]}, got {tuple(t.shape)}")
+            if not t.is_floating_point():
+                raise TypeError(f"TriPlaneGenerator.render_rays: {name} must be a floating-point tensor, got {t.dtype}")
+        if ray_origins.shape != ray_directions.shape:
+            raise ValueError(f"ray_directions {tuple(ray_directions.shape)} must match ray_origins {tuple(ray_origins.shape)}")
+        self._query_guard("render_rays", ws, differentiable=True)
+        if not (ray_origins.is_cuda and ray_directions.is_cuda):
+            raise RuntimeError("TriPlaneGenerator.render_rays: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
+        cfg = self.cfg
+        b, r = ray_origins.shape[0], ray_origins.shape[1]
+        dev = ws.device
+        params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
+        grad = torch.is_grad_enabled() and (ws.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad or
+                                            any(p.requires_grad for p in params))
+        if b == 0 or r == 0:
+            zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0      # keeps the autograd edges
+            feat = torch.zeros(b, r, 32, device=dev) + zero
+            return {"feature": feat, "rgb": feat[..., :3], "depth": torch.zeros(b, r, device=dev) + zero,
+                    "mask": torch.zeros(b, r, device=dev) + zero}
+        if u_strat is None:
+            u_strat = torch.rand(b, r, cfg.depth_resolution, device=dev)
+        if u_imp is None:
+            u_imp = torch.rand(b * r, cfg.depth_resolution_importance, device=dev)
+        u_strat, u_imp = u_strat.detach().float().reshape(b, r, -1).contiguous(), u_imp.detach().float().contiguous()
+        if grad:
+            if getattr(self, "_grad_sink", None) is not None or getattr(self, "_grad_inplace", False):
+                raise RuntimeError("TriPlaneGenerator.render_rays under grad inside a trainer step scope: its backward is a second "
+                                   "backbone pass and would release every parameter to the gradient sink twice")
+            from .autograd import RenderRaysFn
+            feat, depth, mask = RenderRaysFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, *params)
+        else:
+            with torch.no_grad():
+                planes, pam = self._query_planes(ws)
+                feat, depth, mask, tmm = ops.raymarch_rays(planes, ray_origins.detach().float().contiguous(),
+                                                           ray_directions.detach().float().contiguous(), u_strat, u_imp,
+                                                           planes_absmax=pam, **self._rays_kwargs())
+                depth = ops.depth_clamp_(depth, tmm)
+        return {"feature": feat, "rgb": feat[..., :3], "depth": depth, "mask": mask}
+
     def sample(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], z: torch.Tensor, c: torch.Tensor,
                truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:
         """EG3D TriPlaneGenerator.sample: `mapping(z, c, truncation_psi)` then `sample_mixed`.  Only truncation_cutoff=None

@@ -727,6 +727,36 @@ def _ray_args(who: str, f, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0
     return b, h, w, r, sc, sf
 
 
+def _ray_list_args(who: str, l, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, ray_start: float,
+                   ray_end: float, box_warp: float, decoder_lr_mul: float, plane_axes, white_back: bool, decoder_precision: str,
+                   planes_absmax, state):
+    """`_ray_args` for a ray list: fills the RayListArgs / RayListBwdArgs ``l`` — the rays, R, and its RaymarchArgs member but the
+    camera (ignored by the list entry points) and the forward's outputs — and returns (B, H, W, R, Sc, Sf).  Owns the checks of the
+    rays' shapes, the uniforms' element counts, `state` and of device, dtype and contiguity of every input."""
+    f = l.base if isinstance(l, L.RayListArgs) else l.bwd.fwd
+    b, h, w = _planes_dims(who, planes)
+    for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
+        if _chk(t, f"{who}: {name}").dim() != 3 or t.shape[0] != b or t.shape[2] != 3:
+            raise RuntimeError(f"{who}: {name} must be [B={b}, R, 3], got {tuple(t.shape)}")
+    if ray_origins.shape != ray_directions.shape:
+        raise RuntimeError(f"{who}: ray_origins {tuple(ray_origins.shape)} and ray_directions {tuple(ray_directions.shape)} differ")
+    r = ray_origins.shape[1]
+    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    if u_strat.numel() != b * r * sc or u_imp.numel() != b * r * sf:
+        raise RuntimeError(f"{who}: u_strat / u_imp have the wrong number of elements")
+    if state is not None and _chk(state, f"{who}: state").shape != (b, r, (sc + sf) * 35):
+        raise RuntimeError(f"{who}: state must be [B, R, {(sc + sf) * 35}] (raymarch_rays_state), got {tuple(state.shape)}")
+    for name, t in (("u_strat", u_strat), ("u_imp", u_imp)):
+        setattr(f, name, _ptr(_chk(t, f"{who}: {name}")))
+    f.planes, f.state = _ptr(planes), _ptr(state)
+    _fill_decoder(who, f, planes, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_precision, planes_absmax)
+    f.B, f.H, f.W, f.res, f.Sc, f.Sf = b, h, w, 0, sc, sf
+    f.plane_axes, f.white_back = _plane_axes_id(plane_axes), int(white_back)
+    f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
+    l.ray_origins, l.ray_directions, l.R = _ptr(ray_origins), _ptr(ray_directions), r
+    return b, h, w, r, sc, sf
+
+
 def _dec_grad_out(who: str, a, params, decoder_grads: bool, dec_out):
     """The four tensors the decoder-parameter gradients are ACCUMULATED into, their pointers set in the RaymarchBwdArgs /
     PlanesQueryBwdArgs ``a``: ``dec_out`` (the parameters' .grad slices, say) or fresh zeros; None without ``decoder_grads``."""
@@ -770,6 +800,31 @@ def raymarch(planes: torch.Tensor, cam2world: torch.Tensor, intrinsics: torch.Te
     tmm = torch.empty(b, r, 2, device=dev, dtype=torch.float32)
     a.feat, a.depth, a.wsum, a.tminmax = _ptr(feat), _ptr(depth), _ptr(wsum), _ptr(tmm)
     L.check(L.lib().hfagp_raymarch_fwd(C.byref(a), _stream()), "raymarch_fwd")
+    return feat, depth, wsum, tmm
+
+
+def raymarch_rays(planes: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor, u_strat: torch.Tensor,
+                  u_imp: torch.Tensor, dec_w0: torch.Tensor, dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor,
+                  ray_start: float, ray_end: float, box_warp: float, decoder_lr_mul: float = 1.0, plane_axes: int = 0,
+                  white_back: bool = False, decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None,
+                  state: Optional[torch.Tensor] = None):
+    """`raymarch` on caller-given rays: ray_origins / ray_directions [B,R,3] (directions as given, not normalised: a sample is
+    o + t d) instead of (cam2world, intrinsics, res) → feat [B,R,32], depth [B,R] (unclamped), wsum [B,R], tminmax [B,R,2].
+    u_strat [B,R,Sc], u_imp [B*R,Sf]; ``state``: `raymarch_rays_state`.  Everything else as `raymarch`."""
+    a = L.RayListArgs()
+    b, _, _, r, _, _ = _ray_list_args("raymarch_rays", a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1,
+                                      dec_b1, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision,
+                                      planes_absmax, state)
+    dev = planes.device
+    feat = torch.empty(b, r, 32, device=dev, dtype=torch.float32)
+    depth = torch.empty(b, r, device=dev, dtype=torch.float32)
+    wsum = torch.empty(b, r, device=dev, dtype=torch.float32)
+    tmm = torch.empty(b, r, 2, device=dev, dtype=torch.float32)
+    if b * r == 0:
+        return feat, depth, wsum, tmm
+    f = a.base
+    f.feat, f.depth, f.wsum, f.tminmax = _ptr(feat), _ptr(depth), _ptr(wsum), _ptr(tmm)
+    L.check(L.lib().hfagp_raymarch_rays_fwd(C.byref(a), _stream()), "raymarch_rays_fwd")
     return feat, depth, wsum, tmm
 
 
@@ -1108,6 +1163,11 @@ def depth_clamp_(depth: torch.Tensor, tminmax: torch.Tensor) -> torch.Tensor:
 def raymarch_state(b: int, res: int, sc: int, sf: int, device) -> torch.Tensor:
     """Buffer for `raymarch(..., state=)` / `raymarch_bwd(..., state=)`: [B, R, 35 (Sc + Sf)] floats = 13.4 KB per ray at 48 + 48."""
     return torch.empty(b, res * res, (sc + sf) * 35, device=device, dtype=torch.float32)
+
+
+def raymarch_rays_state(b: int, r: int, sc: int, sf: int, device) -> torch.Tensor:
+    """`raymarch_state` for a list of ``r`` rays per frame: the buffer of `raymarch_rays(..., state=)` / `raymarch_rays_bwd(..., state=)`."""
+    return torch.empty(b, r, (sc + sf) * 35, device=device, dtype=torch.float32)
 
 
 def _decoder_bound(planes: torch.Tensor, decoder_precision: str, planes_absmax: Optional[torch.Tensor]):
@@ -1669,6 +1729,128 @@ def raymarch_bwd_camera(g_feat: Optional[torch.Tensor], planes: torch.Tensor, re
     L.check(L.lib().hfagp_raymarch_bwd_camera(C.byref(a), _ptr(ray_grad), _ptr(d_c2w), _ptr(d_intr), _stream()),
             "raymarch_bwd_camera")
     return d_c2w, d_intr, ray_grad
+
+
+def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
+                      u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, ray_start: float, ray_end: float, box_warp: float,
+                      decoder_lr_mul: float = 1.0, plane_axes: int = 0, white_back: bool = False, return_rec: bool = False,
+                      decoder_grads: bool = False, decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None,
+                      state: Optional[torch.Tensor] = None, rows: Optional[bool] = None, dec_out=None, _out=None,
+                      g_depth: Optional[torch.Tensor] = None, g_wsum: Optional[torch.Tensor] = None,
+                      depth_range: Optional[torch.Tensor] = None, rec_out: Optional[list] = None):
+    """`raymarch_bwd` of `raymarch_rays`: g_feat [B,R,32] (and / or g_depth, g_wsum [B,R]) → d planes [B,3,H,W,32], with the same
+    keywords and return forms.  ``rows``: None = sort + gather whenever it applies, False = the scatter kernels (the image-column
+    variant of the grid is not offered for a list).  The sort's scratch is bounded by `rows_scratch_cap()` as for the grid; a list may
+    be cut at any ray, so a call that needs more runs in frame chunks and, where one frame is too much, in ray chunks of a frame.
+    ``rec_out``: receives pass 1's records [B,R,Sc+Sf,4] (`raymarch_rays_bwd_rays` reads them)."""
+    who = "raymarch_rays_bwd"
+    b, _, _ = _planes_dims(who, planes)
+    r = ray_origins.shape[1] if ray_origins.dim() == 3 else -1
+    if g_feat is not None and _chk(g_feat, f"{who}: g_feat").shape != (b, r, 32):
+        raise RuntimeError(f"{who}: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
+    for t, name in ((g_depth, "g_depth"), (g_wsum, "g_wsum")):
+        if t is not None and _chk(t, f"{who}: {name}").shape != (b, r):
+            raise RuntimeError(f"{who}: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
+    if depth_range is not None and _chk(depth_range, f"{who}: depth_range").shape != (2,):
+        raise RuntimeError(f"{who}: depth_range must be [2] (ops.depth_range), got {tuple(depth_range.shape)}")
+    sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    d_planes, rec = _out if _out is not None else (
+        torch.zeros_like(planes), torch.empty(b, max(r, 0), sc + sf, 4, device=planes.device, dtype=torch.float32))
+    if rec_out is not None:
+        rec_out.append(rec)
+    if rows is None:
+        rows = os.environ.get("HFAGP_RAYBWD_ROWS", "1") != "0"
+    dec = _raymarch_rays_bwd_chunk(
+        g_feat=g_feat, planes=planes, ray_origins=ray_origins, ray_directions=ray_directions, u_strat=u_strat,
+        u_imp=u_imp.reshape(b, r, sf) if r >= 0 and u_imp.numel() == b * r * sf else u_imp, state=state, g_depth=g_depth, g_wsum=g_wsum,
+        depth_range=depth_range, d_planes=d_planes, rec=rec, decoder_grads=decoder_grads, dec_out=dec_out, rows=rows, dec_w0=dec_w0,
+        dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, ray_start=ray_start, ray_end=ray_end, box_warp=box_warp,
+        decoder_lr_mul=decoder_lr_mul, plane_axes=plane_axes, white_back=white_back, decoder_precision=decoder_precision,
+        planes_absmax=_decoder_bound(planes, decoder_precision, planes_absmax) if planes.numel() else None)
+    if decoder_grads:
+        return d_planes, dec
+    return (d_planes, rec) if return_rec else d_planes
+
+
+def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_strat, u_imp, state, g_depth, g_wsum, depth_range,
+                             d_planes, rec, decoder_grads, dec_out, rows, **scene):
+    """`raymarch_rays_bwd` of the rays it is given: the whole list or — from itself — a chunk of it (`_raymarch_bwd_frames` for a
+    list; u_imp arrives as [B,R,Sf]).  Fills ``d_planes`` and ``rec`` in place, returns the decoder-gradient tuple or None."""
+    who = "raymarch_rays_bwd"
+    a = L.RayListBwdArgs()
+    b, h, w, r, sc, sf = _ray_list_args(who, a, planes, ray_origins, ray_directions, u_strat, u_imp, state=state, **scene)
+    dec = _dec_grad_out(who, a.bwd, [scene[k] for k in _DEC], decoder_grads, dec_out)
+    if b * r == 0:
+        return dec
+    a.bwd.g_feat, a.bwd.d_planes, a.bwd.rec = _ptr(g_feat), _ptr(d_planes), _ptr(rec)
+    scratch = None
+    if rows:
+        fa = L.RayListArgs()
+        fa.base, fa.R = a.bwd.fwd, r
+        need = int(L.lib().hfagp_raymarch_rays_bwd_rows_bytes(C.byref(fa)))
+        cap = rows_scratch_cap(planes.device) if need > (4 << 30) or "HFAGP_RAYBWD_SCRATCH_GIB" in os.environ else (16 << 30)
+        if need > cap and b * r > 1:
+            # every per-ray input / output is [B, R, ...]: frames are contiguous slices, and so are the rays r0:r1 of ONE frame; the
+            # decoder gradients accumulate in the one `dec`, d_planes accumulates per frame, the depth range is the call's
+            per_ray = dict(g_feat=g_feat, ray_origins=ray_origins, ray_directions=ray_directions, u_strat=u_strat, u_imp=u_imp,
+                           state=state, g_depth=g_depth, g_wsum=g_wsum, rec=rec)
+            fit = max(1, int(b * r * cap // need))            # rays one call can take
+            nb, nr = (max(1, min(b - 1, fit // r)), r) if fit >= r and b > 1 else (1, max(1, min(r - 1, fit)))
+            chunks = 0
+            for b0 in range(0, b, nb):
+                for r0 in range(0, r, nr):
+                    cut = {k: None if t is None else t[b0:b0 + nb, r0:r0 + nr] for k, t in per_ray.items()}
+                    _raymarch_rays_bwd_chunk(**cut, planes=planes[b0:b0 + nb], d_planes=d_planes[b0:b0 + nb], depth_range=depth_range,
+                                             decoder_grads=decoder_grads, dec_out=dec, rows=rows, **scene)
+                    chunks += 1
+            ROWS_STATS.update(bytes=min(need, cap), chunks=chunks, path="rows")
+            return dec
+        if need > 0:
+            try:
+                scratch = torch.empty(need, device=planes.device, dtype=torch.uint8)
+                a.bwd.rows_scratch, a.bwd.rows_scratch_bytes = _ptr(scratch), need
+                ROWS_STATS.update(bytes=need, chunks=1, path="rows")
+            except torch.cuda.OutOfMemoryError:
+                _warn_once("rows_oom", f"{who}: {need / 2**30:.2f} GiB of sort scratch could not be allocated: this call runs the "
+                                       f"(~2 x slower) scatter kernels")
+        else:
+            _warn_once("rows_unsupported", f"{who}: the sort + gather backward does not take {h} x {w} planes (more than 8192 bins "
+                                           f"per frame): the (~2 x slower) scatter kernels run")
+        if scratch is None:
+            ROWS_STATS.update(bytes=0, chunks=1, path="scatter")
+    if g_depth is None and g_wsum is None and depth_range is None:
+        gg = None
+    else:
+        gg = L.RaymarchGeomGrads()
+        gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
+    L.check(L.lib().hfagp_raymarch_rays_bwd(C.byref(a), C.byref(gg) if gg is not None else None, _stream()), who)
+    return dec
+
+
+def raymarch_rays_bwd_rays(g_feat: Optional[torch.Tensor], planes: torch.Tensor, rec: torch.Tensor, ray_origins: torch.Tensor,
+                           ray_directions: torch.Tensor, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, ray_start: float,
+                           ray_end: float, box_warp: float, decoder_lr_mul: float = 1.0, plane_axes: int = 0, white_back: bool = False,
+                           decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None):
+    """The rays' gradient of `raymarch_rays` (hfagp_raymarch_rays_bwd_rays) → (d origins, d directions), each [B,R,3].  ``g_feat`` and
+    the other arguments as in the `raymarch_rays_bwd` call that wrote ``rec`` (its ``rec_out=`` / ``return_rec=True``): the depth,
+    opacity and white_back terms are already in the records.  Independent of the pass-2 form that call ran; one writer per ray, no
+    atomics: two calls return the same bits."""
+    who = "raymarch_rays_bwd_rays"
+    a = L.RayListBwdArgs()
+    b, _, _, r, sc, sf = _ray_list_args(who, a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1,
+                                        ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision,
+                                        planes_absmax, None)
+    if _chk(rec, f"{who}: rec").shape != (b, r, sc + sf, 4):
+        raise RuntimeError(f"{who}: rec must be [B, R, Sc + Sf, 4] = [{b}, {r}, {sc + sf}, 4], got {tuple(rec.shape)}")
+    if g_feat is not None and _chk(g_feat, f"{who}: g_feat").shape != (b, r, 32):
+        raise RuntimeError(f"{who}: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
+    d_o = torch.empty(b, r, 3, device=planes.device, dtype=torch.float32)
+    d_d = torch.empty(b, r, 3, device=planes.device, dtype=torch.float32)
+    if b * r == 0:
+        return d_o, d_d
+    a.bwd.g_feat, a.bwd.rec = _ptr(g_feat), _ptr(rec)
+    L.check(L.lib().hfagp_raymarch_rays_bwd_rays(C.byref(a), _ptr(d_o), _ptr(d_d), _stream()), who)
+    return d_o, d_d
 
 
 # ----------------------------------------------------------------------------- loss side of the fitting step

@@ -45,6 +45,8 @@
  *   hfagp_raymarch_bwd      <- autograd of the renderer: grid_sample / decoder / compositing adjoints
  *   hfagp_raymarch_bwd_geom <- the same with gradients of the expected depth and the opacity (silhouette / depth losses)
  *   hfagp_raymarch_bwd_camera <- autograd of RaySampler + grid_sample w.r.t. the sample positions: the gradient of the camera label
+ *   hfagp_raymarch_rays_fwd / _rays_bwd / _rays_bwd_rays <- ImportanceRenderer.forward on explicit (ray_origins, ray_directions) and
+ *                              its autograd w.r.t. planes, decoder and the rays (crops, multi-view lists, arbitrary camera models)
  *   hfagp_planes_query_bwd  <- autograd of sample_mixed (grid_sample + OSGDecoder at given points) w.r.t. planes, decoder and points
  *   hfagp_modconv_fwd modes HFAGP_CONV3X3_BWD / HFAGP_CONVS2_BWD <- conv2d_gradfix data gradients (the same GEMM kernel)
  *   hfagp_conv_wgrad (+ _workspace_bytes) <- conv2d_gradfix weight gradients
@@ -799,6 +801,46 @@ size_t hfagp_raymarch_bwd_rows_bytes(const HfagpRaymarchArgs* fwd);
  * summed over each frame's rays; row 3 of cam2world and intrinsics entries 3, 6, 7, 8 are written as 0.  No atomics: two calls
  * give the same bits.  HFAGP_EBADARG, nothing launched: a, a->rec or ray_grad NULL; one of the two camera outputs alone.     */
 int hfagp_raymarch_bwd_camera(const HfagpRaymarchBwdArgs* a, float* ray_grad, float* d_cam2world, float* d_intrinsics, void* stream);
+
+/* ------------------------------------------------------------------ ray lists (additive to ABI 15)
+ * The same renderer on R caller-given rays per frame instead of the res x res pinhole grid of a label: EG3D's
+ * ImportanceRenderer.forward(planes, decoder, ray_origins, ray_directions, rendering_kwargs) — crops and zoomed windows,
+ * several cameras of one identity as one longer list, random ray batches, camera models that are no 25-float label.
+ * Directions are taken as given and NOT normalised: sample s of a ray is origin + t_s * direction.  Everything after the ray
+ * fetch — depths, gather, decoder, compositing, the per-sample state and records — is the arithmetic of hfagp_raymarch_fwd /
+ * hfagp_raymarch_bwd_geom: the list ray_grid-of-a-label in row order renders what the grid call renders.
+ * In `base` (and `bwd.fwd`) cam2world, intrinsics and res are IGNORED and may be NULL / 0; u_strat, u_imp, the outputs, state,
+ * g_feat, rec and the geometry gradients are sized by R where the grid forms say res * res.  The rays of the launch are walked in
+ * list order, cut into eight contiguous parts (one per XCD): locality is the caller's order.
+ * HFAGP_EBADARG, nothing launched: a NULL struct, ray_origins or ray_directions NULL, R <= 0, then the checks of the grid entry
+ * point; HFAGP_EUNSUPPORTED: sample counts, B * R >= 2^31.                                                                     */
+typedef struct {
+    HfagpRaymarchArgs base;
+    const float* ray_origins;     /* [B][R][3] */
+    const float* ray_directions;  /* [B][R][3] */
+    int32_t R;                    /* rays per frame */
+} HfagpRayListArgs;
+
+typedef struct {
+    HfagpRaymarchBwdArgs bwd;     /* as for hfagp_raymarch_bwd; df_scratch is ignored (the column variant is image-shaped) */
+    const float* ray_origins;     /* [B][R][3] */
+    const float* ray_directions;  /* [B][R][3] */
+    int32_t R;
+} HfagpRayListBwdArgs;
+
+int hfagp_raymarch_rays_fwd(const HfagpRayListArgs* a, void* stream);
+/* d_planes (accumulated into), optional decoder gradients and rec, as hfagp_raymarch_bwd_geom (g may be NULL).  With
+ * bwd.rows_scratch of hfagp_raymarch_rays_bwd_rows_bytes bytes pass 2 is sort + gather (a workgroup of the sort takes 32
+ * consecutive rays of a frame's list); without it the per-sample scatter kernels run.                                         */
+int hfagp_raymarch_rays_bwd(const HfagpRayListBwdArgs* a, const HfagpRaymarchGeomGrads* g, void* stream);
+/* bytes of bwd.rows_scratch for this list (B, H, W, R, Sc, Sf, plane_axes are read); 0 = sort + gather does not apply           */
+size_t hfagp_raymarch_rays_bwd_rows_bytes(const HfagpRayListArgs* a);
+/* The rays' gradient.  After hfagp_raymarch_rays_bwd on the same arguments and stream (a->bwd.rec holds pass 1's records;
+ * d_planes, the scratch buffers and d_dec_* are ignored): d_origins, d_directions [B][R][3] are WRITTEN — per ray the positional
+ * derivative of the gather summed over its samples, plain and depth-weighted (the record hfagp_raymarch_bwd_camera forms before
+ * its reduction; the sample depths carry no gradient).  One writer per ray, no atomics, no reduction: two calls give the same
+ * bits.  HFAGP_EBADARG also for a->bwd.rec, d_origins or d_directions NULL.                                                  */
+int hfagp_raymarch_rays_bwd_rays(const HfagpRayListBwdArgs* a, float* d_origins, float* d_directions, void* stream);
 
 /* ------------------------------------------------------------------ gradients w.r.t. the generator weights
  * (needed once HFA-GP calls tune_generator(), trainer_rgb.py:69-71)                                       */
