@@ -453,13 +453,20 @@ class SynthesisFn(torch.autograd.Function):
         bw.finish_layer(c0rec)
         # ---- feature image: consumer = SR block0.conv0, plus the first 3 channels through image_raw
         feat_img = tape["feat_img"]
+        res, res_sr = tape["res"], cfg.neural_rendering_resolution        # the forward's rays (not the generator's current setting)
+        resampled = res != res_sr
         # (image_raw = channels 0..2 of the feature image: the two NCHW gradients are added inside the fused pass)
         g_feat, s = bw.pointwise(feat_img.contiguous(), dxs_conv=dxs, s_conv=c0rec0["styles"],
-                                 g_nchw3_a=g_rgb_raw.contiguous(), g_nchw3_b=None if g_raw is None else g_raw.float().contiguous())
+                                 g_nchw3_a=g_rgb_raw.contiguous(),
+                                 g_nchw3_b=None if g_raw is None or resampled else g_raw.float().contiguous())
         c0rec0["ds"] = s[:, 0]
         bw.finish_layer(c0rec0)
+        if resampled:
+            # adjoint of the resample in front of the SR blocks: their gradient back at the rays' resolution, with image_raw's (taken
+            # from the unresampled feature image) added in the same pass
+            g_feat = gen._timed("resize_aa_bwd", float(b) * (res * res + res_sr * res_sr) * 128, ops.resize_aa_bwd, g_feat, (res, res),
+                                g_nchw3=None if g_raw is None else g_raw.float().contiguous())
         # ---- renderer
-        res = cfg.neural_rendering_resolution
         geom = {}
         if "depth_range" in tape:    # synthesis(geometry=True); without it image_depth is marked non-differentiable
             if g_depth is not None:
@@ -478,7 +485,7 @@ class SynthesisFn(torch.autograd.Function):
                         u_strat=tape["u_strat"], u_imp=tape["u_imp"], decoder_grads=ctx.pg,
                         planes_absmax=tape.get("planes_absmax"), state=tape.get("ray_state"),
                         dec_out=tuple(p.grad for p in dec_prm) if dec_direct else None, rec_out=rec_out,
-                        **geom, **gen._render_args(tape["c"]))
+                        **geom, **gen._render_args(tape["c"], res))
         d_c = None
         g_nrm = None
         if g_normal is not None:
@@ -488,12 +495,12 @@ class SynthesisFn(torch.autograd.Function):
             d_c2w, d_intr, ray_grad = gen._timed("raymarch_bwd_camera", float(b), ops.raymarch_bwd_camera, g_feat.view(b, res * res, 32),
                                                  tape["planes"], rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
                                                  planes_absmax=tape.get("planes_absmax"), reduce=not nrm_c,
-                                                 **gen._render_args(tape["c"]))
+                                                 **gen._render_args(tape["c"], res))
             if nrm_c:
                 d_c2w, d_intr, _ = gen._timed("raymarch_normals_bwd_camera", float(b), ops.raymarch_normals_bwd_camera, g_nrm,
                                               tape["planes"], tape["ray_state"], ray_grad=ray_grad, u_strat=tape["u_strat"],
                                               u_imp=tape["u_imp"], planes_absmax=tape.get("planes_absmax"),
-                                              **gen._render_args(tape["c"]))
+                                              **gen._render_args(tape["c"], res))
             d_c = torch.cat((d_c2w, d_intr), 1).to(ctx.c_dtype)
         d_coords = None
         if g_qsigma is not None or g_qrgb is not None:
@@ -514,7 +521,7 @@ class SynthesisFn(torch.autograd.Function):
             gen._timed("raymarch_normals_bwd", float(b), ops.raymarch_normals_bwd, g_nrm, tape["planes"], tape["ray_state"],
                        u_strat=tape["u_strat"], u_imp=tape["u_imp"], planes_absmax=tape.get("planes_absmax"),
                        d_planes=rb[0] if ctx.pg else rb, decoder_grads=ctx.pg, dec_out=rb[1] if ctx.pg else None,
-                       **gen._render_args(tape["c"]))
+                       **gen._render_args(tape["c"], res))
         if ctx.pg:
             d_planes, dec = rb
             for prm, g in zip(dec_prm, dec):

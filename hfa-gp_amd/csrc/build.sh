@@ -40,6 +40,7 @@ units+=(raymarch_normals_camera)
 units+=(planes_query_normals)
 units+=(planes_query_normals_bwd)
 units+=(raymarch_rays)
+units+=(resample_aa)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

@@ -646,20 +646,21 @@ class TriPlaneGenerator(nn.Module):
         net = self.decoder.net
         return net["0"].weight, net["0"].bias, net["2"].weight, net["2"].bias
 
-    def _render_args(self, c: torch.Tensor):
+    def _render_args(self, c: torch.Tensor, res: Optional[int] = None):
+        """`res`: the ray resolution of the call (a backward pass hands in its forward's); None = the current one."""
         cfg = self.cfg
         hit = getattr(self, "_cam_cache", None)       # the backward pass of a step asks again with the forward's tensor
         if hit is None or hit[0] is not c or hit[1] != c._version:
             hit = self._cam_cache = (c, c._version, c[:, :16].contiguous(), c[:, 16:25].contiguous())
         return dict(zip(ops._DEC, self.decoder_params()), cam2world=hit[2], intrinsics=hit[3],
-                    res=cfg.neural_rendering_resolution, ray_start=cfg.ray_start, ray_end=cfg.ray_end,
+                    res=self.neural_rendering_resolution if res is None else res, ray_start=cfg.ray_start, ray_end=cfg.ray_end,
                     box_warp=cfg.box_warp, decoder_lr_mul=cfg.decoder_lr_mul,
                     plane_axes=ops._plane_axes_id(cfg.plane_axes), white_back=cfg.white_back,
                     decoder_precision=cfg.decoder_precision)
 
     def _uniforms(self, b: int, dev, u_strat, u_imp):
         cfg = self.cfg
-        r = cfg.neural_rendering_resolution ** 2
+        r = self.neural_rendering_resolution ** 2
         if u_strat is None:
             u_strat = torch.rand(b, r, cfg.depth_resolution, device=dev)
         if u_imp is None:
@@ -670,7 +671,7 @@ class TriPlaneGenerator(nn.Module):
         """state (ops.raymarch_state): filled with the per-sample results the backward pass of this step will need."""
         cfg = self.cfg
         b = planes.shape[0]
-        r = cfg.neural_rendering_resolution ** 2
+        r = self.neural_rendering_resolution ** 2
         u_strat, u_imp = self._uniforms(b, planes.device, u_strat, u_imp)
         # algorithmic bytes per frame (SURVEY.md section 8d): samples * 3 planes * 4 taps * 32 ch * 4 B
         # + outputs R*(32+1+1)*4 + uniforms R*(Sc+Sf)*4
@@ -684,7 +685,7 @@ class TriPlaneGenerator(nn.Module):
         state of the whole batch would exceed RAY_STATE_CAP_BYTES.  Every ray is computed as in the whole-batch launch (the
         decoder's bound on |planes| is the batch's, taken once), so the five results equal the unchunked ones bit for bit."""
         cfg = self.cfg
-        b, res = planes.shape[0], cfg.neural_rendering_resolution
+        b, res = planes.shape[0], self.neural_rendering_resolution
         planes_absmax = ops._decoder_bound(planes, cfg.decoder_precision, planes_absmax)
         u_imp = u_imp.view(b, res * res, -1)
         state = ops.raymarch_state(min(frames, b), res, cfg.depth_resolution, cfg.depth_resolution_importance, planes.device)
@@ -742,6 +743,22 @@ class TriPlaneGenerator(nn.Module):
             raise ValueError(f"expected ws [B,{cfg.num_ws},{cfg.w_dim}] and c [B,{cfg.c_dim}], got "
                              f"{tuple(ws.shape)} and {tuple(c.shape)}")
 
+    def _set_resolution(self, b: int, n: Optional[int], u_strat, u_imp) -> None:
+        """`synthesis(neural_rendering_resolution=n)`: validates and stores the ray resolution of this and later calls (None: the
+        stored one), and checks caller-given uniforms against it."""
+        cfg = self.cfg
+        r0 = cfg.neural_rendering_resolution
+        if n is None:
+            n = self.neural_rendering_resolution
+        elif isinstance(n, bool) or int(n) != n or not (r0 <= 4 * n and n <= 4 * r0):
+            raise ValueError(f"TriPlaneGenerator.synthesis: neural_rendering_resolution={n!r} must be an integer in "
+                             f"[{-(-r0 // 4)}, {4 * r0}] (a quarter to four times the configured {r0})")
+        for name, u, s in (("u_strat", u_strat, cfg.depth_resolution), ("u_imp", u_imp, cfg.depth_resolution_importance)):
+            if u is not None and u.numel() != b * n * n * s:
+                raise ValueError(f"TriPlaneGenerator.synthesis: {name} {tuple(u.shape)} is not sized for {n}^2 rays of {s} samples "
+                                 f"in {b} frames")
+        self.neural_rendering_resolution = int(n)
+
     def _check_normal_grad(self, ws, c, normal_camera_grad: bool = False) -> None:
         """The refusals of `synthesis(normal_grad=True)` under grad, before anything is launched."""
         cfg = self.cfg
@@ -749,7 +766,7 @@ class TriPlaneGenerator(nn.Module):
             raise NotImplementedError("TriPlaneGenerator.synthesis(normal_grad=True): the camera gradient of the normal term is opt-in "
                                       "(c.requires_grad): pass normal_camera_grad=True for it, detach the label, or use normals=True "
                                       "for a detached map")
-        frame_bytes = cfg.neural_rendering_resolution ** 2 * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
+        frame_bytes = self.neural_rendering_resolution ** 2 * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
         if ws.shape[0] * frame_bytes > RAY_STATE_CAP_BYTES:
             raise RuntimeError(f"TriPlaneGenerator.synthesis(normal_grad=True): the backward of 'image_normal' reads the ray marcher's "
                                f"per-sample state, {ws.shape[0] * frame_bytes} bytes for {ws.shape[0]} frames, above "
@@ -769,7 +786,7 @@ class TriPlaneGenerator(nn.Module):
     def _forward_body(self, ws, c, u_strat, u_imp, tape, geometry=False):
         cfg = self.cfg
         b = ws.shape[0]
-        res = cfg.neural_rendering_resolution
+        res, res_sr = self.neural_rendering_resolution, cfg.neural_rendering_resolution      # rays marched; the SR blocks' input
         bb_tape = [] if tape is not None else None
         sr_tape = [] if tape is not None else None
         planes = self.backbone_planes(ws, bb_tape)
@@ -798,10 +815,17 @@ class TriPlaneGenerator(nn.Module):
         depth = ops.depth_clamp_(depth, tmm)
         feat_img = feat.view(b, res, res, 32)                             # channels-last
         rgb_raw = feat_img[..., :3].permute(0, 3, 1, 2).contiguous()      # NCHW, 'image_raw'
-        img = self.superres(rgb_raw, feat_img, ws, sr_tape)
+        feat_sr, rgb_sr = feat_img, rgb_raw
+        if res != res_sr:
+            # SuperresolutionHybrid8XDC.forward brings rgb and x back to its input resolution (antialiased bilinear); per channel, so
+            # one pass over the feature image serves both
+            feat_sr = self._timed("resize_aa", float(b) * (res * res + res_sr * res_sr) * 128, ops.resize_aa, feat_img, (res_sr, res_sr))
+            rgb_sr = feat_sr[..., :3].permute(0, 3, 1, 2).contiguous()
+        img = self.superres(rgb_sr, feat_sr, ws, sr_tape)
         if tape is not None:
+            # (feat_img: the SR blocks' input, what their backward reads; res: the backward marches the forward's rays)
             tape.update(backbone=bb_tape, sr=sr_tape, planes=planes, c=c, u_strat=u_strat, u_imp=u_imp,
-                        feat_img=feat_img, batch=b, planes_absmax=pam, ray_state=ray_state)
+                        feat_img=feat_sr, res=res, batch=b, planes_absmax=pam, ray_state=ray_state)
             if geometry:      # the clamp range of the depth, for its adjoint (autograd.SynthesisFn.backward)
                 tape["depth_range"] = ops.depth_range(tmm)
         if geometry:
@@ -812,7 +836,8 @@ class TriPlaneGenerator(nn.Module):
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                   return_planes: bool = False, geometry: bool = False, query: Optional[torch.Tensor] = None,
                   normals: bool = False, normal_grad: bool = False, normal_camera_grad: bool = False,
-                  query_normals: bool = False, **_unused) -> Dict[str, torch.Tensor]:
+                  query_normals: bool = False, neural_rendering_resolution: Optional[int] = None,
+                  **_unused) -> Dict[str, torch.Tensor]:
         """Drop-in for EG3D's TriPlaneGenerator.synthesis.  Differentiable w.r.t. `ws` (the latent-basis fitting of
         HFA-GP), w.r.t. the generator parameters that require grad (after `tune_generator()`) and w.r.t. the camera label `c`
         when it requires grad (pose refinement; the importance depths are detached as in EG3D).
@@ -849,8 +874,17 @@ class TriPlaneGenerator(nn.Module):
         (ops.planes_query_normals_bwd, after the query's own backward) before the one backbone backward pass; a loss that does not
         touch the two keys launches nothing extra.  It composes with `geometry=True` and `normals=True`.  The two outputs have no
         gradient w.r.t. the points: under grad a `query` that requires grad raises NotImplementedError, and so does the combination
-        with `normal_grad=True` / `normal_camera_grad=True`."""
+        with `normal_grad=True` / `normal_camera_grad=True`.
+        `neural_rendering_resolution=N` (EG3D's keyword): march N x N rays instead of the configured r0 x r0.  The value is stored in
+        `self.neural_rendering_resolution`, as EG3D does, and holds for later calls; None (the default) reads that attribute.
+        'image_raw', 'image_depth', 'image_mask', 'image_normal' and the 'feature_image' of `return_planes` are N x N; 'image' keeps
+        its size: the feature image is resampled to r0 x r0 in front of the super-resolution blocks (ops.resize_aa: antialiased
+        bilinear, as SuperresolutionHybrid8XDC does for rgb and x), and its adjoint (ops.resize_aa_bwd) hands the blocks' gradient
+        back to the N x N rays, so every mode above composes.  N = 2 r0 supersamples (four rays per SR input pixel), N = r0 / 2 is
+        EG3D's cheap training regime.  N outside [r0 / 4, 4 r0], or caller-given `u_strat` / `u_imp` that are not sized for N x N
+        rays, raise ValueError before anything is launched; N = r0 launches exactly what a call without the keyword does."""
         self._check_inputs(ws, c, noise_mode)
+        self._set_resolution(ws.shape[0], neural_rendering_resolution, u_strat, u_imp)
         normal_grad = normal_grad or normal_camera_grad
         if query_normals:
             if query is None:
@@ -872,7 +906,7 @@ class TriPlaneGenerator(nn.Module):
             finally:
                 self._want_normals = self._want_normal_grad = self._want_normal_camera_grad = False
             if "image_normal" not in out:         # (a differentiable one is an output of the autograd function itself)
-                r = self.cfg.neural_rendering_resolution
+                r = self.neural_rendering_resolution
                 out["image_normal"] = self._last_normal if ws.shape[0] else torch.zeros(0, 3, r, r, device=ws.device)
                 if normal_grad and not ws.shape[0] and torch.is_grad_enabled():
                     out["image_normal"] = out["image_normal"] + 0.0 * ws.sum()      # keeps the autograd edge to ws
@@ -893,7 +927,7 @@ class TriPlaneGenerator(nn.Module):
                 return out
         if ws.shape[0] == 0:          # empty batch (ragged last batch of a frame shard): nothing to launch
             cfg, dev = self.cfg, ws.device
-            r = cfg.neural_rendering_resolution
+            r = self.neural_rendering_resolution
             out = {"image": torch.zeros(0, cfg.img_channels, cfg.img_resolution, cfg.img_resolution, device=dev),
                    "image_raw": torch.zeros(0, 3, r, r, device=dev), "image_depth": torch.zeros(0, 1, r, r, device=dev)}
             if geometry:

@@ -172,7 +172,8 @@ class _LatentBasis(nn.Module):
         return out.view(weights.shape[0], -1, self.dim) + delta.view(-1, self.dim)
 
     def get_image(self, latent: torch.Tensor, label: torch.Tensor, *, geometry: bool = False, query=None, normals: bool = False,
-                  normal_grad: bool = False, normal_camera_grad: bool = False, query_normals: bool = False, **renderer_uniforms):
+                  normal_grad: bool = False, normal_camera_grad: bool = False, query_normals: bool = False,
+                  neural_rendering_resolution: Optional[int] = None, **renderer_uniforms):
         """`geometry=True`: the whole synthesis dict ('image', 'image_raw', 'image_depth', 'image_mask'; depth and mask
         differentiable) instead of the image — for silhouette / depth terms of a fitting loss.
         `query=coords` [B or 1, M, 3]: the dict as well, with 'query_sigma' / 'query_rgb' at the points (`synthesis(query=)`:
@@ -184,10 +185,12 @@ class _LatentBasis(nn.Module):
         `normal_camera_grad=True`: as `normal_grad=True`, and the normal term also reaches a `label` that requires grad
         (`synthesis(normal_camera_grad=)`) — pose refinement under normal-map supervision.
         `query_normals=True` (with `query=`): the dict also has 'query_sigma_grad' / 'query_normal' at the points
-        (`synthesis(query_normals=)`: differentiable w.r.t. the latent and the tuned generator) — for surface regularisers."""
+        (`synthesis(query_normals=)`: differentiable w.r.t. the latent and the tuned generator) — for surface regularisers.
+        `neural_rendering_resolution=N`: march N x N rays (`synthesis(neural_rendering_resolution=)`: the image keeps its size; the
+        generator keeps N for later calls) — 2x the configured value for supersampled clips, half of it for cheap fitting steps."""
         flip_label_(label)                               # in place, on the caller's tensor
         return self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad, normal_camera_grad,
-                               query_normals)
+                               query_normals, neural_rendering_resolution)
 
     def get_shape(self, latent: torch.Tensor, resolution: int = 512, **kw) -> torch.Tensor:
         """Density volume [B, N, N, N] of a fitted latent (`generator.density_grid`): the geometry next to `get_image`.
@@ -200,7 +203,8 @@ class _LatentBasis(nn.Module):
         return self.generator.extract_mesh(latent, **kw)
 
     def _synthesis(self, latent, label, renderer_uniforms, geometry: bool = False, query=None, normals: bool = False,
-                   normal_grad: bool = False, normal_camera_grad: bool = False, query_normals: bool = False):
+                   normal_grad: bool = False, normal_camera_grad: bool = False, query_normals: bool = False,
+                   neural_rendering_resolution: Optional[int] = None):
         """`generator.synthesis(latent, c=label, noise_mode='const')['image']` (headnerf.py:112).  `renderer_uniforms`
         (keyword-only `u_strat` [B,R,Sc], `u_imp` [B*R,Sf]) is a TEST HOOK: EG3D's renderer draws its stratified-jitter and
         importance-sampling uniforms inside the call, which makes two renders of one frame differ; a parity
@@ -209,6 +213,8 @@ class _LatentBasis(nn.Module):
         if bad:
             raise TypeError(f"unexpected keyword arguments {sorted(bad)}")
         kw = {k: v for k, v in renderer_uniforms.items() if v is not None}
+        if neural_rendering_resolution is not None:
+            kw["neural_rendering_resolution"] = neural_rendering_resolution
         if query_normals:        # (only then: a call without it hands synthesis the keywords it always did)
             kw["query_normals"] = True
             if query is None:
@@ -259,7 +265,7 @@ class HeadNeRF_final(_LatentBasis):
         return self.encoder(image)          # (weights, pose) when out_pose
 
     def forward(self, image, label, person_2=False, *, geometry=False, query=None, normals=False, normal_grad=False,
-                normal_camera_grad=False, query_normals=False, **renderer_uniforms):
+                normal_camera_grad=False, query_normals=False, neural_rendering_resolution=None, **renderer_uniforms):
         flip_label_(label)
         if self.out_pose:
             weights, pose = self.encoder(image)
@@ -267,7 +273,7 @@ class HeadNeRF_final(_LatentBasis):
             weights, pose = self.encoder(image), None
         latent = self.get_latent(weights, person_2)
         img = self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad, normal_camera_grad,
-                              query_normals)
+                              query_normals, neural_rendering_resolution)
         return (img, pose) if self.out_pose else img
 
 
@@ -301,11 +307,11 @@ class _ParamDriven(_LatentBasis):
         return self.weights_3dmm(params)
 
     def forward(self, params, label, person_2=False, *, geometry=False, query=None, normals=False, normal_grad=False,
-                normal_camera_grad=False, query_normals=False, **renderer_uniforms):
+                normal_camera_grad=False, query_normals=False, neural_rendering_resolution=None, **renderer_uniforms):
         flip_label_(label)
         latent = self.get_latent(self.weights_3dmm(params), person_2)
         return self._synthesis(latent, label, renderer_uniforms, geometry, query, normals, normal_grad, normal_camera_grad,
-                               query_normals)
+                               query_normals, neural_rendering_resolution)
 
 
 class HeadNeRF_3DMM(_ParamDriven):

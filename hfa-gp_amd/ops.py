@@ -1181,6 +1181,122 @@ def _decoder_bound(planes: torch.Tensor, decoder_precision: str, planes_absmax: 
     return _chk(planes_absmax, "planes_absmax")
 
 
+# ----------------------------------------------------------------------------- antialiased resample (synthesis at any ray resolution)
+AA_KMAX = 9              # HFAGP_RESIZE_AA_KMAX: taps per output, and outputs per input, at ratios within [1/4, 4]
+_AA_TABLES = {}          # (n_in, n_out) -> (forward table, transposed table, dense float64 matrix), on the host
+_AA_DEVICE = {}          # (n_in, n_out, device) -> (forward table, transposed table) on the device
+
+
+def _aa_pack(start, count, weights) -> torch.Tensor:
+    """One axis table as the kernels read it: int32 [n, 2 + AA_KMAX], a row = start, count, then the fp32 weights' bits."""
+    n = len(start)
+    t = torch.zeros(n, 2 + AA_KMAX, dtype=torch.int32)
+    t[:, 0] = torch.tensor(start, dtype=torch.int32)
+    t[:, 1] = torch.tensor(count, dtype=torch.int32)
+    t[:, 2:] = weights.view(torch.int32)
+    return t
+
+
+def _aa_unpack(table: torch.Tensor):
+    """(start [n], count [n], weights [n, AA_KMAX] fp32) of a table of `_aa_tables`."""
+    return table[:, 0], table[:, 1], table[:, 2:].contiguous().view(torch.float32)
+
+
+def _aa_tables(n_in: int, n_out: int):
+    """One axis of torch's antialiased bilinear resize (`_upsample_bilinear2d_aa`, align_corners=False) n_in → n_out, built in
+    float64: with s = n_in / n_out, support = max(s, 1), inv = 1 / max(s, 1), output i reads the inputs
+    [max(0, int(c − support + 0.5)), min(n_in, int(c + support + 0.5))) around c = s (i + 0.5) with the weights
+    max(0, 1 − |(j − c + 0.5) inv|) divided by their sum.
+    Returns (forward, transposed, dense) as CPU tensors: `forward` [n_out, 2 + AA_KMAX] int32 — per output its first input, its
+    number of taps and the fp32 weights (`_aa_unpack`); `transposed` [n_in, 2 + AA_KMAX] — per input the (consecutive) outputs
+    that read it and the same fp32 weights, the adjoint in gather form; `dense` [n_out, n_in] float64, the unrounded matrix.
+    ValueError outside n_out / 4 <= n_in <= 4 n_out: within it no output has more than AA_KMAX taps and no input more than
+    AA_KMAX readers (asserted)."""
+    n_in, n_out = int(n_in), int(n_out)
+    hit = _AA_TABLES.get((n_in, n_out))
+    if hit is not None:
+        return hit
+    if n_in < 1 or n_out < 1 or 4 * n_in < n_out or n_in > 4 * n_out:
+        raise ValueError(f"resize_aa: {n_in} -> {n_out} is outside the supported ratios n_out / 4 <= n_in <= 4 n_out")
+    s = n_in / n_out
+    support, inv = max(s, 1.0), 1.0 / max(s, 1.0)
+    dense = torch.zeros(n_out, n_in, dtype=torch.float64)
+    lo_hi = []
+    for i in range(n_out):
+        c = s * (i + 0.5)
+        lo, hi = max(0, int(c - support + 0.5)), min(n_in, int(c + support + 0.5))
+        j = torch.arange(lo, hi, dtype=torch.float64)
+        w = (1.0 - ((j - c + 0.5) * inv).abs()).clamp_min(0.0)
+        dense[i, lo:hi] = w / w.sum()
+        lo_hi.append((lo, hi))
+    assert max(hi - lo for lo, hi in lo_hi) <= AA_KMAX, (n_in, n_out)
+    w32 = dense.float()
+    fw = torch.zeros(n_out, AA_KMAX)
+    for i, (lo, hi) in enumerate(lo_hi):
+        fw[i, :hi - lo] = w32[i, lo:hi]
+    forward = _aa_pack([lo for lo, _ in lo_hi], [hi - lo for lo, hi in lo_hi], fw)
+    # the windows move monotonically with i: the outputs that read input j are consecutive
+    first, count = [], []
+    tw = torch.zeros(n_in, AA_KMAX)
+    for j in range(n_in):
+        readers = [i for i, (lo, hi) in enumerate(lo_hi) if lo <= j < hi]
+        assert readers == list(range(readers[0], readers[0] + len(readers))) if readers else True, (n_in, n_out, j)
+        assert len(readers) <= AA_KMAX, (n_in, n_out, j)
+        first.append(readers[0] if readers else 0)
+        count.append(len(readers))
+        if readers:
+            tw[j, :len(readers)] = w32[readers[0]:readers[0] + len(readers), j]
+    hit = _AA_TABLES[(n_in, n_out)] = (forward, _aa_pack(first, count, tw), dense)
+    return hit
+
+
+def _aa_device_tables(n_in: int, n_out: int, device):
+    key = (int(n_in), int(n_out), device)
+    hit = _AA_DEVICE.get(key)
+    if hit is None:
+        forward, transposed, _ = _aa_tables(n_in, n_out)
+        hit = _AA_DEVICE[key] = (forward.to(device), transposed.to(device))
+    return hit
+
+
+def _resize_aa_args(who: str, src: torch.Tensor, in_hw, out_hw, adjoint: bool):
+    """The ResizeAaArgs of both directions and the destination tensor: `src` is x [B,Hi,Wi,C] (forward) or g_y [B,Ho,Wo,C]
+    (adjoint, read through the transposed tables).  Owns the checks of `src` and of the ratios (ValueError)."""
+    _chk(src, f"{who}: {'g_y' if adjoint else 'x'}")
+    (hi, wi), (ho, wo) = (int(v) for v in in_hw), (int(v) for v in out_hw)
+    if src.dim() != 4 or tuple(src.shape[1:3]) != ((ho, wo) if adjoint else (hi, wi)) or src.shape[3] % 4:
+        raise RuntimeError(f"{who}: expected a channels-last [B, {ho if adjoint else hi}, {wo if adjoint else wi}, C] tensor with "
+                           f"C a multiple of 4, got {tuple(src.shape)}")
+    b, c = src.shape[0], src.shape[3]
+    th, tw = (_aa_device_tables(n_in, n_out, src.device)[int(adjoint)] for n_in, n_out in ((hi, ho), (wi, wo)))
+    dst = torch.empty((b, hi, wi, c) if adjoint else (b, ho, wo, c), device=src.device, dtype=torch.float32)
+    a = L.ResizeAaArgs()
+    a.src, a.dst, a.table_h, a.table_w = _ptr(src), _ptr(dst), _ptr(th), _ptr(tw)
+    a.B, a.Hi, a.Wi, a.Ho, a.Wo, a.C, a.kmax = b, hi, wi, ho, wo, c, AA_KMAX
+    return a, dst
+
+
+def resize_aa(x: torch.Tensor, out_hw) -> torch.Tensor:
+    """x [B,Hi,Wi,C] channels-last, C % 4 == 0 → [B,Ho,Wo,C]: F.interpolate(mode='bilinear', align_corners=False, antialias=True)
+    per channel (EG3D's SuperresolutionHybrid8XDC resize of the feature image and the raw RGB), one launch; the per-axis tap
+    tables come from the host (`_aa_tables`, cached per size and device)."""
+    a, y = _resize_aa_args("resize_aa", x, x.shape[1:3], out_hw, False)
+    if y.numel():
+        L.check(L.lib().hfagp_resize_aa_fwd(C.byref(a), _stream()), "resize_aa_fwd")
+    return y
+
+
+def resize_aa_bwd(g_y: torch.Tensor, in_hw, g_nchw3: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of `resize_aa`: g_y [B,Ho,Wo,C] → g_x [B,Hi,Wi,C], a gather over the transposed tables — every element written once,
+    in a fixed order (two calls give the same bits).  `g_nchw3` [B,3,Hi,Wi] is added to channels 0..2 in the same pass: the gradient
+    of 'image_raw', which is those channels of the unresampled feature image."""
+    a, g_x = _resize_aa_args("resize_aa_bwd", g_y, in_hw, g_y.shape[1:3], True)
+    a.add_nchw3 = _ptr(_chk_operand("resize_aa_bwd", "g_nchw3", g_nchw3, (g_x.shape[0], 3) + tuple(g_x.shape[1:3]), g_y))
+    if g_x.numel():
+        L.check(L.lib().hfagp_resize_aa_bwd(C.byref(a), _stream()), "resize_aa_bwd")
+    return g_x
+
+
 # ----------------------------------------------------------------------------- standalone ops (NCHW)
 def _upfirdn2d_raw(x, f, up, down, padding, gain):
     n, c, h, w = x.shape

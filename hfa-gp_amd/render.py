@@ -33,9 +33,12 @@ def layout_grid(img: torch.Tensor, grid_w: Optional[int] = None, grid_h: int = 1
 
 @torch.no_grad()
 def render_frames(gen, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], person_2: bool = False,
-                  to_host: bool = True) -> Iterator[torch.Tensor]:
+                  to_host: bool = True, neural_rendering_resolution: Optional[int] = None) -> Iterator[torch.Tensor]:
     """`gen` is a HeadNeRF_* module; `batches` yields (driver_input [B,...], label [B,25]) on gen's device.
-    Yields uint8 frames [B,3,H,W].  The label flip side effect of `get_image` is preserved."""
+    Yields uint8 frames [B,3,H,W].  The label flip side effect of `get_image` is preserved.
+    `neural_rendering_resolution=N`: march N x N rays per frame (`get_image(neural_rendering_resolution=)`; twice the configured
+    value supersamples a clip: four rays per super-resolution input pixel).  The generator keeps N afterwards."""
+    res_kw = {} if neural_rendering_resolution is None else {"neural_rendering_resolution": neural_rendering_resolution}
     gen.eval()
     copy_stream = torch.cuda.Stream() if to_host and torch.cuda.is_available() else None
     pending = None
@@ -43,7 +46,7 @@ def render_frames(gen, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], per
         weights = gen.get_weights(driver_in)
         if isinstance(weights, tuple):
             weights = weights[0]
-        frames = to_uint8(gen.get_image(gen.get_latent(weights, person_2), label))
+        frames = to_uint8(gen.get_image(gen.get_latent(weights, person_2), label, **res_kw))
         if copy_stream is None:
             yield frames
             continue

@@ -35,6 +35,8 @@
  *   hfagp_raymarch_normals_bwd <- (none either: what autograd would do with a normal-map loss on such a render)
  *   hfagp_raymarch_normals_bwd_camera <- (none either: the same loss's gradient w.r.t. the camera label)
  *   hfagp_depth_clamp       <- MipRayMarcher2's torch.clamp(depth, min sample depth, max sample depth) over the batch, one launch (ABI 10)
+ *   hfagp_resize_aa_fwd / _bwd <- SuperresolutionHybrid8XDC.forward's antialiased bilinear F.interpolate of rgb and x to its input
+ *                              resolution (synthesis(neural_rendering_resolution=N), N != the configured one) and its autograd
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
  *   hfagp_pool_mse_fwd/_bwd <- face_pool (AdaptiveAvgPool2d) + MSELoss of gen_update (code/trainer_rgb.py:63,84-85) and its backward
@@ -841,6 +843,38 @@ size_t hfagp_raymarch_rays_bwd_rows_bytes(const HfagpRayListArgs* a);
  * its reduction; the sample depths carry no gradient).  One writer per ray, no atomics, no reduction: two calls give the same
  * bits.  HFAGP_EBADARG also for a->bwd.rec, d_origins or d_directions NULL.                                                  */
 int hfagp_raymarch_rays_bwd_rays(const HfagpRayListBwdArgs* a, float* d_origins, float* d_directions, void* stream);
+
+/* ------------------------------------------------------------------ antialiased resample (additive to ABI 15)
+ * SuperresolutionHybrid8XDC's F.interpolate(mode='bilinear', align_corners=False, antialias=True) of the feature image and the
+ * raw RGB when the rays were marched at another resolution than the super-resolution input (neural_rendering_resolution), on
+ * the channels-last feature image, and its adjoint.  The resize is separable; per axis n_in -> n_out, with s = n_in / n_out,
+ * support = max(s, 1) and inv = 1 / max(s, 1), output i reads the inputs
+ *     j in [lo, hi),  lo = max(0, (int)(c - support + 0.5)),  hi = min(n_in, (int)(c + support + 0.5)),  c = s (i + 0.5)
+ * with the weights  w_j = max(0, 1 - |(j - c + 0.5) inv|)  divided by their sum (torch's _upsample_bilinear2d_aa).
+ * The kernels compute NO weights: the caller builds one table per axis (in double, stored as fp32) and passes them in.
+ * A table has one row of 2 + kmax 32-bit words per DESTINATION index of its axis: int32 start, int32 count, then kmax floats —
+ * destination d sums  weight[k] * source[start + k]  over k < count.  Forward: Ho rows (table_h) and Wo rows (table_w) as above.
+ * Adjoint: the TRANSPOSED tables, Hi and Wi rows — per input index the consecutive outputs that read it and the same
+ * (normalised) weights: a gather, every element of dst written exactly once, no atomics, no memset, a fixed summation order
+ * (two calls give the same bits).  Supported ratios per axis: n_out / 4 <= n_in <= 4 n_out (at most HFAGP_RESIZE_AA_KMAX taps
+ * per output and readers per input).  Rows must satisfy 0 <= start, start + count <= source extent (a count is cut to what
+ * fits: nothing is read out of bounds).
+ * HFAGP_EBADARG, nothing launched: a, src, dst or a table NULL.  HFAGP_EUNSUPPORTED: C not a multiple of 4, an empty extent
+ * (B, Hi, Wi, Ho, Wo or C <= 0), a ratio outside the range, kmax < 1 or > HFAGP_RESIZE_AA_KMAX, 2^31 or more float4 outputs.    */
+#define HFAGP_RESIZE_AA_KMAX 9
+typedef struct {
+    const float* src;          /* forward: x [B][Hi][Wi][C];  adjoint: g_y [B][Ho][Wo][C] */
+    float* dst;                /* forward: y [B][Ho][Wo][C];  adjoint: g_x [B][Hi][Wi][C] (written, not accumulated) */
+    const float* add_nchw3;    /* adjoint only, may be NULL: [B][3][Hi][Wi], added to channels 0..2 of g_x in the same pass (the
+                                  gradient of image_raw = those channels of the unresampled feature image); forward: ignored */
+    const int32_t* table_h;    /* rows of the vertical axis:   forward [Ho][2 + kmax], adjoint [Hi][2 + kmax] */
+    const int32_t* table_w;    /* rows of the horizontal axis: forward [Wo][2 + kmax], adjoint [Wi][2 + kmax] */
+    int32_t B, Hi, Wi, Ho, Wo, C;
+    int32_t kmax;              /* weights per table row */
+} HfagpResizeAaArgs;
+
+int hfagp_resize_aa_fwd(const HfagpResizeAaArgs* a, void* stream);
+int hfagp_resize_aa_bwd(const HfagpResizeAaArgs* a, void* stream);
 
 /* ------------------------------------------------------------------ gradients w.r.t. the generator weights
  * (needed once HFA-GP calls tune_generator(), trainer_rgb.py:69-71)                                       */
