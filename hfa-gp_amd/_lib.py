@@ -188,6 +188,10 @@ class RayListBwdArgs(C.Structure):
     _fields_ = [("bwd", RaymarchBwdArgs), ("ray_origins", C.c_void_p), ("ray_directions", C.c_void_p), ("R", C.c_int32)]
 
 
+class RayLimits(C.Structure):
+    _fields_ = [("t_near", C.c_void_p), ("t_far", C.c_void_p)]
+
+
 class ResizeAaArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("src", "dst", "add_nchw3", "table_h", "table_w")] + \
         [(n, C.c_int32) for n in ("B", "Hi", "Wi", "Ho", "Wo", "C", "kmax")]
@@ -247,6 +251,12 @@ SYMBOLS = {
     "hfagp_raymarch_rays_bwd": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RaymarchGeomGrads), C.c_void_p]),
     "hfagp_raymarch_rays_bwd_rows_bytes": (C.c_size_t, [C.POINTER(RayListArgs)]),
     "hfagp_raymarch_rays_bwd_rays": (C.c_int, [C.POINTER(RayListBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hfagp_ray_limits_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "hfagp_raymarch_rays_limits_fwd": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits), C.c_void_p]),
+    "hfagp_raymarch_rays_limits_bwd": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RayLimits), C.POINTER(RaymarchGeomGrads),
+                                                 C.c_void_p]),
+    "hfagp_raymarch_rays_limits_bwd_rays": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RayLimits), C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]),
     "hfagp_resize_aa_fwd": (C.c_int, [C.POINTER(ResizeAaArgs), C.c_void_p]),
     "hfagp_resize_aa_bwd": (C.c_int, [C.POINTER(ResizeAaArgs), C.c_void_p]),
     "hfagp_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

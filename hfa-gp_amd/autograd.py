@@ -708,9 +708,13 @@ class RenderRaysFn(torch.autograd.Function):
     """`TriPlaneGenerator.render_rays` under grad: inputs ws, ray_origins, ray_directions, u_strat, u_imp, gen, *parameters; outputs
     feature [B,R,32], depth [B,R] (clamped to the call's global sample range), mask [B,R].  A backbone forward with a tape, then one
     list launch (ops.raymarch_rays); backward = ops.raymarch_rays_bwd into d_planes (with the decoder gradients when parameters
-    require grad), ops.raymarch_rays_bwd_rays only when the rays require grad, then the backbone backward `synthesis` runs."""
+    require grad), ops.raymarch_rays_bwd_rays only when the rays require grad, then the backbone backward `synthesis` runs.
+    ``limits``: None, or the per-ray depth limits (t_near, t_far) [B,R] — detached tensors, no autograd edge: the three launches
+    then carry them, d origins / d directions are the derivative with the limits held fixed (EG3D's autograd would also move the
+    sample positions through a box intersection: left out on purpose, as the importance depths are), an empty ray gets exactly
+    zero gradient and the g_depth it receives is dropped."""
     @staticmethod
-    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, *params):
+    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params):
         from .generator import RAY_STATE_CAP_BYTES
         ws_c = ws.detach().float().contiguous()
         o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
@@ -722,10 +726,16 @@ class RenderRaysFn(torch.autograd.Function):
             sc, sf = u_strat.shape[-1], u_imp.shape[-1]
             # (the per-sample results for the compositing adjoint, as a differentiated `synthesis` keeps them; skipped above the cap)
             state = ops.raymarch_rays_state(b, r, sc, sf, planes.device) if b * r * (sc + sf) * 140 <= RAY_STATE_CAP_BYTES else None
+            lim = {} if limits is None else dict(t_near=limits[0], t_far=limits[1])
             feat, depth, wsum, tmm = gen._timed("raymarch_rays", float(b), ops.raymarch_rays, planes, o, d, u_strat, u_imp,
-                                                planes_absmax=pam, state=state, **gen._rays_kwargs())
-            depth_range = ops.depth_range(tmm)
-            depth = ops.depth_clamp_(depth, tmm)
+                                                planes_absmax=pam, state=state, **lim, **gen._rays_kwargs())
+            if limits is None:
+                depth_range = ops.depth_range(tmm)
+                depth = ops.depth_clamp_(depth, tmm)
+            else:
+                depth_range = ops.depth_range(tmm, empty_rays=True)
+                depth = ops.depth_clamp_(depth, tmm, empty_rays=True)
+        ctx.lim = lim
         ctx.gen, ctx.tape, ctx.ws_c, ctx.planes, ctx.pam, ctx.state = gen, tape, ws_c, planes, pam, state
         ctx.rays, ctx.uniforms, ctx.depth_range = (o, d), (u_strat, u_imp), depth_range
         ctx.params = params
@@ -741,7 +751,7 @@ class RenderRaysFn(torch.autograd.Function):
         if ctx.tape is None:
             raise RuntimeError("TriPlaneGenerator.render_rays: backward called a second time — the saved activations are released "
                                "by the first backward pass (retain_graph is not supported)")
-        none = (None,) * (6 + len(ctx.params))
+        none = (None,) * (7 + len(ctx.params))
         if g_feat is None and g_depth is None and g_wsum is None:
             return none
         planes = ctx.planes
@@ -759,11 +769,12 @@ class RenderRaysFn(torch.autograd.Function):
         need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         rec_out = [] if need_rays else None
         rb = gen._timed("raymarch_rays_bwd", float(b), ops.raymarch_rays_bwd, g_feat, planes, o, d, u_strat, u_imp,
-                        decoder_grads=ctx.pg, planes_absmax=ctx.pam, state=ctx.state, rec_out=rec_out, **geom, **gen._rays_kwargs())
+                        decoder_grads=ctx.pg, planes_absmax=ctx.pam, state=ctx.state, rec_out=rec_out, **geom, **ctx.lim,
+                        **gen._rays_kwargs())
         d_o = d_d = None
         if need_rays:        # the per-ray record of the camera gradient is itself the answer; autograd carries it on to the camera model
             d_o, d_d = gen._timed("raymarch_rays_bwd_rays", float(b), ops.raymarch_rays_bwd_rays, g_feat, planes, rec_out[0], o, d,
-                                  u_strat, u_imp, planes_absmax=ctx.pam, **gen._rays_kwargs())
+                                  u_strat, u_imp, planes_absmax=ctx.pam, **ctx.lim, **gen._rays_kwargs())
             d_o = d_o.to(ctx.ray_dtypes[0]) if ctx.needs_input_grad[1] else None
             d_d = d_d.to(ctx.ray_dtypes[1]) if ctx.needs_input_grad[2] else None
         if ctx.pg:
@@ -775,4 +786,4 @@ class RenderRaysFn(torch.autograd.Function):
         _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
         ctx.tape = ctx.planes = ctx.state = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return (d_ws, d_o, d_d, None, None, None) + pgrads
+        return (d_ws, d_o, d_d, None, None, None, None) + pgrads

@@ -111,3 +111,43 @@ def ray_grid(c: torch.Tensor, res: int, window=None) -> Tuple[torch.Tensor, torc
     dirs = torch.nn.functional.normalize(world - cam[:, None, :], dim=2)
     origins = cam[:, None, :].repeat(1, dirs.shape[1], 1)
     return origins, dirs.contiguous()          # (both contiguous: ops.raymarch_rays takes them as they are)
+
+
+def ray_grid_ortho(cam2world: torch.Tensor, res: int, extent: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A parallel-projection ray grid: cam2world [B,4,4] (or [B,16]) → (origins, directions), each [B, res*res, 3].  Origins are the
+    res x res pixel centres of a square of side ``extent`` (world units) in the camera's z = 0 plane, centred on the camera
+    position, in `ray_grid`'s row order (x along a row, y down the rows, in the camera's own axes); every direction is the camera's
+    +z axis as cam2world gives it (unit length for a rigid pose).  With `render_rays(..., ray_limits="box")` the camera may stand at
+    any distance.  Differentiable w.r.t. cam2world."""
+    n = cam2world.shape[0]
+    c2w = cam2world.reshape(n, 4, 4)
+    ar = (torch.arange(res, dtype=c2w.dtype, device=c2w.device) * (1.0 / res) + (0.5 / res) - 0.5) * float(extent)
+    yl, xl = torch.meshgrid(ar, ar, indexing="ij")                 # rows = y, columns = x: pixel (i, j) is ray i * res + j
+    pts = torch.stack((xl.reshape(-1), yl.reshape(-1)), dim=-1)    # [R, 2] in the camera's z = 0 plane
+    origins = c2w[:, None, :3, 3] + pts[None, :, 0:1] * c2w[:, None, :3, 0] + pts[None, :, 1:2] * c2w[:, None, :3, 1]
+    dirs = c2w[:, None, :3, 2].expand(-1, res * res, -1)
+    return origins.contiguous(), dirs.contiguous()
+
+
+def ray_limits_box(origins: torch.Tensor, directions: torch.Tensor, box_side: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(t_near, t_far), each [..., ] for rays [..., 3]: the slab intersection with the cube [−box_side/2, box_side/2]³ in plain
+    torch — the formula of `ops.ray_limits_box` (hfagp_ray_limits_box), for which this is the reference, and usable on the CPU.
+    Per axis inv = 1 / d (±inf for a zero component), t0 = (−h − o)·inv, t1 = (h − o)·inv;  t_near = max over the axes of
+    min(t0, t1), clamped below at 0 — NOT EG3D's value for an origin inside the box (math_utils.get_ray_limits_box), on purpose: the
+    ray starts at its origin —;  t_far = min over the axes of max(t0, t1).  A ray misses iff t_far <= t_near; 0 · inf (origin
+    exactly on a slab of an axis the ray is parallel to) is NaN and makes both limits NaN.  Not differentiable (computed under
+    no_grad): the limits carry no gradient."""
+    with torch.no_grad():
+        h = 0.5 * float(box_side)
+        inv = 1.0 / directions
+        t0, t1 = (-h - origins) * inv, (h - origins) * inv
+        near = torch.minimum(t0, t1).amax(-1).clamp(min=0.0)       # (minimum / maximum / amax / amin propagate NaN)
+        far = torch.maximum(t0, t1).amin(-1)
+        bad = torch.isnan(near) | torch.isnan(far)
+        nan = torch.full_like(near, float("nan"))
+        return torch.where(bad, nan, near), torch.where(bad, nan, far)
+
+
+def ray_limits_valid(t_near: torch.Tensor, t_far: torch.Tensor) -> torch.Tensor:
+    """The rays the ray marcher marches: both limits finite and t_far > t_near (bool, the shape of the limits)."""
+    return torch.isfinite(t_near) & torch.isfinite(t_far) & (t_far > t_near)

@@ -41,6 +41,7 @@ units+=(planes_query_normals)
 units+=(planes_query_normals_bwd)
 units+=(raymarch_rays)
 units+=(resample_aa)
+units+=(ray_limits)
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()

@@ -54,6 +54,8 @@ struct WaveLds {
 // bit-identity tests (developer switch HFAGP_DEV_RAY_TAPS_LEGACY=1, launch_raymarch).
 // LIST: the rays are the caller's list (RayParams::ray_o / ray_d, R per frame) instead of the pinhole grid of the frame's label;
 // the one difference is the fetch (raymarch_common.h ray_fetch), so the body is shared and the two kernels below instantiate it.
+// A list may carry per-ray depth limits (RayParams::t_near / t_far, hfagp.h HfagpRayLimits; null otherwise): they replace the
+// config's interval in the stratified depths, and a ray without a valid interval is skipped — both under `if constexpr (LIST)`.
 template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE, bool LEGACY_TAPS, bool LIST>
 __device__ __forceinline__ void raymarch_body(const RayParams& p) {
     static_assert(!FROM_STATE || GRADS, "the saved state is consumed by the backward pass");
@@ -93,14 +95,47 @@ __device__ __forceinline__ void raymarch_body(const RayParams& p) {
     const int seq0 = __builtin_amdgcn_readfirstlane((int)q0);
     int b_l = 0, ray_l = 0;
     float o_l[3] = {0.f, 0.f, 0.f}, d_l[3] = {0.f, 0.f, 0.f};
+    float near_l = 0.f, far_l = 0.f;          // LIST with limits: the ray's [t_near, t_far] (every variant reads them: empty rays)
     {
         const long long sl = (long long)seq0 + (long long)lane * sch.stride;
-        if (sl < sch.end) ray_fetch<LIST, !FROM_STATE>(p, (int)sl, R, b_l, ray_l, o_l, d_l);      // ray_l: index into the [B][R] tensors
+        if (sl < sch.end) {
+            ray_fetch<LIST, !FROM_STATE>(p, (int)sl, R, b_l, ray_l, o_l, d_l);      // ray_l: index into the [B][R] tensors
+            if constexpr (LIST) {
+                if (p.t_near) { near_l = p.t_near[ray_l]; far_l = p.t_far[ray_l]; }
+            }
+        }
     }
     const int nbatch = __builtin_amdgcn_readfirstlane(min(64, ((int)sch.end - seq0 + sch.stride - 1) / sch.stride));
     #pragma unroll 1
     for (int k = 0; k < nbatch; ++k) {
         const int b = __builtin_amdgcn_readlane(b_l, k), ray = __builtin_amdgcn_readlane(ray_l, k);    // wave-uniform -> scalar registers
+        float t_near = 0.f, t_far = 0.f;
+        if constexpr (LIST) {
+            if (p.t_near) {                         // (wave-uniform: the limit-less list call never enters)
+                t_near = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(near_l), k));
+                t_far = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(far_l), k));
+                // An EMPTY ray — a limit that is not finite, or far <= near (the comparisons are false for NaN) — is not marched: no
+                // gather, no decoder, no state.  Forward: the background, no opacity, depth +inf, and (+inf, -inf) so that the ray
+                // does not enter the call's global depth range.  Pass 1 of the backward: S zero records, with which pass 2 and the
+                // rays' pass contribute exactly zero (omega = d sigma = 0 at the ray's origin, handled as any sample is).
+                if (!(fabsf(t_near) < INFINITY && fabsf(t_far) < INFINITY && t_far > t_near)) {
+                    if constexpr (GRADS) {
+                        float* rec = p.rec + (size_t)ray * S * 4;
+                        if (lane < S) *reinterpret_cast<float4*>(rec + lane * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                        if (lane + 64 < S) *reinterpret_cast<float4*>(rec + (lane + 64) * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    } else {
+                        if (lane < 32) a.feat[(size_t)ray * 32 + lane] = a.white_back ? 1.f : -1.f;
+                        if (lane == 0) {
+                            a.depth[ray] = INFINITY;
+                            a.wsum[ray] = 0.f;
+                            a.tminmax[2 * (size_t)ray] = INFINITY;
+                            a.tminmax[2 * (size_t)ray + 1] = -INFINITY;
+                        }
+                    }
+                    continue;
+                }
+            }
+        }
         if constexpr (FROM_STATE) {
             const float* st = a.state + (size_t)ray * kStateFloats;
             // 16-byte loads, ALL of the ray's colours in flight at once (12 per lane at 48 + 48 samples): with 4-byte loads, four in
@@ -131,12 +166,24 @@ __device__ __forceinline__ void raymarch_body(const RayParams& p) {
             }
 
             // ---- stratified depths: torch.linspace(start, end, SC)[s] + u * delta
+            // With per-ray limits (LIST): EG3D's math_utils.linspace + sample_stratified for tensor limits, every operation rounded
+            // on its own:  t_s = near + (s / (SC-1)) * span + u_s * (span / (SC-1)),  span = far - near.
             if (lane < SC) {
-                const float fs = (float)a.ray_start, fe = (float)a.ray_end;
-                const float lin = lane < SC / 2 ? __fadd_rn(fs, __fmul_rn(p.lin_step, (float)lane))
-                                                : __fsub_rn(fe, __fmul_rn(p.lin_step, (float)(SC - 1 - lane)));
+                float lin, dl;
+                bool limits = false;
+                if constexpr (LIST) limits = p.t_near != nullptr;
+                if (limits) {
+                    const float span = __fsub_rn(t_far, t_near);
+                    lin = __fadd_rn(t_near, __fmul_rn(__fdiv_rn((float)lane, (float)(SC - 1)), span));
+                    dl = __fdiv_rn(span, (float)(SC - 1));
+                } else {
+                    const float fs = (float)a.ray_start, fe = (float)a.ray_end;
+                    lin = lane < SC / 2 ? __fadd_rn(fs, __fmul_rn(p.lin_step, (float)lane))
+                                        : __fsub_rn(fe, __fmul_rn(p.lin_step, (float)(SC - 1 - lane)));
+                    dl = p.delta;
+                }
                 const float u = a.u_strat[(size_t)ray * SC + lane];
-                lds.t[lane] = __fadd_rn(lin, __fmul_rn(u, p.delta));
+                lds.t[lane] = __fadd_rn(lin, __fmul_rn(u, dl));
             }
             WAVE_SYNC();
 

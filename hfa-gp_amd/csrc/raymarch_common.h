@@ -24,19 +24,25 @@ struct RayParams {
     // normalised: a sample is o + t d).  Null for the pinhole grid, whose kernels never read these three.
     const float* ray_o, *ray_d;
     int R;               // rays per frame: res * res for the grid
+    // per-ray depth limits of a list (hfagp.h HfagpRayLimits; the *_rays_limits_* entry points): [B][R] each.  Null for every other
+    // entry point; read by the list instantiations of raymarch_body alone (raymarch.hip).
+    const float* t_near, *t_far;
 };
 
 // rays = null: the pinhole grid of a->cam2world / a->intrinsics / a->res.  Else the ray list {origins, directions} of R rays per
 // frame, and those three members of *a are ignored (they may be NULL / 0).
 struct RayList { const float* o; const float* d; int R; };
-inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char* who, const RayList* rays = nullptr) {
+// limits: the list carries per-ray depth limits, so the config's [ray_start, ray_end] is not read and not checked (the caller sets
+// p.t_near / p.t_far afterwards).
+inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char* who, const RayList* rays = nullptr,
+                           bool limits = false) {
     HFAGP_REQUIRE(a->planes && (rays || (a->cam2world && a->intrinsics)) && a->u_strat && a->u_imp && a->dec_w0 && a->dec_b0 &&
                       a->dec_w1 && a->dec_b1,
                   HFAGP_EBADARG, "%s: null pointer", who);
     HFAGP_REQUIRE(!rays || (rays->o && rays->d), HFAGP_EBADARG, "%s: null pointer (ray_origins / ray_directions)", who);
     HFAGP_REQUIRE(!rays || rays->R > 0, HFAGP_EBADARG, "%s: R = %d rays per frame", who, rays ? rays->R : 0);
     HFAGP_REQUIRE(a->B > 0 && a->H > 1 && a->W > 1 && (rays || a->res > 0), HFAGP_EBADARG, "%s: bad dims", who);
-    HFAGP_REQUIRE(a->box_warp > 0.f && a->ray_end > a->ray_start, HFAGP_EBADARG, "%s: bad ray range", who);
+    HFAGP_REQUIRE(a->box_warp > 0.f && (limits || a->ray_end > a->ray_start), HFAGP_EBADARG, "%s: bad ray range", who);
     HFAGP_REQUIRE(a->Sc == a->Sf && (a->Sc == 16 || a->Sc == 32 || a->Sc == 48), HFAGP_EUNSUPPORTED,
                   "%s: unsupported sample counts Sc=%d Sf=%d (supported: 16+16, 32+32, 48+48)", who, a->Sc, a->Sf);
     p.a = *a;
@@ -54,6 +60,7 @@ inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char*
     p.g_feat = nullptr;
     p.g_depth = p.g_wsum = p.depth_range = nullptr;
     p.rec = nullptr;
+    p.t_near = p.t_far = nullptr;
     return HFAGP_OK;
 }
 

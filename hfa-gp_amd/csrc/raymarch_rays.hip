@@ -48,3 +48,53 @@ extern "C" int hfagp_raymarch_rays_bwd_rays(const HfagpRayListBwdArgs* a, float*
     p.rec = a->bwd.rec;
     return launch_ray_list_grads(p, d_origins, d_directions, (hipStream_t)stream);
 }
+
+// ---- the same three with per-ray depth limits (hfagp.h HfagpRayLimits): the limits reach the list instantiations of raymarch_body
+// (the forward and pass 1 of the backward) through RayParams::t_near / t_far; pass 2 and the rays' pass read the depths from the
+// records and need none.  base.ray_start / ray_end are neither read nor checked.
+extern "C" int hfagp_raymarch_rays_limits_fwd(const HfagpRayListArgs* a, const HfagpRayLimits* lim, void* stream) {
+    HFAGP_REQUIRE(lim && lim->t_near && lim->t_far, HFAGP_EBADARG, "raymarch_rays_limits_fwd: null pointer (limits)");
+    HFAGP_REQUIRE(a, HFAGP_EBADARG, "raymarch_rays_limits_fwd: null pointer");
+    const HfagpRaymarchArgs* f = &a->base;
+    HFAGP_REQUIRE(f->feat && f->depth && f->wsum && f->tminmax, HFAGP_EBADARG, "raymarch_rays_limits_fwd: null pointer");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(f, p, "raymarch_rays_limits_fwd", &rays, true);
+    if (rc != HFAGP_OK) return rc;
+    p.t_near = lim->t_near;
+    p.t_far = lim->t_far;
+    return launch_raymarch(p, false, (hipStream_t)stream);
+}
+
+extern "C" int hfagp_raymarch_rays_limits_bwd(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim,
+                                              const HfagpRaymarchGeomGrads* geom, void* stream) {
+    HFAGP_REQUIRE(lim && lim->t_near && lim->t_far, HFAGP_EBADARG, "raymarch_rays_limits_bwd: null pointer (limits)");
+    HFAGP_REQUIRE(a && a->bwd.d_planes && a->bwd.rec, HFAGP_EBADARG, "raymarch_rays_limits_bwd: null pointer");
+    const float* g_depth = geom ? geom->g_depth : nullptr;
+    const float* g_wsum = geom ? geom->g_wsum : nullptr;
+    HFAGP_REQUIRE(a->bwd.g_feat || g_depth || g_wsum, HFAGP_EBADARG,
+                  "raymarch_rays_limits_bwd: no upstream gradient (g_feat, g_depth and g_wsum are all null)");
+    HFAGP_REQUIRE(!g_depth || geom->depth_range, HFAGP_EBADARG, "raymarch_rays_limits_bwd: g_depth needs depth_range");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->bwd.fwd, p, "raymarch_rays_limits_bwd", &rays, true);
+    if (rc != HFAGP_OK) return rc;
+    p.t_near = lim->t_near;
+    p.t_far = lim->t_far;
+    return raymarch_bwd_run(&a->bwd, p, geom, (hipStream_t)stream);
+}
+
+extern "C" int hfagp_raymarch_rays_limits_bwd_rays(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim, float* d_origins,
+                                                   float* d_directions, void* stream) {
+    HFAGP_REQUIRE(lim && lim->t_near && lim->t_far, HFAGP_EBADARG, "raymarch_rays_limits_bwd_rays: null pointer (limits)");
+    HFAGP_REQUIRE(a && a->bwd.rec && d_origins && d_directions, HFAGP_EBADARG, "raymarch_rays_limits_bwd_rays: null pointer");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->bwd.fwd, p, "raymarch_rays_limits_bwd_rays", &rays, true);
+    if (rc != HFAGP_OK) return rc;
+    p.g_feat = a->bwd.g_feat;
+    p.rec = a->bwd.rec;
+    p.t_near = lim->t_near;          // (not read: the depths of the records are the limits' already)
+    p.t_far = lim->t_far;
+    return launch_ray_list_grads(p, d_origins, d_directions, (hipStream_t)stream);
+}

@@ -1127,7 +1127,7 @@ class TriPlaneGenerator(nn.Module):
 
     def render_rays(self, ws: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
                     u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
-                    noise_mode: str = "const") -> Dict[str, torch.Tensor]:
+                    noise_mode: str = "const", t_near=None, t_far=None, ray_limits: Optional[str] = None) -> Dict[str, torch.Tensor]:
         """The renderer of `synthesis` on caller-given rays: ray_origins / ray_directions [B,R,3] in world units, R arbitrary — a
         crop or zoomed window (`cam_utils.ray_grid(c, res, window=)`), several cameras of one identity as one longer list in that
         frame (`torch.cat` along dim 1), random ray batches, or any camera model written in torch.  Directions are taken as given,
@@ -1137,9 +1137,25 @@ class TriPlaneGenerator(nn.Module):
         Under grad the four are differentiable w.r.t. `ws`, the generator parameters that require grad and the rays (so a label
         `c` gets its gradient through `ray_grid` from torch autograd), at the price of a backbone backward pass of its own; inside a
         trainer step scope it raises, as `sample_mixed(differentiable=True)` does.  `u_strat` [B,R,Sc] / `u_imp` [B·R,Sf]: the
-        uniforms of the two sampling passes (drawn here when None).  R = 0 or B = 0: empty tensors, nothing is launched."""
+        uniforms of the two sampling passes (drawn here when None).  R = 0 or B = 0: empty tensors, nothing is launched.
+        Per-ray depth limits — a camera at any distance, directions of any length, visibility rays, depth-guided sampling:
+        `t_near` / `t_far` (tensors [B,R] or Python floats, both or neither) sample ray i on [t_near_i, t_far_i] instead of the
+        config's interval; `ray_limits="box"` takes them from the rays' intersection with the tri-plane cube of side cfg.box_warp
+        (`ops.ray_limits_box`; EG3D's ray_start = ray_end = 'auto', but t_near is clamped at 0: an origin inside the cube starts
+        at the origin).  The dict then also has 'valid' [B,R] bool: both limits finite and t_far > t_near.  Any other ray is EMPTY
+        and is not marched: 'feature' is the background (−1, or +1 with white_back), 'mask' 0 and 'depth' the upper end of the
+        call's clamp range — what EG3D's zero-opacity ray gets (0 if no ray is valid); nothing in the dict is NaN or inf.  The limits
+        are NOT differentiated (a limit that requires grad raises; "box" computes them from detached rays): the rays' gradient is
+        the derivative with the limits held fixed — EG3D's autograd also moves the sample positions through the box intersection;
+        leaving that term out is deliberate, as for the importance depths — and an empty ray gets exactly zero gradient."""
         if noise_mode != "const":
             raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
+        if ray_limits is not None and ray_limits != "box":
+            raise ValueError(f"TriPlaneGenerator.render_rays: ray_limits must be None or 'box', got {ray_limits!r}")
+        if (t_near is None) != (t_far is None):
+            raise ValueError("TriPlaneGenerator.render_rays: t_near and t_far go together (both or neither)")
+        if ray_limits is not None and t_near is not None:
+            raise ValueError("TriPlaneGenerator.render_rays: ray_limits='box' and explicit t_near / t_far are mutually exclusive")
         for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
             if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] != ws.shape[0]:
                 raise ValueError(f"expected {name} [B, R, 3] for ws of batch {ws.shape[0]}, got {tuple(t.shape)}")
@@ -1153,14 +1169,43 @@ class TriPlaneGenerator(nn.Module):
         cfg = self.cfg
         b, r = ray_origins.shape[0], ray_origins.shape[1]
         dev = ws.device
+        limits = None              # (t_near, t_far) fp32 [B,R] on the device, or "box": computed next to the launch
+        if t_near is not None:
+            limits = []
+            for name, t in (("t_near", t_near), ("t_far", t_far)):
+                if isinstance(t, torch.Tensor):
+                    if t.shape != (b, r):
+                        raise ValueError(f"TriPlaneGenerator.render_rays: {name} must be [B, R] = [{b}, {r}] or a float, got "
+                                         f"{tuple(t.shape)}")
+                    if not t.is_floating_point():
+                        raise TypeError(f"TriPlaneGenerator.render_rays: {name} must be a floating-point tensor, got {t.dtype}")
+                    if torch.is_grad_enabled() and t.requires_grad:
+                        raise NotImplementedError(f"TriPlaneGenerator.render_rays: {name} requires grad, but the ray limits are not "
+                                                  f"differentiated (pass {name}.detach())")
+                    if not t.is_cuda:
+                        raise RuntimeError("TriPlaneGenerator.render_rays: the MI355X path needs CUDA/ROCm tensors; there is no CPU "
+                                           "fallback")
+                    limits.append(t.detach().float().contiguous())
+                else:
+                    limits.append(torch.full((b, r), float(t), device=dev, dtype=torch.float32))
+            limits = tuple(limits)
+        elif ray_limits == "box":
+            limits = "box"
         params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
         grad = torch.is_grad_enabled() and (ws.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad or
                                             any(p.requires_grad for p in params))
         if b == 0 or r == 0:
             zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0      # keeps the autograd edges
             feat = torch.zeros(b, r, 32, device=dev) + zero
-            return {"feature": feat, "rgb": feat[..., :3], "depth": torch.zeros(b, r, device=dev) + zero,
-                    "mask": torch.zeros(b, r, device=dev) + zero}
+            out = {"feature": feat, "rgb": feat[..., :3], "depth": torch.zeros(b, r, device=dev) + zero,
+                   "mask": torch.zeros(b, r, device=dev) + zero}
+            if limits is not None:
+                out["valid"] = torch.zeros(b, r, device=dev, dtype=torch.bool)
+            return out
+        if limits == "box":
+            with torch.no_grad():
+                limits = ops.ray_limits_box(ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous(),
+                                            cfg.box_warp)
         if u_strat is None:
             u_strat = torch.rand(b, r, cfg.depth_resolution, device=dev)
         if u_imp is None:
@@ -1171,15 +1216,20 @@ class TriPlaneGenerator(nn.Module):
                 raise RuntimeError("TriPlaneGenerator.render_rays under grad inside a trainer step scope: its backward is a second "
                                    "backbone pass and would release every parameter to the gradient sink twice")
             from .autograd import RenderRaysFn
-            feat, depth, mask = RenderRaysFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, *params)
+            feat, depth, mask = RenderRaysFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits, *params)
         else:
             with torch.no_grad():
                 planes, pam = self._query_planes(ws)
+                lim = {} if limits is None else dict(t_near=limits[0], t_far=limits[1])
                 feat, depth, mask, tmm = ops.raymarch_rays(planes, ray_origins.detach().float().contiguous(),
                                                            ray_directions.detach().float().contiguous(), u_strat, u_imp,
-                                                           planes_absmax=pam, **self._rays_kwargs())
-                depth = ops.depth_clamp_(depth, tmm)
-        return {"feature": feat, "rgb": feat[..., :3], "depth": depth, "mask": mask}
+                                                           planes_absmax=pam, **lim, **self._rays_kwargs())
+                depth = ops.depth_clamp_(depth, tmm) if limits is None else ops.depth_clamp_(depth, tmm, empty_rays=True)
+        out = {"feature": feat, "rgb": feat[..., :3], "depth": depth, "mask": mask}
+        if limits is not None:
+            from .cam_utils import ray_limits_valid
+            out["valid"] = ray_limits_valid(*limits)
+        return out
 
     def sample(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], z: torch.Tensor, c: torch.Tensor,
                truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:

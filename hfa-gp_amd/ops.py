@@ -729,10 +729,12 @@ def _ray_args(who: str, f, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0
 
 def _ray_list_args(who: str, l, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, ray_start: float,
                    ray_end: float, box_warp: float, decoder_lr_mul: float, plane_axes, white_back: bool, decoder_precision: str,
-                   planes_absmax, state):
+                   planes_absmax, state, t_near=None, t_far=None):
     """`_ray_args` for a ray list: fills the RayListArgs / RayListBwdArgs ``l`` — the rays, R, and its RaymarchArgs member but the
-    camera (ignored by the list entry points) and the forward's outputs — and returns (B, H, W, R, Sc, Sf).  Owns the checks of the
-    rays' shapes, the uniforms' element counts, `state` and of device, dtype and contiguity of every input."""
+    camera (ignored by the list entry points) and the forward's outputs — and returns (B, H, W, R, Sc, Sf, limits).  Owns the checks
+    of the rays' shapes, the uniforms' element counts, `state`, the per-ray limits and of device, dtype and contiguity of every
+    input.  ``limits``: a filled RayLimits when t_near / t_far [B,R] are given (both or neither) — the caller then runs the
+    `limits` entry point — else None."""
     f = l.base if isinstance(l, L.RayListArgs) else l.bwd.fwd
     b, h, w = _planes_dims(who, planes)
     for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
@@ -754,7 +756,16 @@ def _ray_list_args(who: str, l, planes, ray_origins, ray_directions, u_strat, u_
     f.plane_axes, f.white_back = _plane_axes_id(plane_axes), int(white_back)
     f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
     l.ray_origins, l.ray_directions, l.R = _ptr(ray_origins), _ptr(ray_directions), r
-    return b, h, w, r, sc, sf
+    if (t_near is None) != (t_far is None):
+        raise RuntimeError(f"{who}: t_near and t_far go together (both or neither)")
+    limits = None
+    if t_near is not None:
+        for name, t in (("t_near", t_near), ("t_far", t_far)):
+            if _chk(t, f"{who}: {name}").shape != (b, r):
+                raise RuntimeError(f"{who}: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
+        limits = L.RayLimits()
+        limits.t_near, limits.t_far = _ptr(t_near), _ptr(t_far)
+    return b, h, w, r, sc, sf, limits
 
 
 def _dec_grad_out(who: str, a, params, decoder_grads: bool, dec_out):
@@ -807,14 +818,19 @@ def raymarch_rays(planes: torch.Tensor, ray_origins: torch.Tensor, ray_direction
                   u_imp: torch.Tensor, dec_w0: torch.Tensor, dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor,
                   ray_start: float, ray_end: float, box_warp: float, decoder_lr_mul: float = 1.0, plane_axes: int = 0,
                   white_back: bool = False, decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None,
-                  state: Optional[torch.Tensor] = None):
+                  state: Optional[torch.Tensor] = None, t_near: Optional[torch.Tensor] = None,
+                  t_far: Optional[torch.Tensor] = None):
     """`raymarch` on caller-given rays: ray_origins / ray_directions [B,R,3] (directions as given, not normalised: a sample is
     o + t d) instead of (cam2world, intrinsics, res) → feat [B,R,32], depth [B,R] (unclamped), wsum [B,R], tminmax [B,R,2].
-    u_strat [B,R,Sc], u_imp [B*R,Sf]; ``state``: `raymarch_rays_state`.  Everything else as `raymarch`."""
+    u_strat [B,R,Sc], u_imp [B*R,Sf]; ``state``: `raymarch_rays_state`.  Everything else as `raymarch`.
+    ``t_near`` / ``t_far`` [B,R] (both or neither; `ray_limits_box`, or any limits of the caller's): every ray is sampled on its own
+    interval instead of [ray_start, ray_end], which is then ignored (hfagp_raymarch_rays_limits_fwd).  A ray whose limits are not
+    finite or have far <= near is EMPTY and not marched: feat = the background (−1, or +1 with white_back), wsum 0, depth +inf,
+    tminmax (+inf, −inf) — `depth_range(..., empty_rays=True)` / `depth_clamp_(..., empty_rays=True)` take such a call."""
     a = L.RayListArgs()
-    b, _, _, r, _, _ = _ray_list_args("raymarch_rays", a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1,
-                                      dec_b1, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision,
-                                      planes_absmax, state)
+    b, _, _, r, _, _, lim = _ray_list_args("raymarch_rays", a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0,
+                                           dec_w1, dec_b1, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back,
+                                           decoder_precision, planes_absmax, state, t_near, t_far)
     dev = planes.device
     feat = torch.empty(b, r, 32, device=dev, dtype=torch.float32)
     depth = torch.empty(b, r, device=dev, dtype=torch.float32)
@@ -824,8 +840,34 @@ def raymarch_rays(planes: torch.Tensor, ray_origins: torch.Tensor, ray_direction
         return feat, depth, wsum, tmm
     f = a.base
     f.feat, f.depth, f.wsum, f.tminmax = _ptr(feat), _ptr(depth), _ptr(wsum), _ptr(tmm)
-    L.check(L.lib().hfagp_raymarch_rays_fwd(C.byref(a), _stream()), "raymarch_rays_fwd")
+    if lim is not None:
+        L.check(L.lib().hfagp_raymarch_rays_limits_fwd(C.byref(a), C.byref(lim), _stream()), "raymarch_rays_limits_fwd")
+    else:
+        L.check(L.lib().hfagp_raymarch_rays_fwd(C.byref(a), _stream()), "raymarch_rays_fwd")
     return feat, depth, wsum, tmm
+
+
+def ray_limits_box(ray_origins: torch.Tensor, ray_directions: torch.Tensor, box_side: float):
+    """(t_near, t_far), each [B,R]: every ray's slab intersection with the cube [−box_side/2, box_side/2]³ the tri-planes cover
+    (box_side = cfg.box_warp) — EG3D's ray_start = ray_end = 'auto' — for `raymarch_rays(..., t_near=, t_far=)`.  t_near is clamped
+    below at 0 (an origin inside the cube starts at the origin); a ray that misses has t_far <= t_near, a 0 · inf case gives NaN
+    limits: both are empty rays to the ray marcher.  One launch (hfagp_ray_limits_box); `cam_utils.ray_limits_box` is the same
+    formula in torch."""
+    who = "ray_limits_box"
+    for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
+        if _chk(t, f"{who}: {name}").dim() != 3 or t.shape[2] != 3:
+            raise RuntimeError(f"{who}: {name} must be [B, R, 3], got {tuple(t.shape)}")
+    if ray_origins.shape != ray_directions.shape:
+        raise RuntimeError(f"{who}: ray_origins {tuple(ray_origins.shape)} and ray_directions {tuple(ray_directions.shape)} differ")
+    if not (box_side > 0 and math.isfinite(box_side)):
+        raise RuntimeError(f"{who}: box_side must be positive and finite, got {box_side}")
+    b, r = ray_origins.shape[:2]
+    t_near = torch.empty(b, r, device=ray_origins.device, dtype=torch.float32)
+    t_far = torch.empty(b, r, device=ray_origins.device, dtype=torch.float32)
+    if b * r:
+        L.check(L.lib().hfagp_ray_limits_box(_ptr(ray_origins), _ptr(ray_directions), _ptr(t_near), _ptr(t_far), b * r, float(box_side),
+                                             _stream()), who)
+    return t_near, t_far
 
 
 def raymarch_normals(planes: torch.Tensor, state: torch.Tensor, *, cam2world: torch.Tensor, intrinsics: torch.Tensor,
@@ -1150,13 +1192,17 @@ def marching_cubes(volume: torch.Tensor, level: float, spacing=(1.0, 1.0, 1.0), 
     return verts, faces
 
 
-def depth_clamp_(depth: torch.Tensor, tminmax: torch.Tensor) -> torch.Tensor:
+def depth_clamp_(depth: torch.Tensor, tminmax: torch.Tensor, empty_rays: bool = False) -> torch.Tensor:
     """In place: depth.clamp_(tminmax[..., 0].min(), tminmax[..., 1].max()) — MipRayMarcher2's batch-global depth clamp — as ONE
-    launch (hfagp_depth_clamp)."""
+    launch (hfagp_depth_clamp).  ``empty_rays``: a `raymarch_rays` call with per-ray limits, whose empty rays carry depth +inf and
+    (+inf, −inf): they stay out of the range (the min / max ignore them) and get its upper end, as EG3D's zero-opacity ray does; a
+    call WITHOUT a valid ray has the range (+inf, −inf), and every depth becomes 0 (no host sync: a `where` on the result)."""
     _chk(depth, "depth")
     _chk(tminmax, "tminmax")
     n = depth.numel()
     L.check(L.lib().hfagp_depth_clamp(_ptr(depth), _ptr(tminmax), n, _stream()), "depth_clamp")
+    if empty_rays:          # (after the clamp a depth is non-finite iff an end of the range is)
+        depth.copy_(torch.where(torch.isfinite(depth), depth, torch.zeros_like(depth)))
     return depth
 
 
@@ -1706,12 +1752,15 @@ def rows_scratch_cap(device=None) -> int:
     return cap
 
 
-def depth_range(tminmax: torch.Tensor) -> torch.Tensor:
+def depth_range(tminmax: torch.Tensor, empty_rays: bool = False) -> torch.Tensor:
     """tminmax [..., 2] as `raymarch` writes it → [2] device tensor (lo, hi): the batch-global range `depth_clamp_` clamps the
-    expected depth to, for `raymarch_bwd(g_depth=..., depth_range=...)`.  No host sync."""
+    expected depth to, for `raymarch_bwd(g_depth=..., depth_range=...)`.  No host sync.  ``empty_rays`` (a `raymarch_rays` call with
+    per-ray limits): the range is over the valid rays — the (+inf, −inf) of an empty ray does not enter a min / max — and an end
+    that is not finite (no valid ray at all) becomes 0, as in `depth_clamp_(..., empty_rays=True)`."""
     _chk(tminmax, "tminmax")
     t = tminmax.reshape(-1, 2)
-    return torch.stack((t[:, 0].amin(), t[:, 1].amax()))
+    rng = torch.stack((t[:, 0].amin(), t[:, 1].amax()))
+    return torch.where(torch.isfinite(rng), rng, torch.zeros_like(rng)) if empty_rays else rng
 
 
 def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0,
@@ -1853,12 +1902,15 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
                       decoder_grads: bool = False, decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None,
                       state: Optional[torch.Tensor] = None, rows: Optional[bool] = None, dec_out=None, _out=None,
                       g_depth: Optional[torch.Tensor] = None, g_wsum: Optional[torch.Tensor] = None,
-                      depth_range: Optional[torch.Tensor] = None, rec_out: Optional[list] = None):
+                      depth_range: Optional[torch.Tensor] = None, rec_out: Optional[list] = None,
+                      t_near: Optional[torch.Tensor] = None, t_far: Optional[torch.Tensor] = None):
     """`raymarch_bwd` of `raymarch_rays`: g_feat [B,R,32] (and / or g_depth, g_wsum [B,R]) → d planes [B,3,H,W,32], with the same
     keywords and return forms.  ``rows``: None = sort + gather whenever it applies, False = the scatter kernels (the image-column
     variant of the grid is not offered for a list).  The sort's scratch is bounded by `rows_scratch_cap()` as for the grid; a list may
     be cut at any ray, so a call that needs more runs in frame chunks and, where one frame is too much, in ray chunks of a frame.
-    ``rec_out``: receives pass 1's records [B,R,Sc+Sf,4] (`raymarch_rays_bwd_rays` reads them)."""
+    ``rec_out``: receives pass 1's records [B,R,Sc+Sf,4] (`raymarch_rays_bwd_rays` reads them).  ``t_near`` / ``t_far`` [B,R]: the
+    forward call's per-ray limits (hfagp_raymarch_rays_limits_bwd); they carry no gradient, an empty ray contributes exactly zero
+    and its g_depth / g_wsum are not read; ``depth_range`` is then `ops.depth_range(tminmax, empty_rays=True)`."""
     who = "raymarch_rays_bwd"
     b, _, _ = _planes_dims(who, planes)
     r = ray_origins.shape[1] if ray_origins.dim() == 3 else -1
@@ -1879,8 +1931,8 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
     dec = _raymarch_rays_bwd_chunk(
         g_feat=g_feat, planes=planes, ray_origins=ray_origins, ray_directions=ray_directions, u_strat=u_strat,
         u_imp=u_imp.reshape(b, r, sf) if r >= 0 and u_imp.numel() == b * r * sf else u_imp, state=state, g_depth=g_depth, g_wsum=g_wsum,
-        depth_range=depth_range, d_planes=d_planes, rec=rec, decoder_grads=decoder_grads, dec_out=dec_out, rows=rows, dec_w0=dec_w0,
-        dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, ray_start=ray_start, ray_end=ray_end, box_warp=box_warp,
+        t_near=t_near, t_far=t_far, depth_range=depth_range, d_planes=d_planes, rec=rec, decoder_grads=decoder_grads, dec_out=dec_out,
+        rows=rows, dec_w0=dec_w0, dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, ray_start=ray_start, ray_end=ray_end, box_warp=box_warp,
         decoder_lr_mul=decoder_lr_mul, plane_axes=plane_axes, white_back=white_back, decoder_precision=decoder_precision,
         planes_absmax=_decoder_bound(planes, decoder_precision, planes_absmax) if planes.numel() else None)
     if decoder_grads:
@@ -1888,13 +1940,14 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
     return (d_planes, rec) if return_rec else d_planes
 
 
-def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_strat, u_imp, state, g_depth, g_wsum, depth_range,
-                             d_planes, rec, decoder_grads, dec_out, rows, **scene):
+def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_strat, u_imp, state, g_depth, g_wsum, t_near, t_far,
+                             depth_range, d_planes, rec, decoder_grads, dec_out, rows, **scene):
     """`raymarch_rays_bwd` of the rays it is given: the whole list or — from itself — a chunk of it (`_raymarch_bwd_frames` for a
     list; u_imp arrives as [B,R,Sf]).  Fills ``d_planes`` and ``rec`` in place, returns the decoder-gradient tuple or None."""
     who = "raymarch_rays_bwd"
     a = L.RayListBwdArgs()
-    b, h, w, r, sc, sf = _ray_list_args(who, a, planes, ray_origins, ray_directions, u_strat, u_imp, state=state, **scene)
+    b, h, w, r, sc, sf, lim = _ray_list_args(who, a, planes, ray_origins, ray_directions, u_strat, u_imp, state=state, t_near=t_near,
+                                             t_far=t_far, **scene)
     dec = _dec_grad_out(who, a.bwd, [scene[k] for k in _DEC], decoder_grads, dec_out)
     if b * r == 0:
         return dec
@@ -1909,7 +1962,7 @@ def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_s
             # every per-ray input / output is [B, R, ...]: frames are contiguous slices, and so are the rays r0:r1 of ONE frame; the
             # decoder gradients accumulate in the one `dec`, d_planes accumulates per frame, the depth range is the call's
             per_ray = dict(g_feat=g_feat, ray_origins=ray_origins, ray_directions=ray_directions, u_strat=u_strat, u_imp=u_imp,
-                           state=state, g_depth=g_depth, g_wsum=g_wsum, rec=rec)
+                           state=state, g_depth=g_depth, g_wsum=g_wsum, rec=rec, t_near=t_near, t_far=t_far)
             fit = max(1, int(b * r * cap // need))            # rays one call can take
             nb, nr = (max(1, min(b - 1, fit // r)), r) if fit >= r and b > 1 else (1, max(1, min(r - 1, fit)))
             chunks = 0
@@ -1939,23 +1992,28 @@ def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_s
     else:
         gg = L.RaymarchGeomGrads()
         gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
-    L.check(L.lib().hfagp_raymarch_rays_bwd(C.byref(a), C.byref(gg) if gg is not None else None, _stream()), who)
+    if lim is not None:
+        L.check(L.lib().hfagp_raymarch_rays_limits_bwd(C.byref(a), C.byref(lim), C.byref(gg) if gg is not None else None, _stream()), who)
+    else:
+        L.check(L.lib().hfagp_raymarch_rays_bwd(C.byref(a), C.byref(gg) if gg is not None else None, _stream()), who)
     return dec
 
 
 def raymarch_rays_bwd_rays(g_feat: Optional[torch.Tensor], planes: torch.Tensor, rec: torch.Tensor, ray_origins: torch.Tensor,
                            ray_directions: torch.Tensor, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, ray_start: float,
                            ray_end: float, box_warp: float, decoder_lr_mul: float = 1.0, plane_axes: int = 0, white_back: bool = False,
-                           decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None):
+                           decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None,
+                           t_near: Optional[torch.Tensor] = None, t_far: Optional[torch.Tensor] = None):
     """The rays' gradient of `raymarch_rays` (hfagp_raymarch_rays_bwd_rays) → (d origins, d directions), each [B,R,3].  ``g_feat`` and
     the other arguments as in the `raymarch_rays_bwd` call that wrote ``rec`` (its ``rec_out=`` / ``return_rec=True``): the depth,
     opacity and white_back terms are already in the records.  Independent of the pass-2 form that call ran; one writer per ray, no
-    atomics: two calls return the same bits."""
+    atomics: two calls return the same bits.  ``t_near`` / ``t_far``: as in that call (hfagp_raymarch_rays_limits_bwd_rays) — the
+    derivative is the one with the limits HELD FIXED, and exactly zero for an empty ray."""
     who = "raymarch_rays_bwd_rays"
     a = L.RayListBwdArgs()
-    b, _, _, r, sc, sf = _ray_list_args(who, a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1,
-                                        ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision,
-                                        planes_absmax, None)
+    b, _, _, r, sc, sf, lim = _ray_list_args(who, a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1,
+                                             ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back, decoder_precision,
+                                             planes_absmax, None, t_near, t_far)
     if _chk(rec, f"{who}: rec").shape != (b, r, sc + sf, 4):
         raise RuntimeError(f"{who}: rec must be [B, R, Sc + Sf, 4] = [{b}, {r}, {sc + sf}, 4], got {tuple(rec.shape)}")
     if g_feat is not None and _chk(g_feat, f"{who}: g_feat").shape != (b, r, 32):
@@ -1965,7 +2023,10 @@ def raymarch_rays_bwd_rays(g_feat: Optional[torch.Tensor], planes: torch.Tensor,
     if b * r == 0:
         return d_o, d_d
     a.bwd.g_feat, a.bwd.rec = _ptr(g_feat), _ptr(rec)
-    L.check(L.lib().hfagp_raymarch_rays_bwd_rays(C.byref(a), _ptr(d_o), _ptr(d_d), _stream()), who)
+    if lim is not None:
+        L.check(L.lib().hfagp_raymarch_rays_limits_bwd_rays(C.byref(a), C.byref(lim), _ptr(d_o), _ptr(d_d), _stream()), who)
+    else:
+        L.check(L.lib().hfagp_raymarch_rays_bwd_rays(C.byref(a), _ptr(d_o), _ptr(d_d), _stream()), who)
     return d_o, d_d
 
 

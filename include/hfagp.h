@@ -49,6 +49,8 @@
  *   hfagp_raymarch_bwd_camera <- autograd of RaySampler + grid_sample w.r.t. the sample positions: the gradient of the camera label
  *   hfagp_raymarch_rays_fwd / _rays_bwd / _rays_bwd_rays <- ImportanceRenderer.forward on explicit (ray_origins, ray_directions) and
  *                              its autograd w.r.t. planes, decoder and the rays (crops, multi-view lists, arbitrary camera models)
+ *   hfagp_raymarch_rays_limits_fwd / _limits_bwd / _limits_bwd_rays, hfagp_ray_limits_box <- the same with per-ray depth limits:
+ *                              ImportanceRenderer.forward with ray_start == ray_end == 'auto' (math_utils.get_ray_limits_box)
  *   hfagp_planes_query_bwd  <- autograd of sample_mixed (grid_sample + OSGDecoder at given points) w.r.t. planes, decoder and points
  *   hfagp_modconv_fwd modes HFAGP_CONV3X3_BWD / HFAGP_CONVS2_BWD <- conv2d_gradfix data gradients (the same GEMM kernel)
  *   hfagp_conv_wgrad (+ _workspace_bytes) <- conv2d_gradfix weight gradients
@@ -843,6 +845,42 @@ size_t hfagp_raymarch_rays_bwd_rows_bytes(const HfagpRayListArgs* a);
  * its reduction; the sample depths carry no gradient).  One writer per ray, no atomics, no reduction: two calls give the same
  * bits.  HFAGP_EBADARG also for a->bwd.rec, d_origins or d_directions NULL.                                                  */
 int hfagp_raymarch_rays_bwd_rays(const HfagpRayListBwdArgs* a, float* d_origins, float* d_directions, void* stream);
+
+/* ------------------------------------------------------------------ per-ray depth limits for ray lists (additive to ABI 15)
+ * The three list entry points above with a [t_near, t_far] per ray instead of the one interval base.ray_start / ray_end (which
+ * is then neither read nor checked): EG3D's ImportanceRenderer with ray_start == ray_end == 'auto' (hfagp_ray_limits_box gives
+ * the limits of the tri-plane cube), a camera at any distance, directions of any length, a visibility ray from a surface point
+ * (t_near = 0, t_far = the distance to the light), depth-guided sampling (depth -+ delta).
+ * Coarse sample s of S = Sc, in fp32 with every operation rounded on its own (math_utils.linspace + sample_stratified for tensor
+ * limits):   span = far - near,   t_s = near + (float(s) / float(S-1)) * span + u_s * (span / float(S-1)).
+ * Everything after the coarse depths — importance pass, merge, compositing, state, records — is unchanged.
+ * A ray is VALID iff both limits are finite and far > near; any other ray is EMPTY and is not marched (no gather, no decoder):
+ *   forward: feat = -1 in all 32 channels (+1 with white_back), wsum = 0, depth = +inf, tminmax = (+inf, -inf) — so it does not
+ *            enter a min / max over the call's rays; its slice of `state` is not written (unspecified);
+ *   backward: its S records are zero, and with them d_planes, the decoder gradients, d_origins and d_directions receive exactly
+ *            zero from it; g_depth / g_wsum of an empty ray are not read.
+ * The limits carry no gradient (as the sample depths carry none).                                                             */
+typedef struct {
+    const float* t_near;          /* [B][R] */
+    const float* t_far;           /* [B][R] */
+} HfagpRayLimits;
+
+/* Slab intersection of n_rays rays ([n][3] origins / directions, any layout of B and R) with the cube [-box_side/2, box_side/2]^3:
+ * per axis inv = 1 / d (IEEE, +-inf for a zero component), t0 = (-h - o) * inv, t1 = (h - o) * inv; t_near = max over the axes of
+ * min(t0, t1), clamped below at 0 (an origin inside the cube starts at the origin: NOT EG3D's value there); t_far = min over
+ * the axes of max(t0, t1).  A miss has t_far <= t_near; a NaN (origin exactly on a slab of an axis the ray is parallel to) makes
+ * both limits NaN: either way the ray is empty for the entry points below.  t_near, t_far [n]: written.
+ * HFAGP_EBADARG: a NULL pointer, n_rays <= 0 or >= 2^31, box_side not positive and finite.                                      */
+int hfagp_ray_limits_box(const float* ray_origins, const float* ray_directions, float* t_near, float* t_far,
+                         int64_t n_rays, float box_side, void* stream);
+/* HFAGP_EBADARG, nothing launched: lim or one of its members NULL; then the checks of the entry point without limits, minus
+ * ray_end > ray_start.                                                                                                        */
+int hfagp_raymarch_rays_limits_fwd(const HfagpRayListArgs* a, const HfagpRayLimits* lim, void* stream);
+int hfagp_raymarch_rays_limits_bwd(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim,
+                                   const HfagpRaymarchGeomGrads* g, void* stream);
+/* (reads the depths from the records of hfagp_raymarch_rays_limits_bwd; lim is checked, its arrays are not read)               */
+int hfagp_raymarch_rays_limits_bwd_rays(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim,
+                                        float* d_origins, float* d_directions, void* stream);
 
 /* ------------------------------------------------------------------ antialiased resample (additive to ABI 15)
  * SuperresolutionHybrid8XDC's F.interpolate(mode='bilinear', align_corners=False, antialias=True) of the feature image and the
