@@ -257,6 +257,10 @@ SYMBOLS = {
                                                  C.c_void_p]),
     "hfagp_raymarch_rays_limits_bwd_rays": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RayLimits), C.c_void_p, C.c_void_p,
                                                       C.c_void_p]),
+    "hfagp_raymarch_rays_normals": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits), C.c_void_p, C.c_void_p]),
+    "hfagp_raymarch_rays_normals_bwd": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits)] + [C.c_void_p] * 7),
+    "hfagp_raymarch_rays_normals_bwd_rays": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_int, C.c_void_p]),
     "hfagp_resize_aa_fwd": (C.c_int, [C.POINTER(ResizeAaArgs), C.c_void_p]),
     "hfagp_resize_aa_bwd": (C.c_int, [C.POINTER(ResizeAaArgs), C.c_void_p]),
     "hfagp_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),

@@ -787,3 +787,88 @@ class RenderRaysFn(torch.autograd.Function):
         ctx.tape = ctx.planes = ctx.state = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
         return (d_ws, d_o, d_d, None, None, None, None) + pgrads
+
+
+class RenderRaysNormalFn(torch.autograd.Function):
+    """`TriPlaneGenerator.render_rays(normals=True / normal_grad=True)` under grad: the inputs of RenderRaysFn with
+    ``normal_ray_grad`` (a bool) in front of the parameters; outputs feature, depth, mask and normal [B,R,3].  The forward is
+    RenderRaysFn's plus one launch (ops.raymarch_rays_normals) on the state it kept.  Backward, when the loss used the normals:
+    ops.raymarch_rays_bwd first, and only if feature, depth or mask carry a gradient (on mirrored planes it overwrites plane 2);
+    then ops.raymarch_rays_normals_bwd into the same d_planes and decoder gradients (fresh zeros for a normals-only loss); then the
+    rays' passes when the rays require grad — the colour term's, then with ``normal_ray_grad`` the normal term's added to it;
+    then the one backbone backward.  A loss that ignores the normals runs RenderRaysFn's backward as it stands."""
+    @staticmethod
+    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad, *params):
+        feat, depth, wsum = RenderRaysFn.forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params)
+        (o, d), b = ctx.rays, ws.shape[0]
+        with torch.no_grad():
+            if ctx.state is None:        # above RAY_STATE_CAP_BYTES (a detached map: render_rays refuses normal_grad there)
+                from .generator import RAY_STATE_CAP_BYTES
+                per_row = b * (u_strat.shape[-1] + u_imp.shape[-1]) * 140
+                normal = gen._render_rays_normals_chunked(ctx.planes, o, d, u_strat, u_imp, ctx.pam, ctx.lim,
+                                                          max(1, RAY_STATE_CAP_BYTES // per_row))[4]
+            else:
+                normal = gen._timed("raymarch_rays_normals", float(b), ops.raymarch_rays_normals, ctx.planes, ctx.state,
+                                    ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=ctx.pam, **ctx.lim,
+                                    **gen._rays_kwargs())
+        ctx.normal_ray_grad = bool(normal_ray_grad)
+        return feat, depth, wsum, normal
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_feat, g_depth, g_wsum, g_normal):
+        if g_normal is None:             # the loss did not use 'normal': no launch of its own
+            grads = RenderRaysFn.backward(ctx, g_feat, g_depth, g_wsum)
+            return grads[:7] + (None,) + grads[7:]
+        gen = ctx.gen
+        if ctx.tape is None:
+            raise RuntimeError("TriPlaneGenerator.render_rays: backward called a second time — the saved activations are released "
+                               "by the first backward pass (retain_graph is not supported)")
+        if ctx.state is None:
+            raise RuntimeError("TriPlaneGenerator.render_rays(normal_grad=True): the forward kept no per-sample state "
+                               "(RAY_STATE_CAP_BYTES)")
+        planes = ctx.planes
+        b, dev = planes.shape[0], planes.device
+        (o, d), (u_strat, u_imp) = ctx.rays, ctx.uniforms
+        r = o.shape[1]
+        d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
+        bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
+        g_feat = None if g_feat is None else g_feat.float().contiguous()
+        g_nrm = g_normal.float().reshape(b, r, 3).contiguous()
+        geom = {}
+        if g_depth is not None:
+            geom.update(g_depth=g_depth.float().reshape(b, r).contiguous(), depth_range=ctx.depth_range)
+        if g_wsum is not None:
+            geom.update(g_wsum=g_wsum.float().reshape(b, r).contiguous())
+        colour = g_feat is not None or bool(geom)
+        need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        d_planes = dec = None
+        rec_out = [] if need_rays else None
+        if colour:
+            rb = gen._timed("raymarch_rays_bwd", float(b), ops.raymarch_rays_bwd, g_feat, planes, o, d, u_strat, u_imp,
+                            decoder_grads=ctx.pg, planes_absmax=ctx.pam, state=ctx.state, rec_out=rec_out, **geom, **ctx.lim,
+                            **gen._rays_kwargs())
+            d_planes, dec = rb if ctx.pg else (rb, None)
+        # after raymarch_rays_bwd: that call overwrites plane 2 on mirrored planes, this one adds to every plane at its true texels
+        d_planes, dec = gen._timed("raymarch_rays_normals_bwd", float(b), ops.raymarch_rays_normals_bwd, g_nrm, planes, ctx.state,
+                                   ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=ctx.pam,
+                                   d_planes=d_planes, decoder_grads=ctx.pg, dec_out=dec, **ctx.lim, **gen._rays_kwargs())
+        d_o = d_d = None
+        if need_rays:
+            if colour:
+                d_o, d_d = gen._timed("raymarch_rays_bwd_rays", float(b), ops.raymarch_rays_bwd_rays, g_feat, planes, rec_out[0], o, d,
+                                      u_strat, u_imp, planes_absmax=ctx.pam, **ctx.lim, **gen._rays_kwargs())
+            if ctx.normal_ray_grad:      # the normal term joins the colour term's records (written into fresh ones without it)
+                d_o, d_d = gen._timed("raymarch_rays_normals_bwd_rays", float(b), ops.raymarch_rays_normals_bwd_rays, g_nrm, planes,
+                                      ctx.state, d_origins=d_o, d_directions=d_d, ray_origins=o, ray_directions=d, u_strat=u_strat,
+                                      u_imp=u_imp, planes_absmax=ctx.pam, **ctx.lim, **gen._rays_kwargs())
+            if d_o is not None:
+                d_o, d_d = (d_o.to(ctx.ray_dtypes[0]) if ctx.needs_input_grad[1] else None,
+                            d_d.to(ctx.ray_dtypes[1]) if ctx.needs_input_grad[2] else None)
+        if ctx.pg:
+            for prm, g in zip(gen.decoder_params(), dec):
+                bw._acc(prm, g)
+        _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
+        ctx.tape = ctx.planes = ctx.state = None
+        pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
+        return (d_ws, d_o, d_d, None, None, None, None, None) + pgrads

@@ -42,10 +42,14 @@ units+=(planes_query_normals_bwd)
 units+=(raymarch_rays)
 units+=(resample_aa)
 units+=(ray_limits)
+units+=(raymarch_rays_normals)
+# a unit that compiles other units' sources again (#include "x.hip"): their content is part of its object's hash
+declare -A includes=([raymarch_rays_normals]="raymarch_normals raymarch_normals_bwd raymarch_normals_camera")
 for src in "${units[@]}"; do
     obj="${here}/${src}.o"
     extra=()
-    want="$( (echo "${common_hash} ${FLAGS[*]} ${extra[*]:-} ${HFAGP_EXTRA_FLAGS:-}"; cat "${here}/${src}.hip") | sha256sum | cut -d' ' -f1)"
+    want="$( (echo "${common_hash} ${FLAGS[*]} ${extra[*]:-} ${HFAGP_EXTRA_FLAGS:-}"; cat "${here}/${src}.hip"
+              for inc in ${includes[$src]:-}; do cat "${here}/${inc}.hip"; done) | sha256sum | cut -d' ' -f1)"
     have="$(cat "${obj}.sha256" 2>/dev/null || true)"
     if [[ "${HFAGP_CLEAN:-0}" == 1 || ! -f "$obj" || "$want" != "$have" ]]; then
         rm -f "${obj}.sha256"

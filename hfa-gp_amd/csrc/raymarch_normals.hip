@@ -16,13 +16,19 @@
 //                             positional derivative of the bilinear gather (plane_taps_d) -> the four channel groups of a sample
 //                             summed with two shuffles -> n_s -> omega_s n_s on the lanes g == 0.  One writer per ray, plain
 //                             stores, fixed butterfly order: two calls give the same bits.
+//   raymarch_normals_kernel<.., LIST = true>   the same on a caller's ray list (hfagp_raymarch_rays_normals): the state is the one
+//                             raymarch_rays_kernel filled.
 #include "decoder_adjoint.h"
 
 namespace hfagp {
 
 constexpr int kNrmWaves = 4;
 
-template <int S, bool DEC16>
+// LIST: the rays of a caller's list (raymarch_common.h ray_fetch; directions as given) instead of the pinhole grid.  With per-ray
+// limits (RayParams::t_near / t_far) an EMPTY ray (raymarch.hip's predicate) stores three zeros and reads nothing of its `state`,
+// which the forward never wrote.  (The ray fetch is a template parameter of the kernel, not a shared body function: moving the code
+// into one changed the grid instantiations' register allocation — DESIGN.md has the table.)
+template <int S, bool DEC16, bool LIST = false>
 __global__ void __launch_bounds__(kNrmWaves * 64, 2)
 raymarch_normals_kernel(const RayParams p, float* __restrict__ normal) {
     __shared__ float w0t[2 * 16 * 64];
@@ -31,7 +37,7 @@ raymarch_normals_kernel(const RayParams p, float* __restrict__ normal) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const HfagpRaymarchArgs& a = p.a;
     const int j = lane & 15, g = lane >> 4;
-    const int R = a.res * a.res;
+    const int R = LIST ? p.R : a.res * a.res;
     constexpr int NT = S / 16;
     if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
     if constexpr (DEC16) build_grad16_lds<false>(a, nullptr, w0t, lane, wave, kNrmWaves);
@@ -44,11 +50,25 @@ raymarch_normals_kernel(const RayParams p, float* __restrict__ normal) {
     const float sx = (float)a.W * 0.5f * 0.3333333333333333f, sy = (float)a.H * 0.5f * 0.3333333333333333f;
     const RaySchedule sch = ray_schedule((long long)p.total_rays, wave, kNrmWaves);
     for (long long rp = sch.begin; rp < sch.end; rp += sch.stride) {
-        int b, pi, pj;
-        ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
-        const int ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+        int b, ray;
         float o3[3], d3[3];
-        ray_setup(a, b, pi, pj, o3, d3);
+        if constexpr (LIST) {
+            int ray_v;
+            ray_fetch<true>(p, __builtin_amdgcn_readfirstlane((int)rp), R, b, ray_v, o3, d3);
+            ray = __builtin_amdgcn_readfirstlane(ray_v);
+            if (p.t_near) {                         // (wave-uniform: the limit-less list call never enters)
+                const float t_near = p.t_near[ray], t_far = p.t_far[ray];
+                if (!(fabsf(t_near) < INFINITY && fabsf(t_far) < INFINITY && t_far > t_near)) {
+                    if (lane < 3) normal[(size_t)ray * 3 + lane] = 0.f;
+                    continue;
+                }
+            }
+        } else {
+            int pi, pj;
+            ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
+            ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+            ray_setup(a, b, pi, pj, o3, d3);
+        }
         {
             const float* st = a.state + (size_t)ray * (S * HFAGP_RAYMARCH_STATE_FLOATS_PER_SAMPLE);
 #pragma unroll
@@ -142,17 +162,18 @@ raymarch_normals_kernel(const RayParams p, float* __restrict__ normal) {
     }
 }
 
-template <int S>
+template <int S, bool LIST>
 static void launch_normals(const RayParams& p, float* normal, hipStream_t s) {
     const unsigned blocks = (unsigned)std::min<long long>(((long long)p.total_rays + kNrmWaves - 1) / kNrmWaves, (long long)kNumCU * 6);
-    if (p.a.planes_absmax) raymarch_normals_kernel<S, true><<<blocks, kNrmWaves * 64, 0, s>>>(p, normal);
-    else raymarch_normals_kernel<S, false><<<blocks, kNrmWaves * 64, 0, s>>>(p, normal);
+    if (p.a.planes_absmax) raymarch_normals_kernel<S, true, LIST><<<blocks, kNrmWaves * 64, 0, s>>>(p, normal);
+    else raymarch_normals_kernel<S, false, LIST><<<blocks, kNrmWaves * 64, 0, s>>>(p, normal);
 }
 
 }  // namespace hfagp
 
 using namespace hfagp;
 
+#ifndef HFAGP_RAY_LIST_UNIT        // (raymarch_rays_normals.hip compiles this source again for the list entry point alone)
 extern "C" int hfagp_raymarch_normals(const HfagpRaymarchArgs* fwd, float* normal, void* stream) {
     HFAGP_REQUIRE(fwd && normal && fwd->state && fwd->planes, HFAGP_EBADARG, "raymarch_normals: null pointer");
     RayParams p;
@@ -160,8 +181,26 @@ extern "C" int hfagp_raymarch_normals(const HfagpRaymarchArgs* fwd, float* norma
     if (rc != HFAGP_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int S = fwd->Sc + fwd->Sf;
-    if (S == 96) launch_normals<96>(p, normal, s);
-    else if (S == 64) launch_normals<64>(p, normal, s);
-    else launch_normals<32>(p, normal, s);
+    if (S == 96) launch_normals<96, false>(p, normal, s);
+    else if (S == 64) launch_normals<64, false>(p, normal, s);
+    else launch_normals<32, false>(p, normal, s);
     return check_launch("raymarch_normals");
 }
+
+#else
+extern "C" int hfagp_raymarch_rays_normals(const HfagpRayListArgs* a, const HfagpRayLimits* lim, float* normal, void* stream) {
+    HFAGP_REQUIRE(a && normal && a->base.state, HFAGP_EBADARG, "raymarch_rays_normals: null pointer");
+    HFAGP_REQUIRE(!lim || (lim->t_near && lim->t_far), HFAGP_EBADARG, "raymarch_rays_normals: null pointer (limits)");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->base, p, "raymarch_rays_normals", &rays, lim != nullptr);
+    if (rc != HFAGP_OK) return rc;
+    if (lim) { p.t_near = lim->t_near; p.t_far = lim->t_far; }
+    hipStream_t s = (hipStream_t)stream;
+    const int S = a->base.Sc + a->base.Sf;
+    if (S == 96) launch_normals<96, true>(p, normal, s);
+    else if (S == 64) launch_normals<64, true>(p, normal, s);
+    else launch_normals<32, true>(p, normal, s);
+    return check_launch("raymarch_rays_normals");
+}
+#endif

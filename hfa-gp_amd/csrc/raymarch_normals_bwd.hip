@@ -35,13 +35,23 @@ constexpr int kNbWaves = 4;
 // below marked `twin:` have a copy there as functions, used by that unit: calling them from here changed this unit's register
 // allocation and instruction order, so the lines stay inline; keep the two in step.)
 
-template <int S, bool DEC16, bool PG>
+// LIST: the rays of a caller's list (raymarch_common.h ray_fetch; directions as given) instead of the pinhole grid.  With per-ray
+// limits (RayParams::t_near / t_far) an EMPTY ray (raymarch.hip's predicate) is skipped before anything of it is read: its `state`
+// was never written.  (The ray fetch is a template parameter of the kernel, not a shared body function: see the note above on this
+// unit's register allocation — DESIGN.md has the table.)
+// With the 16-bit decoder the list form takes a = W0'^T dH from the exact fp32 MFMA in both passes (decoder_dh_lds + w0t_mul, the
+// choice of raymarch_normals_camera.hip and of normals_pass_a; no split-bf16 image of W0'^T is built), where the grid form takes it
+// from the forward normals' split-bf16 product (2^-16 per product): on the 2 x 101 list of non-unit directions that product put
+// d_planes at 1.09 of the gradient bar (small128; 0.044 with the fp32 decoder), beyond what the fp32 reference's own error allows.
+// n is then the forward's to ~2^-16, not to the bit.  The grid form keeps its arithmetic.
+template <int S, bool DEC16, bool PG, bool LIST = false>
 __global__ void __launch_bounds__(kNbWaves * 64, PG ? 1 : 2)
 raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_normal, float* __restrict__ d_planes, const DecGrads dg) {
     __shared__ Tile2Lds lds_all[kNbWaves];
     __shared__ __attribute__((aligned(16))) float glds_raw[PG ? kNbWaves * sizeof(NrmGradLds) / sizeof(float) : 1];
     __shared__ float w0t[2 * 16 * 64];                       // fp32 A operands of W0'^T (build_grad_lds)
-    __shared__ float g0img[DEC16 ? 2 * 16 * 64 : 1];         // split-bf16 A operands of W0'^T: the forward normals' adjoint
+    constexpr bool A16 = DEC16 && !LIST;                     // a from the split-bf16 product (the grid form with the 16-bit decoder)
+    __shared__ float g0img[A16 ? 2 * 16 * 64 : 1];           // split-bf16 A operands of W0'^T: the forward normals' adjoint
     __shared__ float w0f[DEC16 ? 32 * 64 : 1];               // fp32 A operands of W0' (fp32 decoder: rows 0-31 of wfwd)
     __shared__ float wfwd[kDecLdsRows * 64];
     // by sorted position: depths, raw densities, omega, n, 1 / r
@@ -50,12 +60,12 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const HfagpRaymarchArgs& a = p.a;
     const int j = lane & 15, g = lane >> 4;
-    const int R = a.res * a.res;
+    const int R = LIST ? p.R : a.res * a.res;
     constexpr int NT = S / 16;
     if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
     build_grad_lds<false>(a, nullptr, w0t, threadIdx.x, kNbWaves * 64);
     if constexpr (DEC16) {
-        build_grad16_lds<false>(a, nullptr, g0img, lane, wave, kNbWaves);
+        if constexpr (A16) build_grad16_lds<false>(a, nullptr, g0img, lane, wave, kNbWaves);
         const float g0 = a.decoder_lr_mul * 0.17677669529663687f;
         for (int i = threadIdx.x; i < 32 * 64; i += kNbWaves * 64) {
             const int l = i & 63, row = i >> 6;              // row = mt * 8 + t
@@ -92,14 +102,24 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
     const size_t plane_stride = (size_t)a.H * a.W * 32;
     const RaySchedule sch = ray_schedule((long long)p.total_rays, wave, kNbWaves);
     for (long long rp = sch.begin; rp < sch.end; rp += sch.stride) {
-        int b, pi, pj;
-        ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
-        const int ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+        int b, pi, pj, ray;
+        float o3[3], d3[3];
+        if constexpr (LIST) {
+            int ray_v;
+            ray_fetch<true>(p, __builtin_amdgcn_readfirstlane((int)rp), R, b, ray_v, o3, d3);
+            ray = __builtin_amdgcn_readfirstlane(ray_v);
+            if (p.t_near) {                         // (wave-uniform: the limit-less list call never enters)
+                const float t_near = p.t_near[ray], t_far = p.t_far[ray];
+                if (!(fabsf(t_near) < INFINITY && fabsf(t_far) < INFINITY && t_far > t_near)) continue;
+            }
+        } else {
+            ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
+            ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+        }
         const float Gh[3] = {g_normal[(size_t)ray * 3], g_normal[(size_t)ray * 3 + 1], g_normal[(size_t)ray * 3 + 2]};
         if (Gh[0] == 0.f && Gh[1] == 0.f && Gh[2] == 0.f) continue;       // (wave-uniform)
         any = true;
-        float o3[3], d3[3];
-        ray_setup(a, b, pi, pj, o3, d3);
+        if constexpr (!LIST) ray_setup(a, b, pi, pj, o3, d3);
         // (twin: normals_load_ray, raymarch_normals_common.h)
         {
             const float* st = a.state + (size_t)ray * (S * HFAGP_RAYMARCH_STATE_FLOATS_PER_SAMPLE);
@@ -135,7 +155,8 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
             else decoder_fwd_lds<true>(wfwd, ln, f, hp, h, sigma, o);
             f32x4 dH[4];
             f32x4 dF2[2];
-            if constexpr (DEC16) decoder_bwd16_lds<false>(wfwd, nullptr, g0img, ln, o, 1.f, hp, dH, dF2);
+            if constexpr (A16) decoder_bwd16_lds<false>(wfwd, nullptr, g0img, ln, o, 1.f, hp, dH, dF2);
+            else if constexpr (DEC16) { decoder_dh_lds<true>(wfwd, ln, hp, dH); w0t_mul(w0t, ln, dH, dF2); }
             else decoder_bwd_lds<false>(wfwd, nullptr, w0t, ln, o, 1.f, hp, dH, dF2);
             float q[3], dq[3];
             sample_point(p, o3, d3, tz, q);
@@ -236,7 +257,8 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
             if constexpr (DEC16) decoder_fwd16_lds<true>(wfwd, ln, f, hp, h, sigma, o);
             else decoder_fwd_lds<true>(wfwd, ln, f, hp, h, sigma, o);
             f32x4 dH[4], av[2];                  // dH = wsig sigmoid(hp); av = a = W0'^T dH (as pass A)
-            if constexpr (DEC16) decoder_bwd16_lds<false>(wfwd, nullptr, g0img, ln, o, 1.f, hp, dH, av);
+            if constexpr (A16) decoder_bwd16_lds<false>(wfwd, nullptr, g0img, ln, o, 1.f, hp, dH, av);
+            else if constexpr (DEC16) { decoder_dh_lds<true>(wfwd, ln, hp, dH); w0t_mul(w0t, ln, dH, av); }
             else decoder_bwd_lds<false>(wfwd, nullptr, w0t, ln, o, 1.f, hp, dH, av);
             f32x4 v[4], x[4];
             w0_mul(w0fwd, ln, u, v);
@@ -280,32 +302,34 @@ raymarch_normals_bwd_kernel(const RayParams p, const float* __restrict__ g_norma
     }
 }
 
-template <int S, bool DEC16, bool PG>
+template <int S, bool DEC16, bool PG, bool LIST>
 static int launch_nb(const RayParams& p, const float* g_normal, float* d_planes, const DecGrads& dg, hipStream_t s) {
     // one round of resident workgroups, each wave walking its run of rays
     static int resident = 0;
     if (resident == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, raymarch_normals_bwd_kernel<S, DEC16, PG>, kNbWaves * 64, 0) != hipSuccess ||
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, raymarch_normals_bwd_kernel<S, DEC16, PG, LIST>, kNbWaves * 64, 0) != hipSuccess ||
             n < 1)
             n = 1;
         resident = n;
     }
     const long long blocks = std::min<long long>(((long long)p.total_rays + kNbWaves - 1) / kNbWaves, (long long)kNumCU * resident);
-    raymarch_normals_bwd_kernel<S, DEC16, PG><<<(unsigned)blocks, kNbWaves * 64, 0, s>>>(p, g_normal, d_planes, dg);
-    return check_launch("raymarch_normals_bwd");
+    raymarch_normals_bwd_kernel<S, DEC16, PG, LIST><<<(unsigned)blocks, kNbWaves * 64, 0, s>>>(p, g_normal, d_planes, dg);
+    return check_launch(LIST ? "raymarch_rays_normals_bwd" : "raymarch_normals_bwd");
 }
 
-template <int S>
+template <int S, bool LIST>
 static int launch_nb_s(const RayParams& p, const float* g_normal, float* d_planes, const DecGrads& dg, bool pg, hipStream_t s) {
-    if (p.a.planes_absmax) return pg ? launch_nb<S, true, true>(p, g_normal, d_planes, dg, s) : launch_nb<S, true, false>(p, g_normal, d_planes, dg, s);
-    return pg ? launch_nb<S, false, true>(p, g_normal, d_planes, dg, s) : launch_nb<S, false, false>(p, g_normal, d_planes, dg, s);
+    if (p.a.planes_absmax)
+        return pg ? launch_nb<S, true, true, LIST>(p, g_normal, d_planes, dg, s) : launch_nb<S, true, false, LIST>(p, g_normal, d_planes, dg, s);
+    return pg ? launch_nb<S, false, true, LIST>(p, g_normal, d_planes, dg, s) : launch_nb<S, false, false, LIST>(p, g_normal, d_planes, dg, s);
 }
 
 }  // namespace hfagp
 
 using namespace hfagp;
 
+#ifndef HFAGP_RAY_LIST_UNIT        // (raymarch_rays_normals.hip compiles this source again for the list entry point alone)
 extern "C" int hfagp_raymarch_normals_bwd(const HfagpRaymarchArgs* fwd, const float* g_normal, float* d_planes, float* d_dec_w0,
                                           float* d_dec_b0, float* d_dec_w1, float* d_dec_b1, void* stream) {
     HFAGP_REQUIRE(fwd && g_normal && d_planes && fwd->state && fwd->planes, HFAGP_EBADARG, "raymarch_normals_bwd: null pointer");
@@ -318,7 +342,30 @@ extern "C" int hfagp_raymarch_normals_bwd(const HfagpRaymarchArgs* fwd, const fl
     const DecGrads dg = {d_dec_w0, d_dec_b0, d_dec_w1, d_dec_b1};
     hipStream_t s = (hipStream_t)stream;
     const int S = fwd->Sc + fwd->Sf;
-    if (S == 96) return launch_nb_s<96>(p, g_normal, d_planes, dg, pg, s);
-    if (S == 64) return launch_nb_s<64>(p, g_normal, d_planes, dg, pg, s);
-    return launch_nb_s<32>(p, g_normal, d_planes, dg, pg, s);
+    if (S == 96) return launch_nb_s<96, false>(p, g_normal, d_planes, dg, pg, s);
+    if (S == 64) return launch_nb_s<64, false>(p, g_normal, d_planes, dg, pg, s);
+    return launch_nb_s<32, false>(p, g_normal, d_planes, dg, pg, s);
 }
+
+#else
+extern "C" int hfagp_raymarch_rays_normals_bwd(const HfagpRayListArgs* a, const HfagpRayLimits* lim, const float* g_normal,
+                                               float* d_planes, float* d_dec_w0, float* d_dec_b0, float* d_dec_w1, float* d_dec_b1,
+                                               void* stream) {
+    HFAGP_REQUIRE(a && g_normal && d_planes && a->base.state, HFAGP_EBADARG, "raymarch_rays_normals_bwd: null pointer");
+    HFAGP_REQUIRE(!lim || (lim->t_near && lim->t_far), HFAGP_EBADARG, "raymarch_rays_normals_bwd: null pointer (limits)");
+    const bool pg = d_dec_w0 || d_dec_b0 || d_dec_w1 || d_dec_b1;
+    HFAGP_REQUIRE(!pg || (d_dec_w0 && d_dec_b0 && d_dec_w1 && d_dec_b1), HFAGP_EBADARG,
+                  "raymarch_rays_normals_bwd: the four decoder gradients go together (all or none)");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->base, p, "raymarch_rays_normals_bwd", &rays, lim != nullptr);
+    if (rc != HFAGP_OK) return rc;
+    if (lim) { p.t_near = lim->t_near; p.t_far = lim->t_far; }
+    const DecGrads dg = {d_dec_w0, d_dec_b0, d_dec_w1, d_dec_b1};
+    hipStream_t s = (hipStream_t)stream;
+    const int S = a->base.Sc + a->base.Sf;
+    if (S == 96) return launch_nb_s<96, true>(p, g_normal, d_planes, dg, pg, s);
+    if (S == 64) return launch_nb_s<64, true>(p, g_normal, d_planes, dg, pg, s);
+    return launch_nb_s<32, true>(p, g_normal, d_planes, dg, pg, s);
+}
+#endif

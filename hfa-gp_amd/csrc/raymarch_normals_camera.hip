@@ -28,10 +28,14 @@ namespace hfagp {
 
 constexpr int kNcWaves = 4;
 
-template <int S, bool DEC16>
-__global__ void __launch_bounds__(kNcWaves * 64, 2)
-raymarch_normals_camera_kernel(const RayParams p, const float* __restrict__ g_normal, float* __restrict__ ray_grad,
-                               const int accumulate) {
+// LIST: the rays of a caller's list (raymarch_common.h ray_fetch; directions as given) and the record split into d_origins /
+// d_directions [B][R][3] (`ray_grad` / `d_dir`: the layout of launch_ray_list_grads, whose output `accumulate` adds to) — for a list
+// the per-ray record IS the answer.  With per-ray limits (RayParams::t_near / t_far) an EMPTY ray (raymarch.hip's predicate) reads
+// nothing of its `state`, which the forward never wrote: six zeros when not accumulating, nothing when accumulating.  The body is
+// shared by the two kernels below.
+template <int S, bool DEC16, bool LIST>
+__device__ __forceinline__ void normals_camera_body(const RayParams& p, const float* __restrict__ g_normal, float* __restrict__ ray_grad,
+                                                    float* __restrict__ d_dir, const int accumulate) {
     __shared__ float w0t[2 * 16 * 64];                       // fp32 A operands of W0'^T (build_grad_lds)
     __shared__ float w0f[DEC16 ? 32 * 64 : 1];               // fp32 A operands of W0' (fp32 decoder: rows 0-31 of wfwd)
     __shared__ float wfwd[kDecLdsRows * 64];
@@ -41,7 +45,7 @@ raymarch_normals_camera_kernel(const RayParams p, const float* __restrict__ g_no
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const HfagpRaymarchArgs& a = p.a;
     const int j = lane & 15, g = lane >> 4;
-    const int R = a.res * a.res;
+    const int R = LIST ? p.R : a.res * a.res;
     constexpr int NT = S / 16;
     if (wave == 0) decoder_images_lds<DEC16>(a, wfwd, lane, j, g);
     build_grad_lds<false>(a, nullptr, w0t, threadIdx.x, kNcWaves * 64);
@@ -68,20 +72,34 @@ raymarch_normals_camera_kernel(const RayParams p, const float* __restrict__ g_no
     const float sxy = sx * hy;
     const RaySchedule sch = ray_schedule((long long)p.total_rays, wave, kNcWaves);
     for (long long rp = sch.begin; rp < sch.end; rp += sch.stride) {
-        int b, pi, pj;
-        ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
-        const int ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
-        float* dst = ray_grad + (size_t)ray * 6;
+        int b, pi, pj, ray;
+        float o3[3], d3[3];
+        bool empty = false;                                               // (LIST with limits; wave-uniform)
+        if constexpr (LIST) {
+            int ray_v;
+            ray_fetch<true>(p, __builtin_amdgcn_readfirstlane((int)rp), R, b, ray_v, o3, d3);
+            ray = __builtin_amdgcn_readfirstlane(ray_v);
+            if (p.t_near) {                         // (wave-uniform: the limit-less list call never enters)
+                const float t_near = p.t_near[ray], t_far = p.t_far[ray];
+                empty = !(fabsf(t_near) < INFINITY && fabsf(t_far) < INFINITY && t_far > t_near);
+            }
+        } else {
+            ray_of(__builtin_amdgcn_readfirstlane((int)rp), a.res, b, pi, pj);
+            ray = __builtin_amdgcn_readfirstlane(b * R + pi * a.res + pj);
+        }
+        float* dst = LIST ? ray_grad + (size_t)ray * 3 : ray_grad + (size_t)ray * 6;
+        float* dst_d = LIST ? d_dir + (size_t)ray * 3 : dst + 3;
         const float Gh[3] = {g_normal[(size_t)ray * 3], g_normal[(size_t)ray * 3 + 1], g_normal[(size_t)ray * 3 + 2]};
-        if (Gh[0] == 0.f && Gh[1] == 0.f && Gh[2] == 0.f) {               // (wave-uniform)
+        if (empty || (Gh[0] == 0.f && Gh[1] == 0.f && Gh[2] == 0.f)) {    // (wave-uniform)
             if (!accumulate && lane == 0) {
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dst[k] = 0.f;
+                for (int k = 0; k < 3; ++k) dst[k] = 0.f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dst_d[k] = 0.f;
             }
             continue;
         }
-        float o3[3], d3[3];
-        ray_setup(a, b, pi, pj, o3, d3);
+        if constexpr (!LIST) ray_setup(a, b, pi, pj, o3, d3);
         normals_load_ray<S>(a.state + (size_t)ray * (S * HFAGP_RAYMARCH_STATE_FLOATS_PER_SAMPLE), lane, ts, ss);
         WAVE_SYNC();
         {
@@ -155,10 +173,14 @@ raymarch_normals_camera_kernel(const RayParams p, const float* __restrict__ g_no
         if (lane == 0) {
             if (accumulate) {
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dst[k] += out[k];
+                for (int k = 0; k < 3; ++k) dst[k] += out[k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dst_d[k] += out[3 + k];
             } else {
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dst[k] = out[k];
+                for (int k = 0; k < 3; ++k) dst[k] = out[k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) dst_d[k] = out[3 + k];
             }
         }
         WAVE_SYNC();       // the next ray overwrites the per-ray tables
@@ -166,19 +188,47 @@ raymarch_normals_camera_kernel(const RayParams p, const float* __restrict__ g_no
 }
 
 template <int S, bool DEC16>
-static int launch_nc(const RayParams& p, const float* g_normal, float* ray_grad, int accumulate, hipStream_t s) {
-    // one round of resident workgroups, each wave walking its run of rays
-    static int resident = 0;
+__global__ void __launch_bounds__(kNcWaves * 64, 2)
+raymarch_normals_camera_kernel(const RayParams p, const float* __restrict__ g_normal, float* __restrict__ ray_grad,
+                               const int accumulate) {
+    normals_camera_body<S, DEC16, false>(p, g_normal, ray_grad, nullptr, accumulate);
+}
+
+// hfagp_raymarch_rays_normals_bwd_rays: one writer per ray, no atomics, no reduction
+template <int S, bool DEC16>
+__global__ void __launch_bounds__(kNcWaves * 64, 2)
+raymarch_normals_camera_rays_kernel(const RayParams p, const float* __restrict__ g_normal, float* __restrict__ d_origins,
+                                    float* __restrict__ d_directions, const int accumulate) {
+    normals_camera_body<S, DEC16, true>(p, g_normal, d_origins, d_directions, accumulate);
+}
+
+// one round of resident workgroups, each wave walking its run of rays
+template <typename Kernel>
+static long long nc_blocks(const RayParams& p, Kernel kernel, int& resident) {
     if (resident == 0) {
         int n = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, raymarch_normals_camera_kernel<S, DEC16>, kNcWaves * 64, 0) != hipSuccess ||
-            n < 1)
-            n = 1;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, kNcWaves * 64, 0) != hipSuccess || n < 1) n = 1;
         resident = n;
     }
-    const long long blocks = std::min<long long>(((long long)p.total_rays + kNcWaves - 1) / kNcWaves, (long long)kNumCU * resident);
+    return std::min<long long>(((long long)p.total_rays + kNcWaves - 1) / kNcWaves, (long long)kNumCU * resident);
+}
+
+template <int S, bool DEC16>
+static int launch_nc(const RayParams& p, const float* g_normal, float* ray_grad, int accumulate, hipStream_t s) {
+    static int resident = 0;
+    const long long blocks = nc_blocks(p, raymarch_normals_camera_kernel<S, DEC16>, resident);
     raymarch_normals_camera_kernel<S, DEC16><<<(unsigned)blocks, kNcWaves * 64, 0, s>>>(p, g_normal, ray_grad, accumulate);
     return check_launch("raymarch_normals_bwd_camera");
+}
+
+template <int S, bool DEC16>
+static int launch_nc_rays(const RayParams& p, const float* g_normal, float* d_origins, float* d_directions, int accumulate,
+                          hipStream_t s) {
+    static int resident = 0;
+    const long long blocks = nc_blocks(p, raymarch_normals_camera_rays_kernel<S, DEC16>, resident);
+    raymarch_normals_camera_rays_kernel<S, DEC16><<<(unsigned)blocks, kNcWaves * 64, 0, s>>>(p, g_normal, d_origins, d_directions,
+                                                                                            accumulate);
+    return check_launch("raymarch_rays_normals_bwd_rays");
 }
 
 template <int S>
@@ -187,10 +237,18 @@ static int launch_nc_s(const RayParams& p, const float* g_normal, float* ray_gra
     return launch_nc<S, false>(p, g_normal, ray_grad, accumulate, s);
 }
 
+template <int S>
+static int launch_nc_rays_s(const RayParams& p, const float* g_normal, float* d_origins, float* d_directions, int accumulate,
+                            hipStream_t s) {
+    if (p.a.planes_absmax) return launch_nc_rays<S, true>(p, g_normal, d_origins, d_directions, accumulate, s);
+    return launch_nc_rays<S, false>(p, g_normal, d_origins, d_directions, accumulate, s);
+}
+
 }  // namespace hfagp
 
 using namespace hfagp;
 
+#ifndef HFAGP_RAY_LIST_UNIT        // (raymarch_rays_normals.hip compiles this source again for the list entry point alone)
 extern "C" int hfagp_raymarch_normals_bwd_camera(const HfagpRaymarchArgs* fwd, const float* g_normal, float* ray_grad, int accumulate,
                                                  float* d_cam2world, float* d_intrinsics, void* stream) {
     HFAGP_REQUIRE(fwd && g_normal && ray_grad && fwd->state && fwd->planes, HFAGP_EBADARG, "raymarch_normals_bwd_camera: null pointer");
@@ -209,3 +267,23 @@ extern "C" int hfagp_raymarch_normals_bwd_camera(const HfagpRaymarchArgs* fwd, c
     launch_camera_reduce(p.a, ray_grad, d_cam2world, d_intrinsics, s);
     return check_launch("raymarch_normals_bwd_camera");
 }
+
+#else
+extern "C" int hfagp_raymarch_rays_normals_bwd_rays(const HfagpRayListArgs* a, const HfagpRayLimits* lim, const float* g_normal,
+                                                    float* d_origins, float* d_directions, int accumulate, void* stream) {
+    HFAGP_REQUIRE(a && g_normal && d_origins && d_directions && a->base.state, HFAGP_EBADARG,
+                  "raymarch_rays_normals_bwd_rays: null pointer");
+    HFAGP_REQUIRE(!lim || (lim->t_near && lim->t_far), HFAGP_EBADARG, "raymarch_rays_normals_bwd_rays: null pointer (limits)");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->base, p, "raymarch_rays_normals_bwd_rays", &rays, lim != nullptr);
+    if (rc != HFAGP_OK) return rc;
+    if (lim) { p.t_near = lim->t_near; p.t_far = lim->t_far; }
+    hipStream_t s = (hipStream_t)stream;
+    const int S = a->base.Sc + a->base.Sf;
+    const int acc = accumulate != 0;
+    if (S == 96) return launch_nc_rays_s<96>(p, g_normal, d_origins, d_directions, acc, s);
+    if (S == 64) return launch_nc_rays_s<64>(p, g_normal, d_origins, d_directions, acc, s);
+    return launch_nc_rays_s<32>(p, g_normal, d_origins, d_directions, acc, s);
+}
+#endif

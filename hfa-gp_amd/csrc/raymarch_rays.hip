@@ -2,7 +2,9 @@
 // of the grid's — raymarch_rays_kernel (raymarch.hip), raymarch_bwd_tiles_kernel / raymarch_bwd_df_kernel <.., LIST>
 // (raymarch_bwd.hip), raymarch_bwd_bins_kernel <.., LIST> (raymarch_rows.hip), raymarch_bwd_rays_kernel (raymarch_camera.hip) — which
 // differ from them in the ray fetch alone (raymarch_common.h ray_fetch).  Here: argument checks and the hand-over to the launchers
-// those units share with their grid entry points.
+// those units share with their grid entry points.  (The normals of a list — hfagp_raymarch_rays_normals / _normals_bwd /
+// _normals_bwd_rays — have their entry points next to their kernels, in raymarch_normals.hip, raymarch_normals_bwd.hip and
+// raymarch_normals_camera.hip, compiled by raymarch_rays_normals.hip.)
 #include "raymarch_common.h"
 
 using namespace hfagp;

@@ -1125,9 +1125,46 @@ class TriPlaneGenerator(nn.Module):
                     decoder_lr_mul=cfg.decoder_lr_mul, plane_axes=ops._plane_axes_id(cfg.plane_axes), white_back=cfg.white_back,
                     decoder_precision=cfg.decoder_precision)
 
+    @staticmethod
+    def _render_rays_empty(b: int, r: int, dev, zero, limits: bool, normals: bool, normal_grad: bool) -> Dict[str, torch.Tensor]:
+        """`render_rays` of no rays (B = 0 or R = 0): the dict of a call with these keywords, nothing launched.  ``zero``: 0.0, or
+        under grad a zero scalar that hangs on the call's inputs and keeps their autograd edges."""
+        feat = torch.zeros(b, r, 32, device=dev) + zero
+        out = {"feature": feat, "rgb": feat[..., :3], "depth": torch.zeros(b, r, device=dev) + zero,
+               "mask": torch.zeros(b, r, device=dev) + zero}
+        if limits:
+            out["valid"] = torch.zeros(b, r, device=dev, dtype=torch.bool)
+        if normals:          # (detached unless normal_grad, as in a call with rays)
+            out["normal"] = torch.zeros(b, r, 3, device=dev) + (zero if normal_grad else 0.0)
+        return out
+
+    def _render_rays_normals_chunked(self, planes, o, d, u_strat, u_imp, planes_absmax, lim: dict, rays: int):
+        """`ops.raymarch_rays` + `ops.raymarch_rays_normals` over chunks of `rays` rays per frame through one state buffer of that
+        size: the per-sample state of the whole list would exceed RAY_STATE_CAP_BYTES.  A list may be cut at any ray; every ray is
+        computed as in the whole-list launch (the decoder's bound on |planes| is the call's, taken once), so the five results —
+        feat, depth (unclamped), wsum, tminmax, normal — equal the unchunked ones bit for bit."""
+        cfg = self.cfg
+        b, r = o.shape[0], o.shape[1]
+        sc, sf = cfg.depth_resolution, cfg.depth_resolution_importance
+        planes_absmax = ops._decoder_bound(planes, cfg.decoder_precision, planes_absmax)
+        u_imp = u_imp.view(b, r, sf)
+        buf = ops.raymarch_rays_state(b, min(rays, r), sc, sf, planes.device)
+        parts = []
+        for r0 in range(0, r, rays):
+            n = min(rays, r - r0)
+            cut = lambda t: t[:, r0:r0 + n].contiguous()      # noqa: E731
+            state = buf.view(-1)[:b * n * (sc + sf) * 35].view(b, n, (sc + sf) * 35)
+            oc, dc, us, ui = cut(o), cut(d), cut(u_strat), cut(u_imp).view(b * n, sf)
+            lc = {k: cut(t) for k, t in lim.items()}
+            out = ops.raymarch_rays(planes, oc, dc, us, ui, planes_absmax=planes_absmax, state=state, **lc, **self._rays_kwargs())
+            parts.append(out + (ops.raymarch_rays_normals(planes, state, ray_origins=oc, ray_directions=dc, u_strat=us, u_imp=ui,
+                                                          planes_absmax=planes_absmax, **lc, **self._rays_kwargs()),))
+        return tuple(torch.cat(t, 1) for t in zip(*parts))
+
     def render_rays(self, ws: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
                     u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
-                    noise_mode: str = "const", t_near=None, t_far=None, ray_limits: Optional[str] = None) -> Dict[str, torch.Tensor]:
+                    noise_mode: str = "const", t_near=None, t_far=None, ray_limits: Optional[str] = None, normals: bool = False,
+                    normal_grad: bool = False, normal_ray_grad: bool = False) -> Dict[str, torch.Tensor]:
         """The renderer of `synthesis` on caller-given rays: ray_origins / ray_directions [B,R,3] in world units, R arbitrary — a
         crop or zoomed window (`cam_utils.ray_grid(c, res, window=)`), several cameras of one identity as one longer list in that
         frame (`torch.cat` along dim 1), random ray batches, or any camera model written in torch.  Directions are taken as given,
@@ -1147,9 +1184,20 @@ class TriPlaneGenerator(nn.Module):
         call's clamp range — what EG3D's zero-opacity ray gets (0 if no ray is valid); nothing in the dict is NaN or inf.  The limits
         are NOT differentiated (a limit that requires grad raises; "box" computes them from detached rays): the rays' gradient is
         the derivative with the limits held fixed — EG3D's autograd also moves the sample positions through the box intersection;
-        leaving that term out is deliberate, as for the importance depths — and an empty ray gets exactly zero gradient."""
+        leaving that term out is deliberate, as for the importance depths — and an empty ray gets exactly zero gradient.
+        Surface normals, with the keywords of `synthesis`: `normals=True` adds 'normal' [B,R,3], per ray N = Σ_s ω_s n_s — world
+        space, not normalised, ‖N‖ ≤ 'mask', `white_back` does not enter ('image_normal' of `synthesis`, per ray); exactly 0 for an
+        empty ray.  One more launch (ops.raymarch_rays_normals) on the per-sample state of the march, which a call whose state
+        exceeds RAY_STATE_CAP_BYTES runs in chunks of rays under no_grad.  It is detached unless `normal_grad=True` (which implies
+        `normals`): 'normal' is then differentiable w.r.t. `ws` and the generator parameters that require grad, the four decoder
+        tensors included, at one more backward launch, and only when the loss uses it; above the cap that raises RuntimeError.  The
+        rays get the normal term's gradient only with `normal_ray_grad=True` (which implies `normal_grad`) — rays that require
+        grad raise NotImplementedError without it, as a label does in `synthesis(normal_grad=True)` without
+        `normal_camera_grad=True`.  The sample depths and the limits carry no gradient here either."""
         if noise_mode != "const":
             raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
+        normal_grad = bool(normal_grad or normal_ray_grad)
+        normals = bool(normals or normal_grad)
         if ray_limits is not None and ray_limits != "box":
             raise ValueError(f"TriPlaneGenerator.render_rays: ray_limits must be None or 'box', got {ray_limits!r}")
         if (t_near is None) != (t_far is None):
@@ -1163,6 +1211,11 @@ class TriPlaneGenerator(nn.Module):
                 raise TypeError(f"TriPlaneGenerator.render_rays: {name} must be a floating-point tensor, got {t.dtype}")
         if ray_origins.shape != ray_directions.shape:
             raise ValueError(f"ray_directions {tuple(ray_directions.shape)} must match ray_origins {tuple(ray_origins.shape)}")
+        if normal_grad and not normal_ray_grad and torch.is_grad_enabled() and (ray_origins.requires_grad or
+                                                                                 ray_directions.requires_grad):
+            raise NotImplementedError("TriPlaneGenerator.render_rays(normal_grad=True): the rays' gradient of the normal term is opt-in "
+                                      "(ray_origins / ray_directions require grad): pass normal_ray_grad=True for it, detach the rays, "
+                                      "or use normals=True for a detached map")
         self._query_guard("render_rays", ws, differentiable=True)
         if not (ray_origins.is_cuda and ray_directions.is_cuda):
             raise RuntimeError("TriPlaneGenerator.render_rays: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
@@ -1196,12 +1249,12 @@ class TriPlaneGenerator(nn.Module):
                                             any(p.requires_grad for p in params))
         if b == 0 or r == 0:
             zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0      # keeps the autograd edges
-            feat = torch.zeros(b, r, 32, device=dev) + zero
-            out = {"feature": feat, "rgb": feat[..., :3], "depth": torch.zeros(b, r, device=dev) + zero,
-                   "mask": torch.zeros(b, r, device=dev) + zero}
-            if limits is not None:
-                out["valid"] = torch.zeros(b, r, device=dev, dtype=torch.bool)
-            return out
+            return self._render_rays_empty(b, r, dev, zero, limits is not None, normals, normal_grad)
+        state_bytes = b * r * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
+        if grad and normal_grad and state_bytes > RAY_STATE_CAP_BYTES:
+            raise RuntimeError(f"TriPlaneGenerator.render_rays(normal_grad=True): the backward of 'normal' reads the ray marcher's "
+                               f"per-sample state, {state_bytes} bytes for {b} x {r} rays, above RAY_STATE_CAP_BYTES = "
+                               f"{RAY_STATE_CAP_BYTES}; {RAY_STATE_CAP_BYTES // (state_bytes // (b * r))} rays fit")
         if limits == "box":
             with torch.no_grad():
                 limits = ops.ray_limits_box(ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous(),
@@ -1215,17 +1268,37 @@ class TriPlaneGenerator(nn.Module):
             if getattr(self, "_grad_sink", None) is not None or getattr(self, "_grad_inplace", False):
                 raise RuntimeError("TriPlaneGenerator.render_rays under grad inside a trainer step scope: its backward is a second "
                                    "backbone pass and would release every parameter to the gradient sink twice")
-            from .autograd import RenderRaysFn
-            feat, depth, mask = RenderRaysFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits, *params)
+            if normals:
+                from .autograd import RenderRaysNormalFn
+                feat, depth, mask, normal = RenderRaysNormalFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits,
+                                                                     normal_ray_grad, *params)
+                if not normal_grad:
+                    normal = normal.detach()
+            else:
+                from .autograd import RenderRaysFn
+                feat, depth, mask = RenderRaysFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits, *params)
         else:
             with torch.no_grad():
                 planes, pam = self._query_planes(ws)
                 lim = {} if limits is None else dict(t_near=limits[0], t_far=limits[1])
-                feat, depth, mask, tmm = ops.raymarch_rays(planes, ray_origins.detach().float().contiguous(),
-                                                           ray_directions.detach().float().contiguous(), u_strat, u_imp,
-                                                           planes_absmax=pam, **lim, **self._rays_kwargs())
+                o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
+                if normals and state_bytes > RAY_STATE_CAP_BYTES:        # above the cap: march and take the normals in ray chunks
+                    feat, depth, mask, tmm, normal = self._render_rays_normals_chunked(
+                        planes, o, d, u_strat, u_imp, pam, lim, max(1, RAY_STATE_CAP_BYTES // (state_bytes // r)))
+                else:
+                    state = None
+                    if normals:
+                        state = ops.raymarch_rays_state(b, r, cfg.depth_resolution, cfg.depth_resolution_importance, dev)
+                    feat, depth, mask, tmm = ops.raymarch_rays(planes, o, d, u_strat, u_imp, planes_absmax=pam, state=state, **lim,
+                                                               **self._rays_kwargs())
+                    if normals:
+                        normal = self._timed("raymarch_rays_normals", float(b), ops.raymarch_rays_normals, planes, state,
+                                             ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=pam, **lim,
+                                             **self._rays_kwargs())
                 depth = ops.depth_clamp_(depth, tmm) if limits is None else ops.depth_clamp_(depth, tmm, empty_rays=True)
         out = {"feature": feat, "rgb": feat[..., :3], "depth": depth, "mask": mask}
+        if normals:
+            out["normal"] = normal
         if limits is not None:
             from .cam_utils import ray_limits_valid
             out["valid"] = ray_limits_valid(*limits)

@@ -967,6 +967,110 @@ def raymarch_normals_bwd_camera(g_normal: torch.Tensor, planes: torch.Tensor, st
     return d_c2w, d_intr, ray_grad
 
 
+def _rays_normals_args(who: str, planes, state, g_normal, ray_origins, ray_directions, u_strat, u_imp, t_near, t_far, scene):
+    """The RayListArgs of the three list normals ops (`_ray_list_args`), the limits and (B, R); owns the checks of `state` and
+    ``g_normal`` (None for the forward)."""
+    if state is None:
+        raise RuntimeError(f"{who}: state must be the `raymarch_state` buffer the forward call filled, got None")
+    a = L.RayListArgs()
+    b, _, _, r, _, _, lim = _ray_list_args(who, a, planes, ray_origins, ray_directions, u_strat, u_imp, state=state, t_near=t_near,
+                                           t_far=t_far, **scene)
+    if g_normal is not None and _chk(g_normal, f"{who}: g_normal").shape != (b, r, 3):
+        raise RuntimeError(f"{who}: g_normal must be [B, R, 3] = [{b}, {r}, 3], got {tuple(g_normal.shape)}")
+    return a, C.byref(lim) if lim is not None else None, b, r
+
+
+def raymarch_rays_normals(planes: torch.Tensor, state: torch.Tensor, *, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
+                          u_strat: torch.Tensor, u_imp: torch.Tensor, dec_w0: torch.Tensor, dec_b0: torch.Tensor,
+                          dec_w1: torch.Tensor, dec_b1: torch.Tensor, ray_start: float, ray_end: float, box_warp: float,
+                          decoder_lr_mul: float, plane_axes: int, white_back: bool, decoder_precision: str,
+                          planes_absmax: Optional[torch.Tensor] = None, t_near: Optional[torch.Tensor] = None,
+                          t_far: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`raymarch_normals` on a ray list (hfagp_raymarch_rays_normals): per-ray surface normals [B,R,3] of the
+    `raymarch_rays(..., state=state)` call with the same arguments — N = Σ_s ω_s n_s at the samples o + t·d, world space, not
+    normalised, ‖N‖ ≤ wsum; `white_back` does not enter.  ``state``: `raymarch_rays_state`.  ``t_near`` / ``t_far`` [B,R]: that
+    call's per-ray limits; an EMPTY ray (limits not finite, or far ≤ near) has no state and gets exactly (0, 0, 0).  The result
+    carries no gradient (its backward is `raymarch_rays_normals_bwd`).  No atomics: two calls return the same bits."""
+    who = "raymarch_rays_normals"
+    a, lim, b, r = _rays_normals_args(who, planes, state, None, ray_origins, ray_directions, u_strat, u_imp, t_near, t_far, dict(
+        dec_w0=dec_w0, dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, ray_start=ray_start, ray_end=ray_end, box_warp=box_warp,
+        decoder_lr_mul=decoder_lr_mul, plane_axes=plane_axes, white_back=white_back, decoder_precision=decoder_precision,
+        planes_absmax=planes_absmax))
+    normal = torch.empty(b, r, 3, device=planes.device, dtype=torch.float32)
+    if b * r == 0:
+        return normal
+    L.check(L.lib().hfagp_raymarch_rays_normals(C.byref(a), lim, _ptr(normal), _stream()), who)
+    return normal
+
+
+def raymarch_rays_normals_bwd(g_normal: torch.Tensor, planes: torch.Tensor, state: torch.Tensor, *, ray_origins: torch.Tensor,
+                              ray_directions: torch.Tensor, u_strat: torch.Tensor, u_imp: torch.Tensor, dec_w0: torch.Tensor,
+                              dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, ray_start: float, ray_end: float,
+                              box_warp: float, decoder_lr_mul: float, plane_axes: int, white_back: bool, decoder_precision: str,
+                              planes_absmax: Optional[torch.Tensor] = None, t_near: Optional[torch.Tensor] = None,
+                              t_far: Optional[torch.Tensor] = None, d_planes: Optional[torch.Tensor] = None,
+                              decoder_grads: bool = False, dec_out=None):
+    """Backward of `raymarch_rays_normals(planes, state, ...)` (hfagp_raymarch_rays_normals_bwd) → ``(d_planes, dec)``: what
+    `raymarch_normals_bwd` is to `raymarch_normals`, with the same ``d_planes`` / ``decoder_grads`` / ``dec_out`` keywords — both
+    ACCUMULATED into, and a ``d_planes`` shared with `raymarch_rays_bwd` must have been through that call FIRST (it overwrites
+    plane 2 on mirrored planes).  ``g_normal`` [B,R,3]: dL/d normal.  A ray whose ``g_normal`` is exactly zero touches nothing, and
+    neither does an empty ray of ``t_near`` / ``t_far`` (its g_normal is not read); the limits and the sample depths carry no
+    gradient.  The other keywords are the forward's; pass its ``planes_absmax``."""
+    who = "raymarch_rays_normals_bwd"
+    a, lim, b, r = _rays_normals_args(who, planes, state, g_normal, ray_origins, ray_directions, u_strat, u_imp, t_near, t_far, dict(
+        dec_w0=dec_w0, dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, ray_start=ray_start, ray_end=ray_end, box_warp=box_warp,
+        decoder_lr_mul=decoder_lr_mul, plane_axes=plane_axes, white_back=white_back, decoder_precision=decoder_precision,
+        planes_absmax=planes_absmax))
+    if d_planes is None:
+        d_planes = torch.zeros_like(planes)
+    elif _chk(d_planes, f"{who}: d_planes").shape != planes.shape:
+        raise RuntimeError(f"{who}: d_planes must be shaped like planes {tuple(planes.shape)}, got {tuple(d_planes.shape)}")
+    out = types.SimpleNamespace(d_dec_w0=None, d_dec_b0=None, d_dec_w1=None, d_dec_b1=None)      # (the entry takes them one by one)
+    dec = _dec_grad_out(who, out, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_grads, dec_out)
+    if b * r == 0:
+        return d_planes, dec
+    L.check(L.lib().hfagp_raymarch_rays_normals_bwd(C.byref(a), lim, _ptr(g_normal), _ptr(d_planes), out.d_dec_w0, out.d_dec_b0,
+                                                    out.d_dec_w1, out.d_dec_b1, _stream()), who)
+    return d_planes, dec
+
+
+def raymarch_rays_normals_bwd_rays(g_normal: torch.Tensor, planes: torch.Tensor, state: torch.Tensor, *, d_origins=None,
+                                   d_directions=None, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
+                                   u_strat: torch.Tensor, u_imp: torch.Tensor, dec_w0: torch.Tensor, dec_b0: torch.Tensor,
+                                   dec_w1: torch.Tensor, dec_b1: torch.Tensor, ray_start: float, ray_end: float, box_warp: float,
+                                   decoder_lr_mul: float, plane_axes: int, white_back: bool, decoder_precision: str,
+                                   planes_absmax: Optional[torch.Tensor] = None, t_near: Optional[torch.Tensor] = None,
+                                   t_far: Optional[torch.Tensor] = None):
+    """The rays' gradient of `raymarch_rays_normals(planes, state, ...)` (hfagp_raymarch_rays_normals_bwd_rays) →
+    ``(d origins, d directions)``, each [B,R,3]: the per-ray record of `raymarch_normals_bwd_camera`, which for a list is the
+    answer (no reduction).  ``g_normal`` [B,R,3]: dL/d normal.
+
+      * ``d_origins`` / ``d_directions`` (both or neither): the [B,R,3] tensors `raymarch_rays_bwd_rays` returned, which the normal
+        term is ADDED to (and which are returned); None = fresh tensors that are written.
+    A ray whose ``g_normal`` is exactly zero, and an empty ray of ``t_near`` / ``t_far``, add nothing (write zeros into fresh
+    tensors).  The derivative holds the limits and the sample depths fixed.  No atomics: two calls return the same bits.  The other
+    keywords are the forward's; pass its ``planes_absmax``."""
+    who = "raymarch_rays_normals_bwd_rays"
+    a, lim, b, r = _rays_normals_args(who, planes, state, g_normal, ray_origins, ray_directions, u_strat, u_imp, t_near, t_far, dict(
+        dec_w0=dec_w0, dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, ray_start=ray_start, ray_end=ray_end, box_warp=box_warp,
+        decoder_lr_mul=decoder_lr_mul, plane_axes=plane_axes, white_back=white_back, decoder_precision=decoder_precision,
+        planes_absmax=planes_absmax))
+    if (d_origins is None) != (d_directions is None):
+        raise RuntimeError(f"{who}: d_origins and d_directions go together (both or neither)")
+    accumulate = d_origins is not None
+    if not accumulate:
+        d_origins = torch.empty(b, r, 3, device=planes.device, dtype=torch.float32)
+        d_directions = torch.empty(b, r, 3, device=planes.device, dtype=torch.float32)
+    for name, t in (("d_origins", d_origins), ("d_directions", d_directions)):
+        if _chk(t, f"{who}: {name}").shape != (b, r, 3):
+            raise RuntimeError(f"{who}: {name} must be [B, R, 3] = [{b}, {r}, 3], got {tuple(t.shape)}")
+    if b * r == 0:
+        return d_origins, d_directions
+    L.check(L.lib().hfagp_raymarch_rays_normals_bwd_rays(C.byref(a), lim, _ptr(g_normal), _ptr(d_origins), _ptr(d_directions),
+                                                         int(accumulate), _stream()), who)
+    return d_origins, d_directions
+
+
 def planes_query(planes: torch.Tensor, coords: Optional[torch.Tensor] = None, *, grid=None, dec_w0: torch.Tensor,
                  dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, box_warp: float, plane_axes,
                  decoder_lr_mul: float, decoder_precision: str, planes_absmax: Optional[torch.Tensor] = None,

@@ -34,6 +34,8 @@
  *                              density gradient of every sample composited with MipRayMarcher2's weights)
  *   hfagp_raymarch_normals_bwd <- (none either: what autograd would do with a normal-map loss on such a render)
  *   hfagp_raymarch_normals_bwd_camera <- (none either: the same loss's gradient w.r.t. the camera label)
+ *   hfagp_raymarch_rays_normals / _normals_bwd / _normals_bwd_rays <- (none either: the three above on explicit ray lists, with
+ *                              optional per-ray depth limits)
  *   hfagp_depth_clamp       <- MipRayMarcher2's torch.clamp(depth, min sample depth, max sample depth) over the batch, one launch (ABI 10)
  *   hfagp_resize_aa_fwd / _bwd <- SuperresolutionHybrid8XDC.forward's antialiased bilinear F.interpolate of rgb and x to its input
  *                              resolution (synthesis(neural_rendering_resolution=N), N != the configured one) and its autograd
@@ -881,6 +883,30 @@ int hfagp_raymarch_rays_limits_bwd(const HfagpRayListBwdArgs* a, const HfagpRayL
 /* (reads the depths from the records of hfagp_raymarch_rays_limits_bwd; lim is checked, its arrays are not read)               */
 int hfagp_raymarch_rays_limits_bwd_rays(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim,
                                         float* d_origins, float* d_directions, void* stream);
+
+/* ------------------------------------------------------------------ surface normals along ray lists (additive to ABI 15)
+ * hfagp_raymarch_normals, hfagp_raymarch_normals_bwd and the per-ray part of hfagp_raymarch_normals_bwd_camera on the rays of a
+ * list: the formulas are those entries', with sample s of ray i at origin_i + t_s * direction_i (directions as given) and R rays
+ * per frame.  list->base.state is the state hfagp_raymarch_rays_fwd / hfagp_raymarch_rays_limits_fwd filled on the same list
+ * ([B][R][(Sc + Sf) * HFAGP_RAYMARCH_STATE_FLOATS_PER_SAMPLE]); the forward's outputs in `base` are not read.  The sample depths
+ * and the limits carry no gradient.  (One difference in arithmetic: with the 16-bit decoder hfagp_raymarch_rays_normals_bwd forms
+ * a = W0'^T dH in fp32, as hfagp_raymarch_normals_bwd_camera does, not from split-bf16 parts as hfagp_raymarch_normals_bwd.)
+ * lim: NULL = the list was marched on the config's [ray_start, ray_end]; else the limits of that forward call, and a ray that is
+ * EMPTY by them (see HfagpRayLimits) has no state: nothing of it is read,
+ *   hfagp_raymarch_rays_normals            writes three zeros for it,
+ *   hfagp_raymarch_rays_normals_bwd        skips it (its g_normal is not read),
+ *   hfagp_raymarch_rays_normals_bwd_rays   writes six zeros for it, or leaves its six floats alone when accumulating.
+ * normal [B][R][3]: written.  d_planes and the four decoder gradients (all or none): ACCUMULATED into, as in the grid entry — after
+ * hfagp_raymarch_rays_bwd where they share d_planes (that call overwrites plane 2 on mirrored planes).  d_origins, d_directions
+ * [B][R][3] (the layout of hfagp_raymarch_rays_bwd_rays): written, or with accumulate != 0 added to, so that the normal term joins
+ * the colour term's; no reduction follows.  One writer per ray in the first and the third: two calls give the same bits.
+ * HFAGP_EBADARG, nothing launched: list, its state or an output NULL; lim non-NULL with a NULL member; one decoder gradient without
+ * the others; then the checks of hfagp_raymarch_rays_fwd (with lim: minus ray_end > ray_start).                                */
+int hfagp_raymarch_rays_normals(const HfagpRayListArgs* list, const HfagpRayLimits* lim, float* normal /* [B][R][3] */, void* stream);
+int hfagp_raymarch_rays_normals_bwd(const HfagpRayListArgs* list, const HfagpRayLimits* lim, const float* g_normal /* [B][R][3] */,
+                                    float* d_planes, float* d_dec_w0, float* d_dec_b0, float* d_dec_w1, float* d_dec_b1, void* stream);
+int hfagp_raymarch_rays_normals_bwd_rays(const HfagpRayListArgs* list, const HfagpRayLimits* lim, const float* g_normal /* [B][R][3] */,
+                                         float* d_origins, float* d_directions, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------ antialiased resample (additive to ABI 15)
  * SuperresolutionHybrid8XDC's F.interpolate(mode='bilinear', align_corners=False, antialias=True) of the feature image and the
