@@ -192,6 +192,10 @@ class RayLimits(C.Structure):
     _fields_ = [("t_near", C.c_void_p), ("t_far", C.c_void_p)]
 
 
+class RaySamples(C.Structure):
+    _fields_ = [("weights", C.c_void_p), ("depths", C.c_void_p)]
+
+
 class ResizeAaArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("src", "dst", "add_nchw3", "table_h", "table_w")] + \
         [(n, C.c_int32) for n in ("B", "Hi", "Wi", "Ho", "Wo", "C", "kmax")]
@@ -257,6 +261,9 @@ SYMBOLS = {
                                                  C.c_void_p]),
     "hfagp_raymarch_rays_limits_bwd_rays": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RayLimits), C.c_void_p, C.c_void_p,
                                                       C.c_void_p]),
+    "hfagp_raymarch_rays_samples_fwd": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits), C.POINTER(RaySamples), C.c_void_p]),
+    "hfagp_raymarch_rays_samples_bwd": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RayLimits), C.POINTER(RaymarchGeomGrads),
+                                                  C.c_void_p, C.c_void_p]),
     "hfagp_raymarch_rays_normals": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits), C.c_void_p, C.c_void_p]),
     "hfagp_raymarch_rays_normals_bwd": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits)] + [C.c_void_p] * 7),
     "hfagp_raymarch_rays_normals_bwd_rays": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits), C.c_void_p, C.c_void_p, C.c_void_p,

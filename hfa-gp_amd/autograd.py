@@ -715,6 +715,12 @@ class RenderRaysFn(torch.autograd.Function):
     zero gradient and the g_depth it receives is dropped."""
     @staticmethod
     def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params):
+        return RenderRaysFn._forward(ctx, False, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params)
+
+    @staticmethod
+    def _forward(ctx, samples, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params):
+        """``samples`` (RenderRaysSamplesFn): the launch is ops.raymarch_rays(samples=True) and two more results follow the three —
+        sample_weights [B,R,S-1] and sample_depths [B,R,S]."""
         from .generator import RAY_STATE_CAP_BYTES
         ws_c = ws.detach().float().contiguous()
         o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
@@ -727,8 +733,9 @@ class RenderRaysFn(torch.autograd.Function):
             # (the per-sample results for the compositing adjoint, as a differentiated `synthesis` keeps them; skipped above the cap)
             state = ops.raymarch_rays_state(b, r, sc, sf, planes.device) if b * r * (sc + sf) * 140 <= RAY_STATE_CAP_BYTES else None
             lim = {} if limits is None else dict(t_near=limits[0], t_far=limits[1])
-            feat, depth, wsum, tmm = gen._timed("raymarch_rays", float(b), ops.raymarch_rays, planes, o, d, u_strat, u_imp,
-                                                planes_absmax=pam, state=state, **lim, **gen._rays_kwargs())
+            smp = dict(samples=True) if samples else {}
+            feat, depth, wsum, tmm, *ws_ts = gen._timed("raymarch_rays", float(b), ops.raymarch_rays, planes, o, d, u_strat, u_imp,
+                                                        planes_absmax=pam, state=state, **lim, **smp, **gen._rays_kwargs())
             if limits is None:
                 depth_range = ops.depth_range(tmm)
                 depth = ops.depth_clamp_(depth, tmm)
@@ -742,17 +749,21 @@ class RenderRaysFn(torch.autograd.Function):
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape, ctx.ray_dtypes = ws.shape, (ray_origins.dtype, ray_directions.dtype)
         ctx.set_materialize_grads(False)
-        return feat, depth, wsum
+        return (feat, depth, wsum) + tuple(ws_ts)
 
     @staticmethod
     @torch.no_grad()
     def backward(ctx, g_feat, g_depth, g_wsum):
+        return RenderRaysFn._backward(ctx, g_feat, g_depth, g_wsum)
+
+    @staticmethod
+    def _backward(ctx, g_feat, g_depth, g_wsum, g_weights=None):
         gen = ctx.gen
         if ctx.tape is None:
             raise RuntimeError("TriPlaneGenerator.render_rays: backward called a second time — the saved activations are released "
                                "by the first backward pass (retain_graph is not supported)")
         none = (None,) * (7 + len(ctx.params))
-        if g_feat is None and g_depth is None and g_wsum is None:
+        if g_feat is None and g_depth is None and g_wsum is None and g_weights is None:
             return none
         planes = ctx.planes
         b, dev = planes.shape[0], planes.device
@@ -766,6 +777,8 @@ class RenderRaysFn(torch.autograd.Function):
             geom.update(g_depth=g_depth.float().reshape(b, r).contiguous(), depth_range=ctx.depth_range)
         if g_wsum is not None:
             geom.update(g_wsum=g_wsum.float().reshape(b, r).contiguous())
+        if g_weights is not None:        # (RenderRaysSamplesFn; the records carry the term on to the rays' pass)
+            geom.update(g_weights=g_weights.float().reshape(b, r, -1).contiguous())
         need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         rec_out = [] if need_rays else None
         rb = gen._timed("raymarch_rays_bwd", float(b), ops.raymarch_rays_bwd, g_feat, planes, o, d, u_strat, u_imp,
@@ -799,7 +812,13 @@ class RenderRaysNormalFn(torch.autograd.Function):
     then the one backbone backward.  A loss that ignores the normals runs RenderRaysFn's backward as it stands."""
     @staticmethod
     def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad, *params):
-        feat, depth, wsum = RenderRaysFn.forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params)
+        return RenderRaysNormalFn._forward(ctx, False, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad,
+                                           *params)
+
+    @staticmethod
+    def _forward(ctx, samples, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad, *params):
+        feat, depth, wsum, *ws_ts = RenderRaysFn._forward(ctx, samples, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits,
+                                                          *params)
         (o, d), b = ctx.rays, ws.shape[0]
         with torch.no_grad():
             if ctx.state is None:        # above RAY_STATE_CAP_BYTES (a detached map: render_rays refuses normal_grad there)
@@ -812,13 +831,17 @@ class RenderRaysNormalFn(torch.autograd.Function):
                                     ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=ctx.pam, **ctx.lim,
                                     **gen._rays_kwargs())
         ctx.normal_ray_grad = bool(normal_ray_grad)
-        return feat, depth, wsum, normal
+        return (feat, depth, wsum, normal) + tuple(ws_ts)
 
     @staticmethod
     @torch.no_grad()
     def backward(ctx, g_feat, g_depth, g_wsum, g_normal):
+        return RenderRaysNormalFn._backward(ctx, g_feat, g_depth, g_wsum, g_normal)
+
+    @staticmethod
+    def _backward(ctx, g_feat, g_depth, g_wsum, g_normal, g_weights=None):
         if g_normal is None:             # the loss did not use 'normal': no launch of its own
-            grads = RenderRaysFn.backward(ctx, g_feat, g_depth, g_wsum)
+            grads = RenderRaysFn._backward(ctx, g_feat, g_depth, g_wsum, g_weights)
             return grads[:7] + (None,) + grads[7:]
         gen = ctx.gen
         if ctx.tape is None:
@@ -840,6 +863,8 @@ class RenderRaysNormalFn(torch.autograd.Function):
             geom.update(g_depth=g_depth.float().reshape(b, r).contiguous(), depth_range=ctx.depth_range)
         if g_wsum is not None:
             geom.update(g_wsum=g_wsum.float().reshape(b, r).contiguous())
+        if g_weights is not None:        # the weight term goes with the colour term's launch, which then runs for it alone too
+            geom.update(g_weights=g_weights.float().reshape(b, r, -1).contiguous())
         colour = g_feat is not None or bool(geom)
         need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         d_planes = dec = None
@@ -872,3 +897,38 @@ class RenderRaysNormalFn(torch.autograd.Function):
         ctx.tape = ctx.planes = ctx.state = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
         return (d_ws, d_o, d_d, None, None, None, None, None) + pgrads
+
+
+class RenderRaysSamplesFn(torch.autograd.Function):
+    """`TriPlaneGenerator.render_rays(samples=True)` under grad: RenderRaysFn with two more outputs, sample_weights [B,R,S-1] (the
+    compositing weights w_e = alpha_e T_e of the intervals between the depth-sorted samples) and sample_depths [B,R,S] (marked
+    non-differentiable: importance depths are detached as in EG3D, stratified ones are constants).  The gradient of sample_weights
+    is one more addend of pass 1's adjoint in the one ops.raymarch_rays_bwd launch (g_weights=), which runs even when nothing else
+    carries a gradient; the rays' pass reads that launch's records, so the rays get the term with no launch of its own."""
+    @staticmethod
+    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params):
+        out = RenderRaysFn._forward(ctx, True, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params)
+        ctx.mark_non_differentiable(out[4])
+        return out
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_feat, g_depth, g_wsum, g_weights, _g_depths):
+        return RenderRaysFn._backward(ctx, g_feat, g_depth, g_wsum, g_weights)
+
+
+class RenderRaysNormalSamplesFn(torch.autograd.Function):
+    """`render_rays(samples=True)` together with `normals=` / `normal_grad=` / `normal_ray_grad=`: RenderRaysNormalFn with the two
+    outputs of RenderRaysSamplesFn behind 'normal'.  The weight gradient joins the colour term's launch (ops.raymarch_rays_bwd),
+    which precedes the normal term's as in RenderRaysNormalFn."""
+    @staticmethod
+    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad, *params):
+        out = RenderRaysNormalFn._forward(ctx, True, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad,
+                                          *params)
+        ctx.mark_non_differentiable(out[5])
+        return out
+
+    @staticmethod
+    @torch.no_grad()
+    def backward(ctx, g_feat, g_depth, g_wsum, g_normal, g_weights, _g_depths):
+        return RenderRaysNormalFn._backward(ctx, g_feat, g_depth, g_wsum, g_normal, g_weights)

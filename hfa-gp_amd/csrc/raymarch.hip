@@ -56,6 +56,9 @@ struct WaveLds {
 // the one difference is the fetch (raymarch_common.h ray_fetch), so the body is shared and the two kernels below instantiate it.
 // A list may carry per-ray depth limits (RayParams::t_near / t_far, hfagp.h HfagpRayLimits; null otherwise): they replace the
 // config's interval in the stratified depths, and a ray without a valid interval is skipped — both under `if constexpr (LIST)`.
+// A list may also ask for the per-sample results (RayParams::samples_w / samples_t, hfagp.h HfagpRaySamples): the forward stores the
+// compositing weights and the sorted depths it composites with, and pass 1 of the backward takes their gradient
+// (RayParams::g_weights) as one more addend of its adjoint — under `if constexpr (LIST)` as well, behind wave-uniform null tests.
 template <int NC, int NF, bool GRADS, bool DEC16, bool FROM_STATE, bool LEGACY_TAPS, bool LIST>
 __device__ __forceinline__ void raymarch_body(const RayParams& p) {
     static_assert(!FROM_STATE || GRADS, "the saved state is consumed by the backward pass");
@@ -130,6 +133,14 @@ __device__ __forceinline__ void raymarch_body(const RayParams& p) {
                             a.wsum[ray] = 0.f;
                             a.tminmax[2 * (size_t)ray] = INFINITY;
                             a.tminmax[2 * (size_t)ray + 1] = -INFINITY;
+                        }
+                        if (p.samples_w) {            // no interval, no sample: zeros (not inf: w * t stays finite in a caller's loss)
+                            float* sw = p.samples_w + (size_t)ray * (S - 1);
+                            float* st = p.samples_t + (size_t)ray * S;
+                            if (lane < S - 1) sw[lane] = 0.f;
+                            if (lane + 64 < S - 1) sw[lane + 64] = 0.f;
+                            if (lane < S) st[lane] = 0.f;
+                            if (lane + 64 < S) st[lane + 64] = 0.f;
                         }
                     }
                     continue;
@@ -439,10 +450,23 @@ __device__ __forceinline__ void raymarch_body(const RayParams& p) {
             if (lane == 0) p1 = w0_63;
             if (lane < S) lds.om[lds.sid[lane]] = 0.5f * (p0 + w0);
             if (lane + 64 < S) lds.om[lds.sid[lane + 64]] = 0.5f * (p1 + w1);
+            if constexpr (LIST && !GRADS) {
+                // per-sample outputs (hfagp.h HfagpRaySamples): the weights composited with above and the sorted depths they belong
+                // to, by sorted position; consecutive lanes, consecutive floats
+                if (p.samples_w) {                  // (wave-uniform: no other list call enters)
+                    float* sw = p.samples_w + (size_t)ray * (S - 1);
+                    float* st = p.samples_t + (size_t)ray * S;
+                    if (lane < S - 1) sw[lane] = w0;
+                    if (lane + 64 < S - 1) sw[lane + 64] = w1;
+                    if (lane < S) st[lane] = lds.ts[lane];
+                    if (lane + 64 < S) st[lane + 64] = lds.ts[lane + 64];
+                }
+            }
             if constexpr (GRADS) {
                 // adjoint of the compositing.  rgb = sum_e w_e cbar_e (+ white_back term),
                 //   G_e = g . cbar_e - wb * sum(g),   dL/dalpha_e = G_e T_e - (sum_{k>e} G_k w_k) / (1 - alpha_e + eps)
                 //   with depth / opacity gradients (hfagp.h HfagpRaymarchGeomGrads):  G_e += gamma_W + gamma_d (tbar_e - d) / W
+                //   with a per-sample weight gradient (hfagp.h HfagpRaySamples, lists only):  G_e += g_weights[e]
                 //   dalpha/dsigma~ = delta (1 - alpha),  dsigma~/dsigmabar = sigmoid(sigmabar - 1)
                 const float wb = a.white_back ? gsum2 : 0.f;
                 float G[2];
@@ -465,6 +489,16 @@ __device__ __forceinline__ void raymarch_body(const RayParams& p) {
 #pragma unroll
                     for (int k = 0; k < 2; ++k)
                         if (lane + 64 * k < S - 1) G[k] += gW + (gD != 0.f ? gD * (tm[k] - d) : 0.f);
+                }
+                if constexpr (LIST) {
+                    // dL/dw_e given per sample (hfagp_raymarch_rays_samples_bwd): G_e is dL/dw_e, so it is one more addend; white_back
+                    // and the depth clamp do not enter the weights
+                    if (p.g_weights) {                // (wave-uniform)
+                        const float* gw = p.g_weights + (size_t)ray * (S - 1);
+#pragma unroll
+                        for (int k = 0; k < 2; ++k)
+                            if (lane + 64 * k < S - 1) G[k] += gw[lane + 64 * k];
+                    }
                 }
                 const float gw0 = G[0] * w0, gw1 = G[1] * w1;
                 const float inc0 = wave_scan_add(gw0, lane), inc1 = wave_scan_add(gw1, lane);

@@ -27,6 +27,12 @@ struct RayParams {
     // per-ray depth limits of a list (hfagp.h HfagpRayLimits; the *_rays_limits_* entry points): [B][R] each.  Null for every other
     // entry point; read by the list instantiations of raymarch_body alone (raymarch.hip).
     const float* t_near, *t_far;
+    // per-sample outputs and their gradient (hfagp.h HfagpRaySamples; hfagp_raymarch_rays_samples_fwd / _samples_bwd): the compositing
+    // weights of the S-1 intervals between the depth-sorted samples [B][R][S-1], the sorted depths [B][R][S], and dL/d weights
+    // [B][R][S-1] added to pass 1's adjoint G_e.  Null for every other entry point; read by the list instantiations of raymarch_body
+    // alone.
+    float* samples_w, *samples_t;
+    const float* g_weights;
 };
 
 // rays = null: the pinhole grid of a->cam2world / a->intrinsics / a->res.  Else the ray list {origins, directions} of R rays per
@@ -61,6 +67,8 @@ inline int fill_ray_params(const HfagpRaymarchArgs* a, RayParams& p, const char*
     p.g_depth = p.g_wsum = p.depth_range = nullptr;
     p.rec = nullptr;
     p.t_near = p.t_far = nullptr;
+    p.samples_w = p.samples_t = nullptr;
+    p.g_weights = nullptr;
     return HFAGP_OK;
 }
 

@@ -100,3 +100,38 @@ extern "C" int hfagp_raymarch_rays_limits_bwd_rays(const HfagpRayListBwdArgs* a,
     p.t_far = lim->t_far;
     return launch_ray_list_grads(p, d_origins, d_directions, (hipStream_t)stream);
 }
+
+// ---- per-sample compositing weights (hfagp.h HfagpRaySamples): the forward with two more outputs, the backward with one more
+// addend in pass 1's adjoint (RayParams::samples_w / samples_t / g_weights, raymarch.hip), with or without per-ray limits.  Pass 2
+// and the rays' pass (hfagp_raymarch_rays_bwd_rays / _limits_bwd_rays above) read the records, into which the term is folded.
+extern "C" int hfagp_raymarch_rays_samples_fwd(const HfagpRayListArgs* a, const HfagpRayLimits* lim, const HfagpRaySamples* out,
+                                               void* stream) {
+    HFAGP_REQUIRE(!lim || (lim->t_near && lim->t_far), HFAGP_EBADARG, "raymarch_rays_samples_fwd: null pointer (limits)");
+    HFAGP_REQUIRE(out && out->weights && out->depths, HFAGP_EBADARG, "raymarch_rays_samples_fwd: null pointer (samples)");
+    HFAGP_REQUIRE(a, HFAGP_EBADARG, "raymarch_rays_samples_fwd: null pointer");
+    const HfagpRaymarchArgs* f = &a->base;
+    HFAGP_REQUIRE(f->feat && f->depth && f->wsum && f->tminmax, HFAGP_EBADARG, "raymarch_rays_samples_fwd: null pointer");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(f, p, "raymarch_rays_samples_fwd", &rays, lim != nullptr);
+    if (rc != HFAGP_OK) return rc;
+    if (lim) { p.t_near = lim->t_near; p.t_far = lim->t_far; }
+    p.samples_w = out->weights;
+    p.samples_t = out->depths;
+    return launch_raymarch(p, false, (hipStream_t)stream);
+}
+
+extern "C" int hfagp_raymarch_rays_samples_bwd(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim,
+                                               const HfagpRaymarchGeomGrads* geom, const float* g_weights, void* stream) {
+    HFAGP_REQUIRE(!lim || (lim->t_near && lim->t_far), HFAGP_EBADARG, "raymarch_rays_samples_bwd: null pointer (limits)");
+    HFAGP_REQUIRE(g_weights, HFAGP_EBADARG, "raymarch_rays_samples_bwd: null pointer (g_weights)");
+    HFAGP_REQUIRE(a && a->bwd.d_planes && a->bwd.rec, HFAGP_EBADARG, "raymarch_rays_samples_bwd: null pointer");
+    HFAGP_REQUIRE(!(geom && geom->g_depth) || geom->depth_range, HFAGP_EBADARG, "raymarch_rays_samples_bwd: g_depth needs depth_range");
+    const RayList rays{a->ray_origins, a->ray_directions, a->R};
+    RayParams p;
+    const int rc = fill_ray_params(&a->bwd.fwd, p, "raymarch_rays_samples_bwd", &rays, lim != nullptr);
+    if (rc != HFAGP_OK) return rc;
+    if (lim) { p.t_near = lim->t_near; p.t_far = lim->t_far; }
+    p.g_weights = g_weights;          // (g_feat, g_depth and g_wsum may all be null: this gradient alone is an upstream gradient)
+    return raymarch_bwd_run(&a->bwd, p, geom, (hipStream_t)stream);
+}

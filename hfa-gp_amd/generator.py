@@ -1126,7 +1126,8 @@ class TriPlaneGenerator(nn.Module):
                     decoder_precision=cfg.decoder_precision)
 
     @staticmethod
-    def _render_rays_empty(b: int, r: int, dev, zero, limits: bool, normals: bool, normal_grad: bool) -> Dict[str, torch.Tensor]:
+    def _render_rays_empty(b: int, r: int, dev, zero, limits: bool, normals: bool, normal_grad: bool,
+                           samples: int = 0) -> Dict[str, torch.Tensor]:
         """`render_rays` of no rays (B = 0 or R = 0): the dict of a call with these keywords, nothing launched.  ``zero``: 0.0, or
         under grad a zero scalar that hangs on the call's inputs and keeps their autograd edges."""
         feat = torch.zeros(b, r, 32, device=dev) + zero
@@ -1136,13 +1137,17 @@ class TriPlaneGenerator(nn.Module):
             out["valid"] = torch.zeros(b, r, device=dev, dtype=torch.bool)
         if normals:          # (detached unless normal_grad, as in a call with rays)
             out["normal"] = torch.zeros(b, r, 3, device=dev) + (zero if normal_grad else 0.0)
+        if samples:          # (S = Sc + Sf of the config; the depths are detached, as in a call with rays)
+            out["sample_weights"] = torch.zeros(b, r, samples - 1, device=dev) + zero
+            out["sample_depths"] = torch.zeros(b, r, samples, device=dev)
         return out
 
-    def _render_rays_normals_chunked(self, planes, o, d, u_strat, u_imp, planes_absmax, lim: dict, rays: int):
+    def _render_rays_normals_chunked(self, planes, o, d, u_strat, u_imp, planes_absmax, lim: dict, rays: int, samples: bool = False):
         """`ops.raymarch_rays` + `ops.raymarch_rays_normals` over chunks of `rays` rays per frame through one state buffer of that
         size: the per-sample state of the whole list would exceed RAY_STATE_CAP_BYTES.  A list may be cut at any ray; every ray is
         computed as in the whole-list launch (the decoder's bound on |planes| is the call's, taken once), so the five results —
-        feat, depth (unclamped), wsum, tminmax, normal — equal the unchunked ones bit for bit."""
+        feat, depth (unclamped), wsum, tminmax, normal — equal the unchunked ones bit for bit.  ``samples``: sample_weights and
+        sample_depths of `ops.raymarch_rays(samples=True)` follow as results six and seven."""
         cfg = self.cfg
         b, r = o.shape[0], o.shape[1]
         sc, sf = cfg.depth_resolution, cfg.depth_resolution_importance
@@ -1156,15 +1161,16 @@ class TriPlaneGenerator(nn.Module):
             state = buf.view(-1)[:b * n * (sc + sf) * 35].view(b, n, (sc + sf) * 35)
             oc, dc, us, ui = cut(o), cut(d), cut(u_strat), cut(u_imp).view(b * n, sf)
             lc = {k: cut(t) for k, t in lim.items()}
-            out = ops.raymarch_rays(planes, oc, dc, us, ui, planes_absmax=planes_absmax, state=state, **lc, **self._rays_kwargs())
-            parts.append(out + (ops.raymarch_rays_normals(planes, state, ray_origins=oc, ray_directions=dc, u_strat=us, u_imp=ui,
-                                                          planes_absmax=planes_absmax, **lc, **self._rays_kwargs()),))
+            out = ops.raymarch_rays(planes, oc, dc, us, ui, planes_absmax=planes_absmax, state=state, samples=samples, **lc,
+                                    **self._rays_kwargs())
+            parts.append(out[:4] + (ops.raymarch_rays_normals(planes, state, ray_origins=oc, ray_directions=dc, u_strat=us, u_imp=ui,
+                                                          planes_absmax=planes_absmax, **lc, **self._rays_kwargs()),) + out[4:])
         return tuple(torch.cat(t, 1) for t in zip(*parts))
 
     def render_rays(self, ws: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
                     u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                     noise_mode: str = "const", t_near=None, t_far=None, ray_limits: Optional[str] = None, normals: bool = False,
-                    normal_grad: bool = False, normal_ray_grad: bool = False) -> Dict[str, torch.Tensor]:
+                    normal_grad: bool = False, normal_ray_grad: bool = False, samples: bool = False) -> Dict[str, torch.Tensor]:
         """The renderer of `synthesis` on caller-given rays: ray_origins / ray_directions [B,R,3] in world units, R arbitrary — a
         crop or zoomed window (`cam_utils.ray_grid(c, res, window=)`), several cameras of one identity as one longer list in that
         frame (`torch.cat` along dim 1), random ray batches, or any camera model written in torch.  Directions are taken as given,
@@ -1193,7 +1199,19 @@ class TriPlaneGenerator(nn.Module):
         tensors included, at one more backward launch, and only when the loss uses it; above the cap that raises RuntimeError.  The
         rays get the normal term's gradient only with `normal_ray_grad=True` (which implies `normal_grad`) — rays that require
         grad raise NotImplementedError without it, as a label does in `synthesis(normal_grad=True)` without
-        `normal_camera_grad=True`.  The sample depths and the limits carry no gradient here either."""
+        `normal_camera_grad=True`.  The sample depths and the limits carry no gradient here either.
+        The distribution along the ray: `samples=True` adds 'sample_depths' [B,R,S] — the S = Sc + Sf sample depths of the ray, sorted
+        ascending — and 'sample_weights' [B,R,S−1], the compositing weight w_e = α_e·T_e of the interval [t_e, t_{e+1}]: the values
+        the kernel composites with, so Σ_e w_e is 'mask' and Σ_e w_e (t_e + t_{e+1})/2 / Σ_e w_e the depth before its clamp;
+        `white_back` does not enter.  For a distortion loss, a depth-distribution loss against a scan, median / quantile depth, depth
+        variance, transmittance at a depth (`ray_losses`).  Same launch count (ops.raymarch_rays(samples=True)); the four other
+        entries keep their bits.  'sample_depths' is always DETACHED — EG3D detaches the importance depths and the stratified ones
+        are constants of the uniforms — and so are the limits; under grad 'sample_weights' is differentiable w.r.t. `ws`, the
+        generator parameters that require grad (decoder included) and the rays (limits held fixed), its gradient entering the one
+        ray-march backward launch of the colour term, which then runs even when only 'sample_weights' carries a gradient.  An empty
+        ray has zeros in both (not inf: w·t stays finite in a loss).  It composes with the limits, with the three normal keywords
+        and with a state above RAY_STATE_CAP_BYTES; R = 0 gives [B,0,S] / [B,0,S−1].  `synthesis` has no such keyword: its grid as a
+        list (`cam_utils.ray_grid`) renders what it renders."""
         if noise_mode != "const":
             raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
         normal_grad = bool(normal_grad or normal_ray_grad)
@@ -1249,7 +1267,8 @@ class TriPlaneGenerator(nn.Module):
                                             any(p.requires_grad for p in params))
         if b == 0 or r == 0:
             zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0      # keeps the autograd edges
-            return self._render_rays_empty(b, r, dev, zero, limits is not None, normals, normal_grad)
+            return self._render_rays_empty(b, r, dev, zero, limits is not None, normals, normal_grad,
+                                           cfg.depth_resolution + cfg.depth_resolution_importance if samples else 0)
         state_bytes = b * r * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
         if grad and normal_grad and state_bytes > RAY_STATE_CAP_BYTES:
             raise RuntimeError(f"TriPlaneGenerator.render_rays(normal_grad=True): the backward of 'normal' reads the ray marcher's "
@@ -1269,11 +1288,16 @@ class TriPlaneGenerator(nn.Module):
                 raise RuntimeError("TriPlaneGenerator.render_rays under grad inside a trainer step scope: its backward is a second "
                                    "backbone pass and would release every parameter to the gradient sink twice")
             if normals:
-                from .autograd import RenderRaysNormalFn
-                feat, depth, mask, normal = RenderRaysNormalFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits,
-                                                                     normal_ray_grad, *params)
+                from .autograd import RenderRaysNormalFn, RenderRaysNormalSamplesFn
+                fn = RenderRaysNormalSamplesFn if samples else RenderRaysNormalFn
+                feat, depth, mask, normal, *ws_ts = fn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits,
+                                                             normal_ray_grad, *params)
                 if not normal_grad:
                     normal = normal.detach()
+            elif samples:
+                from .autograd import RenderRaysSamplesFn
+                feat, depth, mask, *ws_ts = RenderRaysSamplesFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits,
+                                                                      *params)
             else:
                 from .autograd import RenderRaysFn
                 feat, depth, mask = RenderRaysFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits, *params)
@@ -1282,15 +1306,16 @@ class TriPlaneGenerator(nn.Module):
                 planes, pam = self._query_planes(ws)
                 lim = {} if limits is None else dict(t_near=limits[0], t_far=limits[1])
                 o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
+                smp = dict(samples=True) if samples else {}
                 if normals and state_bytes > RAY_STATE_CAP_BYTES:        # above the cap: march and take the normals in ray chunks
-                    feat, depth, mask, tmm, normal = self._render_rays_normals_chunked(
-                        planes, o, d, u_strat, u_imp, pam, lim, max(1, RAY_STATE_CAP_BYTES // (state_bytes // r)))
+                    feat, depth, mask, tmm, normal, *ws_ts = self._render_rays_normals_chunked(
+                        planes, o, d, u_strat, u_imp, pam, lim, max(1, RAY_STATE_CAP_BYTES // (state_bytes // r)), **smp)
                 else:
                     state = None
                     if normals:
                         state = ops.raymarch_rays_state(b, r, cfg.depth_resolution, cfg.depth_resolution_importance, dev)
-                    feat, depth, mask, tmm = ops.raymarch_rays(planes, o, d, u_strat, u_imp, planes_absmax=pam, state=state, **lim,
-                                                               **self._rays_kwargs())
+                    feat, depth, mask, tmm, *ws_ts = ops.raymarch_rays(planes, o, d, u_strat, u_imp, planes_absmax=pam, state=state,
+                                                                       **lim, **smp, **self._rays_kwargs())
                     if normals:
                         normal = self._timed("raymarch_rays_normals", float(b), ops.raymarch_rays_normals, planes, state,
                                              ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=pam, **lim,
@@ -1299,6 +1324,8 @@ class TriPlaneGenerator(nn.Module):
         out = {"feature": feat, "rgb": feat[..., :3], "depth": depth, "mask": mask}
         if normals:
             out["normal"] = normal
+        if samples:
+            out["sample_weights"], out["sample_depths"] = ws_ts[0], ws_ts[1].detach()
         if limits is not None:
             from .cam_utils import ray_limits_valid
             out["valid"] = ray_limits_valid(*limits)

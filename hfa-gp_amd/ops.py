@@ -819,27 +819,39 @@ def raymarch_rays(planes: torch.Tensor, ray_origins: torch.Tensor, ray_direction
                   ray_start: float, ray_end: float, box_warp: float, decoder_lr_mul: float = 1.0, plane_axes: int = 0,
                   white_back: bool = False, decoder_precision: str = "f16x3", planes_absmax: Optional[torch.Tensor] = None,
                   state: Optional[torch.Tensor] = None, t_near: Optional[torch.Tensor] = None,
-                  t_far: Optional[torch.Tensor] = None):
+                  t_far: Optional[torch.Tensor] = None, samples: bool = False):
     """`raymarch` on caller-given rays: ray_origins / ray_directions [B,R,3] (directions as given, not normalised: a sample is
     o + t d) instead of (cam2world, intrinsics, res) → feat [B,R,32], depth [B,R] (unclamped), wsum [B,R], tminmax [B,R,2].
     u_strat [B,R,Sc], u_imp [B*R,Sf]; ``state``: `raymarch_rays_state`.  Everything else as `raymarch`.
     ``t_near`` / ``t_far`` [B,R] (both or neither; `ray_limits_box`, or any limits of the caller's): every ray is sampled on its own
     interval instead of [ray_start, ray_end], which is then ignored (hfagp_raymarch_rays_limits_fwd).  A ray whose limits are not
     finite or have far <= near is EMPTY and not marched: feat = the background (−1, or +1 with white_back), wsum 0, depth +inf,
-    tminmax (+inf, −inf) — `depth_range(..., empty_rays=True)` / `depth_clamp_(..., empty_rays=True)` take such a call."""
+    tminmax (+inf, −inf) — `depth_range(..., empty_rays=True)` / `depth_clamp_(..., empty_rays=True)` take such a call.
+    ``samples``: two more results (hfagp_raymarch_rays_samples_fwd) — sample_weights [B,R,Sc+Sf−1], the compositing weight
+    w_e = α_e·T_e of the interval between sorted samples e and e+1 (the values the kernel composites with: their sum is wsum), and
+    sample_depths [B,R,Sc+Sf], ascending; both zero for an empty ray.  The other four results keep their bits."""
     a = L.RayListArgs()
-    b, _, _, r, _, _, lim = _ray_list_args("raymarch_rays", a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0,
-                                           dec_w1, dec_b1, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back,
-                                           decoder_precision, planes_absmax, state, t_near, t_far)
+    b, _, _, r, sc, sf, lim = _ray_list_args("raymarch_rays", a, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0,
+                                             dec_w1, dec_b1, ray_start, ray_end, box_warp, decoder_lr_mul, plane_axes, white_back,
+                                             decoder_precision, planes_absmax, state, t_near, t_far)
     dev = planes.device
     feat = torch.empty(b, r, 32, device=dev, dtype=torch.float32)
     depth = torch.empty(b, r, device=dev, dtype=torch.float32)
     wsum = torch.empty(b, r, device=dev, dtype=torch.float32)
     tmm = torch.empty(b, r, 2, device=dev, dtype=torch.float32)
+    out = (feat, depth, wsum, tmm)
+    if samples:
+        so = L.RaySamples()
+        out += (torch.empty(b, r, sc + sf - 1, device=dev, dtype=torch.float32), torch.empty(b, r, sc + sf, device=dev, dtype=torch.float32))
+        so.weights, so.depths = _ptr(out[4]), _ptr(out[5])
     if b * r == 0:
-        return feat, depth, wsum, tmm
+        return out
     f = a.base
     f.feat, f.depth, f.wsum, f.tminmax = _ptr(feat), _ptr(depth), _ptr(wsum), _ptr(tmm)
+    if samples:
+        L.check(L.lib().hfagp_raymarch_rays_samples_fwd(C.byref(a), C.byref(lim) if lim is not None else None, C.byref(so), _stream()),
+                "raymarch_rays_samples_fwd")
+        return out
     if lim is not None:
         L.check(L.lib().hfagp_raymarch_rays_limits_fwd(C.byref(a), C.byref(lim), _stream()), "raymarch_rays_limits_fwd")
     else:
@@ -2007,14 +2019,18 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
                       state: Optional[torch.Tensor] = None, rows: Optional[bool] = None, dec_out=None, _out=None,
                       g_depth: Optional[torch.Tensor] = None, g_wsum: Optional[torch.Tensor] = None,
                       depth_range: Optional[torch.Tensor] = None, rec_out: Optional[list] = None,
-                      t_near: Optional[torch.Tensor] = None, t_far: Optional[torch.Tensor] = None):
+                      t_near: Optional[torch.Tensor] = None, t_far: Optional[torch.Tensor] = None,
+                      g_weights: Optional[torch.Tensor] = None):
     """`raymarch_bwd` of `raymarch_rays`: g_feat [B,R,32] (and / or g_depth, g_wsum [B,R]) → d planes [B,3,H,W,32], with the same
     keywords and return forms.  ``rows``: None = sort + gather whenever it applies, False = the scatter kernels (the image-column
     variant of the grid is not offered for a list).  The sort's scratch is bounded by `rows_scratch_cap()` as for the grid; a list may
     be cut at any ray, so a call that needs more runs in frame chunks and, where one frame is too much, in ray chunks of a frame.
     ``rec_out``: receives pass 1's records [B,R,Sc+Sf,4] (`raymarch_rays_bwd_rays` reads them).  ``t_near`` / ``t_far`` [B,R]: the
     forward call's per-ray limits (hfagp_raymarch_rays_limits_bwd); they carry no gradient, an empty ray contributes exactly zero
-    and its g_depth / g_wsum are not read; ``depth_range`` is then `ops.depth_range(tminmax, empty_rays=True)`."""
+    and its g_depth / g_wsum are not read; ``depth_range`` is then `ops.depth_range(tminmax, empty_rays=True)`.
+    ``g_weights`` [B,R,Sc+Sf−1]: the gradient w.r.t. the sample_weights of `raymarch_rays(..., samples=True)`, one more addend of the
+    compositing adjoint (hfagp_raymarch_rays_samples_bwd); alone it is a sufficient upstream gradient (g_feat None), the records
+    carry it on to `raymarch_rays_bwd_rays`, and a chunked call slices it with its rays."""
     who = "raymarch_rays_bwd"
     b, _, _ = _planes_dims(who, planes)
     r = ray_origins.shape[1] if ray_origins.dim() == 3 else -1
@@ -2026,6 +2042,8 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
     if depth_range is not None and _chk(depth_range, f"{who}: depth_range").shape != (2,):
         raise RuntimeError(f"{who}: depth_range must be [2] (ops.depth_range), got {tuple(depth_range.shape)}")
     sc, sf = u_strat.shape[-1], u_imp.shape[-1]
+    if g_weights is not None and _chk(g_weights, f"{who}: g_weights").shape != (b, r, sc + sf - 1):
+        raise RuntimeError(f"{who}: g_weights must be [B, R, Sc + Sf - 1] = [{b}, {r}, {sc + sf - 1}], got {tuple(g_weights.shape)}")
     d_planes, rec = _out if _out is not None else (
         torch.zeros_like(planes), torch.empty(b, max(r, 0), sc + sf, 4, device=planes.device, dtype=torch.float32))
     if rec_out is not None:
@@ -2035,7 +2053,7 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
     dec = _raymarch_rays_bwd_chunk(
         g_feat=g_feat, planes=planes, ray_origins=ray_origins, ray_directions=ray_directions, u_strat=u_strat,
         u_imp=u_imp.reshape(b, r, sf) if r >= 0 and u_imp.numel() == b * r * sf else u_imp, state=state, g_depth=g_depth, g_wsum=g_wsum,
-        t_near=t_near, t_far=t_far, depth_range=depth_range, d_planes=d_planes, rec=rec, decoder_grads=decoder_grads, dec_out=dec_out,
+        g_weights=g_weights, t_near=t_near, t_far=t_far, depth_range=depth_range, d_planes=d_planes, rec=rec, decoder_grads=decoder_grads, dec_out=dec_out,
         rows=rows, dec_w0=dec_w0, dec_b0=dec_b0, dec_w1=dec_w1, dec_b1=dec_b1, ray_start=ray_start, ray_end=ray_end, box_warp=box_warp,
         decoder_lr_mul=decoder_lr_mul, plane_axes=plane_axes, white_back=white_back, decoder_precision=decoder_precision,
         planes_absmax=_decoder_bound(planes, decoder_precision, planes_absmax) if planes.numel() else None)
@@ -2044,8 +2062,8 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
     return (d_planes, rec) if return_rec else d_planes
 
 
-def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_strat, u_imp, state, g_depth, g_wsum, t_near, t_far,
-                             depth_range, d_planes, rec, decoder_grads, dec_out, rows, **scene):
+def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_strat, u_imp, state, g_depth, g_wsum, g_weights,
+                             t_near, t_far, depth_range, d_planes, rec, decoder_grads, dec_out, rows, **scene):
     """`raymarch_rays_bwd` of the rays it is given: the whole list or — from itself — a chunk of it (`_raymarch_bwd_frames` for a
     list; u_imp arrives as [B,R,Sf]).  Fills ``d_planes`` and ``rec`` in place, returns the decoder-gradient tuple or None."""
     who = "raymarch_rays_bwd"
@@ -2066,7 +2084,7 @@ def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_s
             # every per-ray input / output is [B, R, ...]: frames are contiguous slices, and so are the rays r0:r1 of ONE frame; the
             # decoder gradients accumulate in the one `dec`, d_planes accumulates per frame, the depth range is the call's
             per_ray = dict(g_feat=g_feat, ray_origins=ray_origins, ray_directions=ray_directions, u_strat=u_strat, u_imp=u_imp,
-                           state=state, g_depth=g_depth, g_wsum=g_wsum, rec=rec, t_near=t_near, t_far=t_far)
+                           state=state, g_depth=g_depth, g_wsum=g_wsum, g_weights=g_weights, rec=rec, t_near=t_near, t_far=t_far)
             fit = max(1, int(b * r * cap // need))            # rays one call can take
             nb, nr = (max(1, min(b - 1, fit // r)), r) if fit >= r and b > 1 else (1, max(1, min(r - 1, fit)))
             chunks = 0
@@ -2096,7 +2114,10 @@ def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_s
     else:
         gg = L.RaymarchGeomGrads()
         gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
-    if lim is not None:
+    if g_weights is not None:
+        L.check(L.lib().hfagp_raymarch_rays_samples_bwd(C.byref(a), C.byref(lim) if lim is not None else None,
+                                                        C.byref(gg) if gg is not None else None, _ptr(g_weights), _stream()), who)
+    elif lim is not None:
         L.check(L.lib().hfagp_raymarch_rays_limits_bwd(C.byref(a), C.byref(lim), C.byref(gg) if gg is not None else None, _stream()), who)
     else:
         L.check(L.lib().hfagp_raymarch_rays_bwd(C.byref(a), C.byref(gg) if gg is not None else None, _stream()), who)

@@ -53,6 +53,8 @@
  *                              its autograd w.r.t. planes, decoder and the rays (crops, multi-view lists, arbitrary camera models)
  *   hfagp_raymarch_rays_limits_fwd / _limits_bwd / _limits_bwd_rays, hfagp_ray_limits_box <- the same with per-ray depth limits:
  *                              ImportanceRenderer.forward with ray_start == ray_end == 'auto' (math_utils.get_ray_limits_box)
+ *   hfagp_raymarch_rays_samples_fwd / _samples_bwd <- MipRayMarcher2's `weights` and the sorted depths of unify_samples, which
+ *                              ImportanceRenderer.forward drops, as outputs of the list renderer, and autograd through the weights
  *   hfagp_planes_query_bwd  <- autograd of sample_mixed (grid_sample + OSGDecoder at given points) w.r.t. planes, decoder and points
  *   hfagp_modconv_fwd modes HFAGP_CONV3X3_BWD / HFAGP_CONVS2_BWD <- conv2d_gradfix data gradients (the same GEMM kernel)
  *   hfagp_conv_wgrad (+ _workspace_bytes) <- conv2d_gradfix weight gradients
@@ -783,7 +785,9 @@ int hfagp_raymarch_bwd(const HfagpRaymarchBwdArgs* a, void* stream);
  * to the batch-global range [lo, hi] = depth_range): it is 0 where W == 0, where d is not finite and where d lies outside
  * [lo, hi] (a depth ON a bound passes, as torch.clamp's gradient does).  The sample depths carry no gradient (stratified
  * depths come from the uniforms, importance depths are detached as in EG3D), so everything after G_e — d alpha, d sigma, the
- * per-sample records, all of pass 2 — is what the image gradient alone goes through.
+ * per-sample records, all of pass 2 — is what the image gradient alone goes through.  On a ray list a per-sample gradient is one
+ * more addend (hfagp_raymarch_rays_samples_bwd below):
+ *     G_e = g . cbar_e  -  white_back * sum(g)  +  gamma_W  +  gamma_d * (tbar_e - d) / W  +  g_weights[e]
  * hfagp_raymarch_bwd(a, s) == hfagp_raymarch_bwd_geom(a, NULL, s).  a->g_feat may be NULL (zeros) when g_depth or g_wsum is
  * given.  HFAGP_EBADARG, nothing launched: g_depth without depth_range; no upstream gradient at all.                        */
 typedef struct {
@@ -883,6 +887,33 @@ int hfagp_raymarch_rays_limits_bwd(const HfagpRayListBwdArgs* a, const HfagpRayL
 /* (reads the depths from the records of hfagp_raymarch_rays_limits_bwd; lim is checked, its arrays are not read)               */
 int hfagp_raymarch_rays_limits_bwd_rays(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim,
                                         float* d_origins, float* d_directions, void* stream);
+
+/* ------------------------------------------------------------------ per-sample compositing weights of ray lists (additive to ABI 15)
+ * The distribution along every ray of a list, which the entry points above compute and reduce to one number per ray: with
+ * S = Sc + Sf samples sorted by depth, t_0 <= .. <= t_{S-1}, the compositing weight w_e = alpha_e T_e of interval [t_e, t_{e+1}],
+ * e = 0 .. S-2 — for distortion and depth-distribution losses, median / quantile depth, depth variance, transmittance at a depth.
+ *   weights[ray][e] = w_e, the very values the kernel composites feat, wsum (= sum_e w_e) and depth (= sum_e w_e tbar_e / wsum,
+ *                     tbar_e = (t_e + t_{e+1}) / 2) with; white_back does not enter;
+ *   depths[ray][s]  = t_s, by SORTED position (not sample id).
+ * hfagp_raymarch_rays_samples_fwd is hfagp_raymarch_rays_fwd (lim NULL) or hfagp_raymarch_rays_limits_fwd (lim given) with these two
+ * more outputs; every other output has the bits of that call.  An EMPTY ray (see HfagpRayLimits) gets S-1 zeros and S zeros.
+ * hfagp_raymarch_rays_samples_bwd is hfagp_raymarch_rays_bwd / _limits_bwd with g_weights [B][R][Sc+Sf-1] = dL/d weights as one more
+ * addend of pass 1's per-interval adjoint (see HfagpRaymarchGeomGrads):
+ *     G_e = g . cbar_e  -  white_back * sum(g)  +  gamma_W  +  gamma_d * (tbar_e - d) / W  +  g_weights[e]
+ * The depths carry no gradient (importance depths are detached as in EG3D, stratified ones are constants), so all that follows
+ * G_e is unchanged, and the rays' gradient of the term comes from hfagp_raymarch_rays_bwd_rays / _limits_bwd_rays on the records
+ * this call wrote.  g_weights of an empty ray is not read.  g_weights alone is an upstream gradient: a->bwd.g_feat and g (or its
+ * members) may all be NULL.
+ * HFAGP_EBADARG, nothing launched: out or one of its members NULL; g_weights NULL; lim non-NULL with a NULL member; then the checks
+ * of the list entry point with (lim given) or without limits.                                                                  */
+typedef struct {
+    float* weights;               /* [B][R][Sc+Sf-1] */
+    float* depths;                /* [B][R][Sc+Sf]   */
+} HfagpRaySamples;
+int hfagp_raymarch_rays_samples_fwd(const HfagpRayListArgs* a, const HfagpRayLimits* lim /* NULL: config interval */,
+                                    const HfagpRaySamples* out, void* stream);
+int hfagp_raymarch_rays_samples_bwd(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim /* NULL ok */,
+                                    const HfagpRaymarchGeomGrads* g /* NULL ok */, const float* g_weights, void* stream);
 
 /* ------------------------------------------------------------------ surface normals along ray lists (additive to ABI 15)
  * hfagp_raymarch_normals, hfagp_raymarch_normals_bwd and the per-ray part of hfagp_raymarch_normals_bwd_camera on the rays of a
