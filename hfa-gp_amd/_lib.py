@@ -256,6 +256,8 @@ SYMBOLS = {
     "hfagp_raymarch_rays_bwd_rows_bytes": (C.c_size_t, [C.POINTER(RayListArgs)]),
     "hfagp_raymarch_rays_bwd_rays": (C.c_int, [C.POINTER(RayListBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hfagp_ray_limits_box": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "hfagp_ray_limits_grid": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_float, C.c_void_p]),
+    "hfagp_occupancy_pack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
     "hfagp_raymarch_rays_limits_fwd": (C.c_int, [C.POINTER(RayListArgs), C.POINTER(RayLimits), C.c_void_p]),
     "hfagp_raymarch_rays_limits_bwd": (C.c_int, [C.POINTER(RayListBwdArgs), C.POINTER(RayLimits), C.POINTER(RaymarchGeomGrads),
                                                  C.c_void_p]),

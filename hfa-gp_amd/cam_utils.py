@@ -151,3 +151,57 @@ def ray_limits_box(origins: torch.Tensor, directions: torch.Tensor, box_side: fl
 def ray_limits_valid(t_near: torch.Tensor, t_far: torch.Tensor) -> torch.Tensor:
     """The rays the ray marcher marches: both limits finite and t_far > t_near (bool, the shape of the limits)."""
     return torch.isfinite(t_near) & torch.isfinite(t_far) & (t_far > t_near)
+
+
+def ray_limits_grid(origins: torch.Tensor, directions: torch.Tensor, dense: torch.Tensor, cube_length: float,
+                    max_pairs: int = 1 << 22) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(t_near, t_far), each [B, R], of rays [B, R, 3] against an occupancy mask `dense` bool [B or 1, G, G, G] (indexed ix, iy, iz)
+    over the cube of side `cube_length`: the entry of the first and the exit of the last occupied cell a ray passes through at
+    t ≥ 0 — the reference of `ops.ray_limits_grid` (hfagp_ray_limits_grid) in plain torch, in the dtype of the rays (float32 as the
+    kernel computes, float64 as its yardstick), usable on the CPU.  A BRUTE FORCE on purpose: per ray the slab interval against
+    EVERY occupied cell, then a min / max over the cells — no traversal, no order, nothing shared with the kernel's DDA.  Chunked
+    over the rays so that rays × cells stays below `max_pairs`.
+    Cell (ix, iy, iz) spans [plane(i), plane(i+1)] per axis, plane(i) = −L/2 + i·(L/G).  Per axis with d ≠ 0: inv = 1/d,
+    ta = (plane(i) − o)·inv, tb = (plane(i+1) − o)·inv, in = min(ta, tb), out = max(ta, tb) (`ray_limits_box`'s formula on the
+    cell's planes); an axis with d = 0 lies in the half-open slab plane(i) ≤ o < plane(i+1) of one i (in = −inf, out = +inf), and
+    o ≤ plane(0) or o ≥ plane(G) there empties the ray (the box's 0·inf).  near_c = max in, far_c = min out; a cell COUNTS iff
+    far_c > max(near_c, 0) (a NaN never does); t_near = min over the counting cells of max(near_c, 0), t_far = max of far_c.  No
+    counting cell, a zero direction or a limit that is not finite: (+inf, −inf), an empty ray.  Not differentiable."""
+    if origins.dim() != 3 or origins.shape[-1] != 3 or origins.shape != directions.shape:
+        raise ValueError(f"ray_limits_grid: origins / directions must be [B, R, 3], got {tuple(origins.shape)}, {tuple(directions.shape)}")
+    if dense.dim() != 4 or dense.shape[0] not in (1, origins.shape[0]) or len(set(dense.shape[1:])) != 1:
+        raise ValueError(f"ray_limits_grid: dense must be [B or 1, G, G, G] for {origins.shape[0]} frames, got {tuple(dense.shape)}")
+    with torch.no_grad():
+        b, r = origins.shape[:2]
+        g = dense.shape[1]
+        dt, dev = origins.dtype, origins.device
+        inf = float("inf")
+        half = torch.tensor(0.5 * float(cube_length), dtype=dt, device=dev)
+        cell = torch.tensor(float(cube_length), dtype=dt, device=dev) / g
+        plane = -half + torch.arange(g + 1, device=dev).to(dt) * cell          # [G+1], each operation rounded in dt
+        t_near = torch.full((b, r), inf, dtype=dt, device=dev)
+        t_far = torch.full((b, r), -inf, dtype=dt, device=dev)
+        for f in range(b):
+            cells = dense[f if dense.shape[0] > 1 else 0].nonzero()          # [C, 3]
+            if cells.shape[0] == 0:
+                continue
+            lo, hi = plane[cells], plane[cells + 1]                           # [C, 3]
+            chunk = max(1, int(max_pairs) // cells.shape[0])
+            for r0 in range(0, r, chunk):
+                o, d = origins[f, r0:r0 + chunk, None, :], directions[f, r0:r0 + chunk, None, :]     # [n, 1, 3]
+                inv = 1.0 / d
+                ta, tb = (lo - o) * inv, (hi - o) * inv                       # [n, C, 3]
+                t_in, t_out = torch.minimum(ta, tb), torch.maximum(ta, tb)    # (NaN propagates)
+                par = (d == 0).expand_as(ta)
+                inside = (lo <= o) & (o < hi)
+                t_in = torch.where(par, torch.where(inside, -inf, inf).to(dt), t_in)
+                t_out = torch.where(par, torch.where(inside, inf, -inf).to(dt), t_out)
+                near_c = t_in.amax(-1).clamp(min=0.0)                         # (amax / amin / clamp propagate NaN)
+                far_c = t_out.amin(-1)
+                counts = far_c > near_c                                       # (False for a NaN)
+                t_near[f, r0:r0 + chunk] = torch.where(counts, near_c, torch.full_like(near_c, inf)).amin(1)
+                t_far[f, r0:r0 + chunk] = torch.where(counts, far_c, torch.full_like(far_c, -inf)).amax(1)
+        par = directions == 0
+        empty = par.all(-1) | (par & ((origins <= plane[0]) | (origins >= plane[g]))).any(-1)
+        empty |= ~(torch.isfinite(t_near) & torch.isfinite(t_far))
+        return torch.where(empty, torch.full_like(t_near, inf), t_near), torch.where(empty, torch.full_like(t_far, -inf), t_far)

@@ -1169,8 +1169,9 @@ class TriPlaneGenerator(nn.Module):
 
     def render_rays(self, ws: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
                     u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
-                    noise_mode: str = "const", t_near=None, t_far=None, ray_limits: Optional[str] = None, normals: bool = False,
-                    normal_grad: bool = False, normal_ray_grad: bool = False, samples: bool = False) -> Dict[str, torch.Tensor]:
+                    noise_mode: str = "const", t_near=None, t_far=None, ray_limits=None, normals: bool = False,
+                    normal_grad: bool = False, normal_ray_grad: bool = False, samples: bool = False,
+                    compact: bool = False) -> Dict[str, torch.Tensor]:
         """The renderer of `synthesis` on caller-given rays: ray_origins / ray_directions [B,R,3] in world units, R arbitrary — a
         crop or zoomed window (`cam_utils.ray_grid(c, res, window=)`), several cameras of one identity as one longer list in that
         frame (`torch.cat` along dim 1), random ray batches, or any camera model written in torch.  Directions are taken as given,
@@ -1211,17 +1212,43 @@ class TriPlaneGenerator(nn.Module):
         ray-march backward launch of the colour term, which then runs even when only 'sample_weights' carries a gradient.  An empty
         ray has zeros in both (not inf: w·t stays finite in a loss).  It composes with the limits, with the three normal keywords
         and with a state above RAY_STATE_CAP_BYTES; R = 0 gives [B,0,S] / [B,0,S−1].  `synthesis` has no such keyword: its grid as a
-        list (`cam_utils.ray_grid`) renders what it renders."""
+        list (`cam_utils.ray_grid`) renders what it renders.
+        Empty space: `ray_limits=occ` with an `OccupancyGrid` (`occupancy_grid`, or `OccupancyGrid.from_dense` of any mask; batch B
+        or 1, cube_length == cfg.box_warp) takes the limits from the grid instead of the cube — per ray the entry of the first and
+        the exit of the last occupied cell (`ops.ray_limits_grid`, under no_grad from detached rays, as "box"), so the samples
+        are spent on the head's chord and a ray that meets no occupied cell is empty.  The same launches as `t_near=` / `t_far=`
+        run, and every keyword composes.  ONE interval per ray: empty cells between occupied ones are still sampled.
+        `compact=True` (only with limits of any kind): per frame the valid rays are moved to the front (stable: their order is
+        kept), only the first R' = the largest valid count of a frame are marched (plus one empty ray, which costs nothing and
+        carries the depth an empty ray gets), and the results are scattered back — the forward entries are bit-identical to
+        `compact=False`, since a ray's result depends on its own inputs only; the rays' gradient comes through the gather from torch
+        autograd.  It costs one host sync (R' is a Python int); no valid ray at all launches nothing."""
         if noise_mode != "const":
             raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
         normal_grad = bool(normal_grad or normal_ray_grad)
         normals = bool(normals or normal_grad)
-        if ray_limits is not None and ray_limits != "box":
-            raise ValueError(f"TriPlaneGenerator.render_rays: ray_limits must be None or 'box', got {ray_limits!r}")
+        from .occupancy import OccupancyGrid
+        occ = ray_limits if isinstance(ray_limits, OccupancyGrid) else None
+        if ray_limits is not None and occ is None and not (isinstance(ray_limits, str) and ray_limits == "box"):
+            raise ValueError(f"TriPlaneGenerator.render_rays: ray_limits must be None or 'box' or an OccupancyGrid, got {ray_limits!r}")
         if (t_near is None) != (t_far is None):
             raise ValueError("TriPlaneGenerator.render_rays: t_near and t_far go together (both or neither)")
         if ray_limits is not None and t_near is not None:
-            raise ValueError("TriPlaneGenerator.render_rays: ray_limits='box' and explicit t_near / t_far are mutually exclusive")
+            raise ValueError("TriPlaneGenerator.render_rays: ray_limits='box' / an OccupancyGrid and explicit t_near / t_far are "
+                             "mutually exclusive")
+        if compact and ray_limits is None and t_near is None:
+            raise ValueError("TriPlaneGenerator.render_rays: compact=True needs ray limits (t_near / t_far or ray_limits=): without "
+                             "them every ray is marched")
+        if occ is not None:
+            if occ.batch not in (1, ws.shape[0]):
+                raise ValueError(f"TriPlaneGenerator.render_rays: the occupancy grid's batch must be B = {ws.shape[0]} or 1, got "
+                                 f"{occ.batch}")
+            if float(occ.cube_length) != float(self.cfg.box_warp):
+                raise ValueError(f"TriPlaneGenerator.render_rays: the occupancy grid's cube_length {occ.cube_length} differs from "
+                                 f"cfg.box_warp = {self.cfg.box_warp}")
+            if not occ.bits.is_cuda or occ.bits.device != ws.device:
+                raise RuntimeError(f"TriPlaneGenerator.render_rays: the occupancy grid lives on {occ.bits.device}, ws on {ws.device}; "
+                                   f"the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
         for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
             if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] != ws.shape[0]:
                 raise ValueError(f"expected {name} [B, R, 3] for ws of batch {ws.shape[0]}, got {tuple(t.shape)}")
@@ -1260,8 +1287,8 @@ class TriPlaneGenerator(nn.Module):
                 else:
                     limits.append(torch.full((b, r), float(t), device=dev, dtype=torch.float32))
             limits = tuple(limits)
-        elif ray_limits == "box":
-            limits = "box"
+        elif ray_limits is not None:
+            limits = "box" if occ is None else "grid"
         params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
         grad = torch.is_grad_enabled() and (ws.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad or
                                             any(p.requires_grad for p in params))
@@ -1270,7 +1297,7 @@ class TriPlaneGenerator(nn.Module):
             return self._render_rays_empty(b, r, dev, zero, limits is not None, normals, normal_grad,
                                            cfg.depth_resolution + cfg.depth_resolution_importance if samples else 0)
         state_bytes = b * r * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
-        if grad and normal_grad and state_bytes > RAY_STATE_CAP_BYTES:
+        if grad and normal_grad and state_bytes > RAY_STATE_CAP_BYTES and not compact:      # (compact: the check of the inner call)
             raise RuntimeError(f"TriPlaneGenerator.render_rays(normal_grad=True): the backward of 'normal' reads the ray marcher's "
                                f"per-sample state, {state_bytes} bytes for {b} x {r} rays, above RAY_STATE_CAP_BYTES = "
                                f"{RAY_STATE_CAP_BYTES}; {RAY_STATE_CAP_BYTES // (state_bytes // (b * r))} rays fit")
@@ -1278,11 +1305,21 @@ class TriPlaneGenerator(nn.Module):
             with torch.no_grad():
                 limits = ops.ray_limits_box(ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous(),
                                             cfg.box_warp)
+        elif limits == "grid":
+            with torch.no_grad():
+                limits = ops.ray_limits_grid(ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous(),
+                                             occ)
         if u_strat is None:
             u_strat = torch.rand(b, r, cfg.depth_resolution, device=dev)
         if u_imp is None:
             u_imp = torch.rand(b * r, cfg.depth_resolution_importance, device=dev)
         u_strat, u_imp = u_strat.detach().float().reshape(b, r, -1).contiguous(), u_imp.detach().float().contiguous()
+        if compact:
+            out = self._render_rays_compact(ws, ray_origins, ray_directions, u_strat, u_imp, limits, grad,
+                                            dict(normals=normals, normal_grad=normal_grad, normal_ray_grad=normal_ray_grad,
+                                                 samples=samples))
+            if out is not None:
+                return out
         if grad:
             if getattr(self, "_grad_sink", None) is not None or getattr(self, "_grad_inplace", False):
                 raise RuntimeError("TriPlaneGenerator.render_rays under grad inside a trainer step scope: its backward is a second "
@@ -1331,6 +1368,49 @@ class TriPlaneGenerator(nn.Module):
             out["valid"] = ray_limits_valid(*limits)
         return out
 
+    def _render_rays_compact(self, ws, ray_origins, ray_directions, u_strat, u_imp, limits, grad: bool, kw: dict):
+        """`render_rays(compact=True)` once the limits are tensors: the valid rays of every frame first (stable), the first R' + 1 of
+        them marched by a plain `render_rays(t_near=, t_far=)` call, the results scattered back over the empty-ray values.  None when
+        a frame has no empty ray (nothing to leave out: the caller goes on as without the keyword).  The + 1: an empty ray is not
+        marched, and its 'depth' is what every empty ray of the call gets — the upper end of the clamp range over the valid rays,
+        which are the same rays in both calls."""
+        from .cam_utils import ray_limits_valid
+        cfg = self.cfg
+        b, r = ray_origins.shape[:2]
+        dev = ws.device
+        valid = ray_limits_valid(*limits)
+        n_valid = int(valid.sum(1).max())                  # (the one host sync)
+        if n_valid == r:
+            return None
+        s = cfg.depth_resolution + cfg.depth_resolution_importance
+        if n_valid == 0:
+            zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0
+            out = self._render_rays_empty(b, r, dev, zero, True, kw["normals"], kw["normal_grad"], s if kw["samples"] else 0)
+            out["feature"] = out["feature"] + (1.0 if cfg.white_back else -1.0)
+            out["rgb"] = out["feature"][..., :3]
+            return out
+        m = n_valid + 1
+        idx = torch.argsort((~valid).to(torch.uint8), dim=1, stable=True)[:, :m]              # [B, m]: the valid rays, then empty ones
+        idx3 = idx[..., None].expand(b, m, 3)
+        sf = u_imp.shape[-1]
+        sub = self.render_rays(ws, ray_origins.gather(1, idx3), ray_directions.gather(1, idx3),
+                               u_strat.gather(1, idx[..., None].expand(b, m, u_strat.shape[-1])),
+                               u_imp.view(b, r, sf).gather(1, idx[..., None].expand(b, m, sf)).reshape(b * m, sf),
+                               t_near=limits[0].gather(1, idx), t_far=limits[1].gather(1, idx), **kw)
+        background = 1.0 if cfg.white_back else -1.0
+        fill = {"feature": background, "depth": sub["depth"][0, -1].detach(), "mask": 0.0, "normal": 0.0, "sample_weights": 0.0,
+                "sample_depths": 0.0}
+        out = {}
+        for key, val in sub.items():
+            if key in ("rgb", "valid"):
+                continue
+            full = torch.empty(b, r, *val.shape[2:], device=dev, dtype=val.dtype)
+            full[...] = fill[key]
+            out[key] = full.scatter(1, idx.reshape(b, m, *([1] * (val.dim() - 2))).expand_as(val), val)
+        out["rgb"] = out["feature"][..., :3]
+        out["valid"] = valid
+        return out
+
     def sample(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], z: torch.Tensor, c: torch.Tensor,
                truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:
         """EG3D TriPlaneGenerator.sample: `mapping(z, c, truncation_psi)` then `sample_mixed`.  Only truncation_cutoff=None
@@ -1361,6 +1441,38 @@ class TriPlaneGenerator(nn.Module):
             planes, pam = self._query_planes(ws)
             self._fill_density(vol, planes, pam, cube, max_points)
         return vol
+
+    def occupancy_grid(self, ws: torch.Tensor, resolution: int = 64, level: float = 0.0, oversample: int = 2, dilate: int = 1,
+                       cube_length: Optional[float] = None, max_points: Optional[int] = None):
+        """An `OccupancyGrid` of the heads of `ws` for `render_rays(..., ray_limits=occ)`: G = `resolution` (2 … 256) cells per axis
+        over a cube of side `cube_length` (default box_warp — the only one `render_rays` takes).  One backbone pass; the raw density
+        on the exact integer lattice of n = G·k + 1 points per axis, k = `oversample` ≥ 1 (`density_grid`'s kernel), then ONE launch
+        (ops.occupancy_pack): a cell is occupied iff one of the (k+1)³ lattice points of its closed extent has !(σ < level) — faces
+        are shared with the neighbours, which errs on the conservative side; a NaN is occupied — and the grid is dilated by
+        `dilate` cells (0 … 8).  Forward only.
+        `level` is the caller's trade-off between tight limits and lost density: it is compared with the RAW σ of `sample_mixed`,
+        which enters the march as softplus(σ − 1) — at σ = 0 that is still 0.31 per unit length.  With trained EG3D weights empty
+        space is strongly negative and a level around 0 keeps every visible sample; with random weights no level is meaningful.
+        The field is only seen at the lattice points: `oversample` and `dilate` are the margin for what lies between them."""
+        from .occupancy import OccupancyGrid
+        g, k = int(resolution), int(oversample)
+        if not 2 <= g <= 256:
+            raise ValueError(f"occupancy_grid: resolution must be in [2, 256], got {resolution}")
+        if k < 1 or g * k + 1 > 1025:
+            raise ValueError(f"occupancy_grid: oversample must be >= 1 with resolution * oversample + 1 <= 1025, got {oversample}")
+        if not 0 <= int(dilate) <= 8:
+            raise ValueError(f"occupancy_grid: dilate must be in [0, 8], got {dilate}")
+        self._query_guard("occupancy_grid", ws)
+        b, n = ws.shape[0], g * k + 1
+        cube = float(self.cfg.box_warp if cube_length is None else cube_length)
+        if b == 0:
+            return OccupancyGrid(torch.zeros(0, g, g, (g + 31) // 32, device=ws.device, dtype=torch.int32), g, cube)
+        with torch.no_grad():
+            vol = torch.empty(b, n, n, n, device=ws.device, dtype=torch.float32)
+            planes, pam = self._query_planes(ws)
+            self._fill_density(vol, planes, pam, cube, max_points)
+            bits = self._timed("occupancy_pack", float(b), ops.occupancy_pack, vol, g, k, float(level), int(dilate))
+        return OccupancyGrid(bits, g, cube)
 
     def _fill_density(self, vol: torch.Tensor, planes: torch.Tensor, pam, cube: float, max_points: Optional[int]) -> None:
         b, n = vol.shape[0], vol.shape[1]

@@ -882,6 +882,64 @@ def ray_limits_box(ray_origins: torch.Tensor, ray_directions: torch.Tensor, box_
     return t_near, t_far
 
 
+def ray_limits_grid(ray_origins: torch.Tensor, ray_directions: torch.Tensor, occ):
+    """(t_near, t_far), each [B,R]: per ray the entry of the FIRST and the exit of the LAST occupied cell of the `OccupancyGrid`
+    ``occ`` it passes through at t ≥ 0 (t_near clamped below at 0: an origin inside an occupied cell starts at the origin), for
+    `raymarch_rays(..., t_near=, t_far=)`.  A ray that meets no occupied cell, misses the cube, has a zero direction or the box
+    kernel's 0 · inf case gets (+inf, −inf): an empty ray to the ray marcher.  Directions of any length, t in units of d.  The
+    grid's batch is B or 1 (one grid for every frame).  One launch (hfagp_ray_limits_grid: a 3-D DDA bounded at 3 G + 3 steps, every
+    t recomputed from its plane index); `cam_utils.ray_limits_grid` is its brute-force reference in torch."""
+    who = "ray_limits_grid"
+    for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
+        if _chk(t, f"{who}: {name}").dim() != 3 or t.shape[2] != 3:
+            raise RuntimeError(f"{who}: {name} must be [B, R, 3], got {tuple(t.shape)}")
+    if ray_origins.shape != ray_directions.shape:
+        raise RuntimeError(f"{who}: ray_origins {tuple(ray_origins.shape)} and ray_directions {tuple(ray_directions.shape)} differ")
+    bits = getattr(occ, "bits", None)
+    if bits is None:
+        raise RuntimeError(f"{who}: occ must be an OccupancyGrid, got {type(occ).__name__}")
+    b, r = ray_origins.shape[:2]
+    g = int(occ.resolution)
+    if not (bits.is_cuda and bits.device == ray_origins.device and bits.dtype == torch.int32 and bits.is_contiguous() and
+            tuple(bits.shape[1:]) == (g, g, (g + 31) // 32)):
+        raise RuntimeError(f"{who}: occ.bits must be a contiguous int32 tensor [B, {g}, {g}, {(g + 31) // 32}] on {ray_origins.device}, "
+                           f"got {bits.dtype} {tuple(bits.shape)} on {bits.device}")
+    if bits.shape[0] not in (1, b):
+        raise RuntimeError(f"{who}: the grid's batch must be B = {b} or 1, got {bits.shape[0]}")
+    t_near = torch.empty(b, r, device=ray_origins.device, dtype=torch.float32)
+    t_far = torch.empty(b, r, device=ray_origins.device, dtype=torch.float32)
+    if b * r:
+        nb, nr = (b, r) if bits.shape[0] == b else (1, b * r)          # one grid for all frames: the list as one frame
+        L.check(L.lib().hfagp_ray_limits_grid(_ptr(ray_origins), _ptr(ray_directions), _ptr(bits), _ptr(t_near), _ptr(t_far), nb, nr, g,
+                                              float(occ.cube_length), _stream()), who)
+    return t_near, t_far
+
+
+def occupancy_pack(vol: torch.Tensor, resolution: int, oversample: int, level: float, dilate: int) -> torch.Tensor:
+    """A density lattice → the bits of an `OccupancyGrid`: vol [B, n, n, n] with n = G·k + 1 points per axis (G = ``resolution``,
+    k = ``oversample`` ≥ 1; `density_grid`'s layout, iz fastest) → int32 [B, G, G, ceil(G/32)].  A cell is occupied iff one of the
+    (k+1)³ lattice points of its closed extent has !(v < level) — faces are shared with the neighbours, a NaN counts — and the grid
+    is then dilated by ``dilate`` cells (0 … 8; Chebyshev distance, clipped at the cube).  One launch (hfagp_occupancy_pack), no
+    atomics; `occupancy.occupancy_reference` is the same in torch."""
+    who = "occupancy_pack"
+    g, k, dilate = int(resolution), int(oversample), int(dilate)
+    if not 2 <= g <= 256:
+        raise ValueError(f"{who}: resolution must be in [2, 256], got {resolution}")
+    if k < 1 or g * k + 1 > 1025:
+        raise ValueError(f"{who}: oversample must be >= 1 with G * oversample + 1 <= 1025, got {oversample} at G = {g}")
+    if not 0 <= dilate <= 8:
+        raise ValueError(f"{who}: dilate must be in [0, 8], got {dilate}")
+    if math.isnan(float(level)):
+        raise ValueError(f"{who}: level is NaN")
+    n = g * k + 1
+    if _chk(vol, f"{who}: vol").dim() != 4 or tuple(vol.shape[1:]) != (n, n, n):
+        raise RuntimeError(f"{who}: vol must be [B, {n}, {n}, {n}] for G = {g}, oversample = {k}, got {tuple(vol.shape)}")
+    bits = torch.empty(vol.shape[0], g, g, (g + 31) // 32, device=vol.device, dtype=torch.int32)
+    if vol.shape[0]:
+        L.check(L.lib().hfagp_occupancy_pack(_ptr(vol), _ptr(bits), vol.shape[0], g, k, float(level), dilate, _stream()), who)
+    return bits
+
+
 def raymarch_normals(planes: torch.Tensor, state: torch.Tensor, *, cam2world: torch.Tensor, intrinsics: torch.Tensor,
                      u_strat: torch.Tensor, u_imp: torch.Tensor, dec_w0: torch.Tensor, dec_b0: torch.Tensor,
                      dec_w1: torch.Tensor, dec_b1: torch.Tensor, res: int, ray_start: float, ray_end: float, box_warp: float,

@@ -888,6 +888,35 @@ int hfagp_raymarch_rays_limits_bwd(const HfagpRayListBwdArgs* a, const HfagpRayL
 int hfagp_raymarch_rays_limits_bwd_rays(const HfagpRayListBwdArgs* a, const HfagpRayLimits* lim,
                                         float* d_origins, float* d_directions, void* stream);
 
+/* ------------------------------------------------------------------ occupancy grids for ray lists (additive to ABI 15)
+ * Tight per-ray limits and a miss test from a bit grid of the occupied space, as the input of the limits entry points above.
+ * The grid: G^3 cells (2 <= G <= 256) over the cube [-box_side/2, box_side/2]^3 in the world frame; cell (ix, iy, iz) is the box
+ * [plane(i), plane(i+1)] per axis, plane(i) = -box_side/2 + float(i) * (box_side / float(G)) in fp32, every operation rounded on
+ * its own.  bits [B][G][G][W] int32, W = (G + 31) / 32: bit (iz & 31) of word (iz >> 5) at [b][ix][iy]; padding bits are 0.
+ *
+ * hfagp_ray_limits_grid: rays [B][R][3] (directions of any length, t in units of d) against grid b of bits.  A cell COUNTS for a ray
+ * iff its bit is set and the ray's slab interval with it — the formula of hfagp_ray_limits_box on the cell's planes — has a positive
+ * chord at t >= 0: far_c > max(near_c, 0).  On an axis with d_k == 0 the ray lies in the half-open slab plane(i) <= o_k < plane(i+1)
+ * of one i; o_k <= plane(0) or o_k >= plane(G) there empties the ray (the box entry's 0 * inf case included).
+ *   t_near = min over the counting cells of max(near_c, 0)  — the entry of the FIRST occupied cell, 0 for an origin inside one;
+ *   t_far  = max over the counting cells of far_c           — the exit of the LAST occupied cell.
+ * A ray without a counting cell, with a zero direction, with a NaN component or with a limit that is not finite gets
+ * (+inf, -inf): an EMPTY ray.  Cells are found by a 3-D DDA bounded at 3 G + 3 steps; every reported t is recomputed from its
+ * integer plane index, never accumulated.  One launch, one thread per ray.  To use ONE grid for several frames pass B = 1 and
+ * R = the total ray count.
+ * HFAGP_EBADARG: a NULL pointer, B or R <= 0, B * R >= 2^31, G outside 2 .. 256, box_side not positive and finite.                */
+int hfagp_ray_limits_grid(const float* ray_origins, const float* ray_directions, const int32_t* bits, float* t_near, float* t_far,
+                          int32_t B, int32_t R, int32_t G, float box_side, void* stream);
+/* A density lattice -> bits.  volume [B][n][n][n] fp32, n = G * oversample + 1 lattice points per axis over the cube (z fastest;
+ * lattice point i * oversample lies on plane(i)): cell (ix, iy, iz) is occupied iff one of the (oversample + 1)^3 lattice points of
+ * its closed extent has !(v < level) — faces are shared with the neighbours (conservative), a NaN is occupied — and its bit is
+ * set iff a cell within Chebyshev distance `dilate` of it (clipped at the cube) is occupied.  bits as above: written, padding 0.
+ * One launch, no atomics: a wave owns the words of one [b][ix][iy] column and writes them with plain stores.
+ * HFAGP_EBADARG: a NULL pointer, B <= 0, G outside 2 .. 256, oversample < 1 or G * oversample + 1 > 1025, dilate outside 0 .. 8,
+ * level NaN.                                                                                                                   */
+int hfagp_occupancy_pack(const float* volume, int32_t* bits, int32_t B, int32_t G, int32_t oversample, float level,
+                         int32_t dilate, void* stream);
+
 /* ------------------------------------------------------------------ per-sample compositing weights of ray lists (additive to ABI 15)
  * The distribution along every ray of a list, which the entry points above compute and reduce to one number per ray: with
  * S = Sc + Sf samples sorted by depth, t_0 <= .. <= t_{S-1}, the compositing weight w_e = alpha_e T_e of interval [t_e, t_{e+1}],
