@@ -702,233 +702,3 @@ class SampleMixedNormalFn(torch.autograd.Function):
         ctx.tape = ctx.planes = None
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
         return (d_ws, None, None) + pgrads
-
-
-class RenderRaysFn(torch.autograd.Function):
-    """`TriPlaneGenerator.render_rays` under grad: inputs ws, ray_origins, ray_directions, u_strat, u_imp, gen, *parameters; outputs
-    feature [B,R,32], depth [B,R] (clamped to the call's global sample range), mask [B,R].  A backbone forward with a tape, then one
-    list launch (ops.raymarch_rays); backward = ops.raymarch_rays_bwd into d_planes (with the decoder gradients when parameters
-    require grad), ops.raymarch_rays_bwd_rays only when the rays require grad, then the backbone backward `synthesis` runs.
-    ``limits``: None, or the per-ray depth limits (t_near, t_far) [B,R] — detached tensors, no autograd edge: the three launches
-    then carry them, d origins / d directions are the derivative with the limits held fixed (EG3D's autograd would also move the
-    sample positions through a box intersection: left out on purpose, as the importance depths are), an empty ray gets exactly
-    zero gradient and the g_depth it receives is dropped."""
-    @staticmethod
-    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params):
-        return RenderRaysFn._forward(ctx, False, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params)
-
-    @staticmethod
-    def _forward(ctx, samples, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params):
-        """``samples`` (RenderRaysSamplesFn): the launch is ops.raymarch_rays(samples=True) and two more results follow the three —
-        sample_weights [B,R,S-1] and sample_depths [B,R,S]."""
-        from .generator import RAY_STATE_CAP_BYTES
-        ws_c = ws.detach().float().contiguous()
-        o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
-        b, r = o.shape[0], o.shape[1]
-        tape = []
-        with torch.no_grad():
-            planes = gen.backbone_planes(ws_c, tape)
-            pam = getattr(gen, "_planes_absmax", None)
-            sc, sf = u_strat.shape[-1], u_imp.shape[-1]
-            # (the per-sample results for the compositing adjoint, as a differentiated `synthesis` keeps them; skipped above the cap)
-            state = ops.raymarch_rays_state(b, r, sc, sf, planes.device) if b * r * (sc + sf) * 140 <= RAY_STATE_CAP_BYTES else None
-            lim = {} if limits is None else dict(t_near=limits[0], t_far=limits[1])
-            smp = dict(samples=True) if samples else {}
-            feat, depth, wsum, tmm, *ws_ts = gen._timed("raymarch_rays", float(b), ops.raymarch_rays, planes, o, d, u_strat, u_imp,
-                                                        planes_absmax=pam, state=state, **lim, **smp, **gen._rays_kwargs())
-            if limits is None:
-                depth_range = ops.depth_range(tmm)
-                depth = ops.depth_clamp_(depth, tmm)
-            else:
-                depth_range = ops.depth_range(tmm, empty_rays=True)
-                depth = ops.depth_clamp_(depth, tmm, empty_rays=True)
-        ctx.lim = lim
-        ctx.gen, ctx.tape, ctx.ws_c, ctx.planes, ctx.pam, ctx.state = gen, tape, ws_c, planes, pam, state
-        ctx.rays, ctx.uniforms, ctx.depth_range = (o, d), (u_strat, u_imp), depth_range
-        ctx.params = params
-        ctx.pg = any(p.requires_grad for p in params)
-        ctx.ws_shape, ctx.ray_dtypes = ws.shape, (ray_origins.dtype, ray_directions.dtype)
-        ctx.set_materialize_grads(False)
-        return (feat, depth, wsum) + tuple(ws_ts)
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_feat, g_depth, g_wsum):
-        return RenderRaysFn._backward(ctx, g_feat, g_depth, g_wsum)
-
-    @staticmethod
-    def _backward(ctx, g_feat, g_depth, g_wsum, g_weights=None):
-        gen = ctx.gen
-        if ctx.tape is None:
-            raise RuntimeError("TriPlaneGenerator.render_rays: backward called a second time — the saved activations are released "
-                               "by the first backward pass (retain_graph is not supported)")
-        none = (None,) * (7 + len(ctx.params))
-        if g_feat is None and g_depth is None and g_wsum is None and g_weights is None:
-            return none
-        planes = ctx.planes
-        b, dev = planes.shape[0], planes.device
-        (o, d), (u_strat, u_imp) = ctx.rays, ctx.uniforms
-        r = o.shape[1]
-        d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
-        bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
-        g_feat = None if g_feat is None else g_feat.float().contiguous()
-        geom = {}
-        if g_depth is not None:
-            geom.update(g_depth=g_depth.float().reshape(b, r).contiguous(), depth_range=ctx.depth_range)
-        if g_wsum is not None:
-            geom.update(g_wsum=g_wsum.float().reshape(b, r).contiguous())
-        if g_weights is not None:        # (RenderRaysSamplesFn; the records carry the term on to the rays' pass)
-            geom.update(g_weights=g_weights.float().reshape(b, r, -1).contiguous())
-        need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        rec_out = [] if need_rays else None
-        rb = gen._timed("raymarch_rays_bwd", float(b), ops.raymarch_rays_bwd, g_feat, planes, o, d, u_strat, u_imp,
-                        decoder_grads=ctx.pg, planes_absmax=ctx.pam, state=ctx.state, rec_out=rec_out, **geom, **ctx.lim,
-                        **gen._rays_kwargs())
-        d_o = d_d = None
-        if need_rays:        # the per-ray record of the camera gradient is itself the answer; autograd carries it on to the camera model
-            d_o, d_d = gen._timed("raymarch_rays_bwd_rays", float(b), ops.raymarch_rays_bwd_rays, g_feat, planes, rec_out[0], o, d,
-                                  u_strat, u_imp, planes_absmax=ctx.pam, **ctx.lim, **gen._rays_kwargs())
-            d_o = d_o.to(ctx.ray_dtypes[0]) if ctx.needs_input_grad[1] else None
-            d_d = d_d.to(ctx.ray_dtypes[1]) if ctx.needs_input_grad[2] else None
-        if ctx.pg:
-            d_planes, dec = rb
-            for prm, g in zip(gen.decoder_params(), dec):
-                bw._acc(prm, g)
-        else:
-            d_planes = rb
-        _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
-        ctx.tape = ctx.planes = ctx.state = None
-        pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return (d_ws, d_o, d_d, None, None, None, None) + pgrads
-
-
-class RenderRaysNormalFn(torch.autograd.Function):
-    """`TriPlaneGenerator.render_rays(normals=True / normal_grad=True)` under grad: the inputs of RenderRaysFn with
-    ``normal_ray_grad`` (a bool) in front of the parameters; outputs feature, depth, mask and normal [B,R,3].  The forward is
-    RenderRaysFn's plus one launch (ops.raymarch_rays_normals) on the state it kept.  Backward, when the loss used the normals:
-    ops.raymarch_rays_bwd first, and only if feature, depth or mask carry a gradient (on mirrored planes it overwrites plane 2);
-    then ops.raymarch_rays_normals_bwd into the same d_planes and decoder gradients (fresh zeros for a normals-only loss); then the
-    rays' passes when the rays require grad — the colour term's, then with ``normal_ray_grad`` the normal term's added to it;
-    then the one backbone backward.  A loss that ignores the normals runs RenderRaysFn's backward as it stands."""
-    @staticmethod
-    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad, *params):
-        return RenderRaysNormalFn._forward(ctx, False, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad,
-                                           *params)
-
-    @staticmethod
-    def _forward(ctx, samples, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad, *params):
-        feat, depth, wsum, *ws_ts = RenderRaysFn._forward(ctx, samples, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits,
-                                                          *params)
-        (o, d), b = ctx.rays, ws.shape[0]
-        with torch.no_grad():
-            if ctx.state is None:        # above RAY_STATE_CAP_BYTES (a detached map: render_rays refuses normal_grad there)
-                from .generator import RAY_STATE_CAP_BYTES
-                per_row = b * (u_strat.shape[-1] + u_imp.shape[-1]) * 140
-                normal = gen._render_rays_normals_chunked(ctx.planes, o, d, u_strat, u_imp, ctx.pam, ctx.lim,
-                                                          max(1, RAY_STATE_CAP_BYTES // per_row))[4]
-            else:
-                normal = gen._timed("raymarch_rays_normals", float(b), ops.raymarch_rays_normals, ctx.planes, ctx.state,
-                                    ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=ctx.pam, **ctx.lim,
-                                    **gen._rays_kwargs())
-        ctx.normal_ray_grad = bool(normal_ray_grad)
-        return (feat, depth, wsum, normal) + tuple(ws_ts)
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_feat, g_depth, g_wsum, g_normal):
-        return RenderRaysNormalFn._backward(ctx, g_feat, g_depth, g_wsum, g_normal)
-
-    @staticmethod
-    def _backward(ctx, g_feat, g_depth, g_wsum, g_normal, g_weights=None):
-        if g_normal is None:             # the loss did not use 'normal': no launch of its own
-            grads = RenderRaysFn._backward(ctx, g_feat, g_depth, g_wsum, g_weights)
-            return grads[:7] + (None,) + grads[7:]
-        gen = ctx.gen
-        if ctx.tape is None:
-            raise RuntimeError("TriPlaneGenerator.render_rays: backward called a second time — the saved activations are released "
-                               "by the first backward pass (retain_graph is not supported)")
-        if ctx.state is None:
-            raise RuntimeError("TriPlaneGenerator.render_rays(normal_grad=True): the forward kept no per-sample state "
-                               "(RAY_STATE_CAP_BYTES)")
-        planes = ctx.planes
-        b, dev = planes.shape[0], planes.device
-        (o, d), (u_strat, u_imp) = ctx.rays, ctx.uniforms
-        r = o.shape[1]
-        d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
-        bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
-        g_feat = None if g_feat is None else g_feat.float().contiguous()
-        g_nrm = g_normal.float().reshape(b, r, 3).contiguous()
-        geom = {}
-        if g_depth is not None:
-            geom.update(g_depth=g_depth.float().reshape(b, r).contiguous(), depth_range=ctx.depth_range)
-        if g_wsum is not None:
-            geom.update(g_wsum=g_wsum.float().reshape(b, r).contiguous())
-        if g_weights is not None:        # the weight term goes with the colour term's launch, which then runs for it alone too
-            geom.update(g_weights=g_weights.float().reshape(b, r, -1).contiguous())
-        colour = g_feat is not None or bool(geom)
-        need_rays = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        d_planes = dec = None
-        rec_out = [] if need_rays else None
-        if colour:
-            rb = gen._timed("raymarch_rays_bwd", float(b), ops.raymarch_rays_bwd, g_feat, planes, o, d, u_strat, u_imp,
-                            decoder_grads=ctx.pg, planes_absmax=ctx.pam, state=ctx.state, rec_out=rec_out, **geom, **ctx.lim,
-                            **gen._rays_kwargs())
-            d_planes, dec = rb if ctx.pg else (rb, None)
-        # after raymarch_rays_bwd: that call overwrites plane 2 on mirrored planes, this one adds to every plane at its true texels
-        d_planes, dec = gen._timed("raymarch_rays_normals_bwd", float(b), ops.raymarch_rays_normals_bwd, g_nrm, planes, ctx.state,
-                                   ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=ctx.pam,
-                                   d_planes=d_planes, decoder_grads=ctx.pg, dec_out=dec, **ctx.lim, **gen._rays_kwargs())
-        d_o = d_d = None
-        if need_rays:
-            if colour:
-                d_o, d_d = gen._timed("raymarch_rays_bwd_rays", float(b), ops.raymarch_rays_bwd_rays, g_feat, planes, rec_out[0], o, d,
-                                      u_strat, u_imp, planes_absmax=ctx.pam, **ctx.lim, **gen._rays_kwargs())
-            if ctx.normal_ray_grad:      # the normal term joins the colour term's records (written into fresh ones without it)
-                d_o, d_d = gen._timed("raymarch_rays_normals_bwd_rays", float(b), ops.raymarch_rays_normals_bwd_rays, g_nrm, planes,
-                                      ctx.state, d_origins=d_o, d_directions=d_d, ray_origins=o, ray_directions=d, u_strat=u_strat,
-                                      u_imp=u_imp, planes_absmax=ctx.pam, **ctx.lim, **gen._rays_kwargs())
-            if d_o is not None:
-                d_o, d_d = (d_o.to(ctx.ray_dtypes[0]) if ctx.needs_input_grad[1] else None,
-                            d_d.to(ctx.ray_dtypes[1]) if ctx.needs_input_grad[2] else None)
-        if ctx.pg:
-            for prm, g in zip(gen.decoder_params(), dec):
-                bw._acc(prm, g)
-        _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
-        ctx.tape = ctx.planes = ctx.state = None
-        pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return (d_ws, d_o, d_d, None, None, None, None, None) + pgrads
-
-
-class RenderRaysSamplesFn(torch.autograd.Function):
-    """`TriPlaneGenerator.render_rays(samples=True)` under grad: RenderRaysFn with two more outputs, sample_weights [B,R,S-1] (the
-    compositing weights w_e = alpha_e T_e of the intervals between the depth-sorted samples) and sample_depths [B,R,S] (marked
-    non-differentiable: importance depths are detached as in EG3D, stratified ones are constants).  The gradient of sample_weights
-    is one more addend of pass 1's adjoint in the one ops.raymarch_rays_bwd launch (g_weights=), which runs even when nothing else
-    carries a gradient; the rays' pass reads that launch's records, so the rays get the term with no launch of its own."""
-    @staticmethod
-    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params):
-        out = RenderRaysFn._forward(ctx, True, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, *params)
-        ctx.mark_non_differentiable(out[4])
-        return out
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_feat, g_depth, g_wsum, g_weights, _g_depths):
-        return RenderRaysFn._backward(ctx, g_feat, g_depth, g_wsum, g_weights)
-
-
-class RenderRaysNormalSamplesFn(torch.autograd.Function):
-    """`render_rays(samples=True)` together with `normals=` / `normal_grad=` / `normal_ray_grad=`: RenderRaysNormalFn with the two
-    outputs of RenderRaysSamplesFn behind 'normal'.  The weight gradient joins the colour term's launch (ops.raymarch_rays_bwd),
-    which precedes the normal term's as in RenderRaysNormalFn."""
-    @staticmethod
-    def forward(ctx, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad, *params):
-        out = RenderRaysNormalFn._forward(ctx, True, ws, ray_origins, ray_directions, u_strat, u_imp, gen, limits, normal_ray_grad,
-                                          *params)
-        ctx.mark_non_differentiable(out[5])
-        return out
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_feat, g_depth, g_wsum, g_normal, g_weights, _g_depths):
-        return RenderRaysNormalFn._backward(ctx, g_feat, g_depth, g_wsum, g_normal, g_weights)

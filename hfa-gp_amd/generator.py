@@ -1125,48 +1125,6 @@ class TriPlaneGenerator(nn.Module):
                     decoder_lr_mul=cfg.decoder_lr_mul, plane_axes=ops._plane_axes_id(cfg.plane_axes), white_back=cfg.white_back,
                     decoder_precision=cfg.decoder_precision)
 
-    @staticmethod
-    def _render_rays_empty(b: int, r: int, dev, zero, limits: bool, normals: bool, normal_grad: bool,
-                           samples: int = 0) -> Dict[str, torch.Tensor]:
-        """`render_rays` of no rays (B = 0 or R = 0): the dict of a call with these keywords, nothing launched.  ``zero``: 0.0, or
-        under grad a zero scalar that hangs on the call's inputs and keeps their autograd edges."""
-        feat = torch.zeros(b, r, 32, device=dev) + zero
-        out = {"feature": feat, "rgb": feat[..., :3], "depth": torch.zeros(b, r, device=dev) + zero,
-               "mask": torch.zeros(b, r, device=dev) + zero}
-        if limits:
-            out["valid"] = torch.zeros(b, r, device=dev, dtype=torch.bool)
-        if normals:          # (detached unless normal_grad, as in a call with rays)
-            out["normal"] = torch.zeros(b, r, 3, device=dev) + (zero if normal_grad else 0.0)
-        if samples:          # (S = Sc + Sf of the config; the depths are detached, as in a call with rays)
-            out["sample_weights"] = torch.zeros(b, r, samples - 1, device=dev) + zero
-            out["sample_depths"] = torch.zeros(b, r, samples, device=dev)
-        return out
-
-    def _render_rays_normals_chunked(self, planes, o, d, u_strat, u_imp, planes_absmax, lim: dict, rays: int, samples: bool = False):
-        """`ops.raymarch_rays` + `ops.raymarch_rays_normals` over chunks of `rays` rays per frame through one state buffer of that
-        size: the per-sample state of the whole list would exceed RAY_STATE_CAP_BYTES.  A list may be cut at any ray; every ray is
-        computed as in the whole-list launch (the decoder's bound on |planes| is the call's, taken once), so the five results —
-        feat, depth (unclamped), wsum, tminmax, normal — equal the unchunked ones bit for bit.  ``samples``: sample_weights and
-        sample_depths of `ops.raymarch_rays(samples=True)` follow as results six and seven."""
-        cfg = self.cfg
-        b, r = o.shape[0], o.shape[1]
-        sc, sf = cfg.depth_resolution, cfg.depth_resolution_importance
-        planes_absmax = ops._decoder_bound(planes, cfg.decoder_precision, planes_absmax)
-        u_imp = u_imp.view(b, r, sf)
-        buf = ops.raymarch_rays_state(b, min(rays, r), sc, sf, planes.device)
-        parts = []
-        for r0 in range(0, r, rays):
-            n = min(rays, r - r0)
-            cut = lambda t: t[:, r0:r0 + n].contiguous()      # noqa: E731
-            state = buf.view(-1)[:b * n * (sc + sf) * 35].view(b, n, (sc + sf) * 35)
-            oc, dc, us, ui = cut(o), cut(d), cut(u_strat), cut(u_imp).view(b * n, sf)
-            lc = {k: cut(t) for k, t in lim.items()}
-            out = ops.raymarch_rays(planes, oc, dc, us, ui, planes_absmax=planes_absmax, state=state, samples=samples, **lc,
-                                    **self._rays_kwargs())
-            parts.append(out[:4] + (ops.raymarch_rays_normals(planes, state, ray_origins=oc, ray_directions=dc, u_strat=us, u_imp=ui,
-                                                          planes_absmax=planes_absmax, **lc, **self._rays_kwargs()),) + out[4:])
-        return tuple(torch.cat(t, 1) for t in zip(*parts))
-
     def render_rays(self, ws: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor,
                     u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
                     noise_mode: str = "const", t_near=None, t_far=None, ray_limits=None, normals: bool = False,
@@ -1223,193 +1181,9 @@ class TriPlaneGenerator(nn.Module):
         carries the depth an empty ray gets), and the results are scattered back — the forward entries are bit-identical to
         `compact=False`, since a ray's result depends on its own inputs only; the rays' gradient comes through the gather from torch
         autograd.  It costs one host sync (R' is a Python int); no valid ray at all launches nothing."""
-        if noise_mode != "const":
-            raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
-        normal_grad = bool(normal_grad or normal_ray_grad)
-        normals = bool(normals or normal_grad)
-        from .occupancy import OccupancyGrid
-        occ = ray_limits if isinstance(ray_limits, OccupancyGrid) else None
-        if ray_limits is not None and occ is None and not (isinstance(ray_limits, str) and ray_limits == "box"):
-            raise ValueError(f"TriPlaneGenerator.render_rays: ray_limits must be None or 'box' or an OccupancyGrid, got {ray_limits!r}")
-        if (t_near is None) != (t_far is None):
-            raise ValueError("TriPlaneGenerator.render_rays: t_near and t_far go together (both or neither)")
-        if ray_limits is not None and t_near is not None:
-            raise ValueError("TriPlaneGenerator.render_rays: ray_limits='box' / an OccupancyGrid and explicit t_near / t_far are "
-                             "mutually exclusive")
-        if compact and ray_limits is None and t_near is None:
-            raise ValueError("TriPlaneGenerator.render_rays: compact=True needs ray limits (t_near / t_far or ray_limits=): without "
-                             "them every ray is marched")
-        if occ is not None:
-            if occ.batch not in (1, ws.shape[0]):
-                raise ValueError(f"TriPlaneGenerator.render_rays: the occupancy grid's batch must be B = {ws.shape[0]} or 1, got "
-                                 f"{occ.batch}")
-            if float(occ.cube_length) != float(self.cfg.box_warp):
-                raise ValueError(f"TriPlaneGenerator.render_rays: the occupancy grid's cube_length {occ.cube_length} differs from "
-                                 f"cfg.box_warp = {self.cfg.box_warp}")
-            if not occ.bits.is_cuda or occ.bits.device != ws.device:
-                raise RuntimeError(f"TriPlaneGenerator.render_rays: the occupancy grid lives on {occ.bits.device}, ws on {ws.device}; "
-                                   f"the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
-        for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
-            if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] != ws.shape[0]:
-                raise ValueError(f"expected {name} [B, R, 3] for ws of batch {ws.shape[0]}, got {tuple(t.shape)}")
-            if not t.is_floating_point():
-                raise TypeError(f"TriPlaneGenerator.render_rays: {name} must be a floating-point tensor, got {t.dtype}")
-        if ray_origins.shape != ray_directions.shape:
-            raise ValueError(f"ray_directions {tuple(ray_directions.shape)} must match ray_origins {tuple(ray_origins.shape)}")
-        if normal_grad and not normal_ray_grad and torch.is_grad_enabled() and (ray_origins.requires_grad or
-                                                                                 ray_directions.requires_grad):
-            raise NotImplementedError("TriPlaneGenerator.render_rays(normal_grad=True): the rays' gradient of the normal term is opt-in "
-                                      "(ray_origins / ray_directions require grad): pass normal_ray_grad=True for it, detach the rays, "
-                                      "or use normals=True for a detached map")
-        self._query_guard("render_rays", ws, differentiable=True)
-        if not (ray_origins.is_cuda and ray_directions.is_cuda):
-            raise RuntimeError("TriPlaneGenerator.render_rays: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
-        cfg = self.cfg
-        b, r = ray_origins.shape[0], ray_origins.shape[1]
-        dev = ws.device
-        limits = None              # (t_near, t_far) fp32 [B,R] on the device, or "box": computed next to the launch
-        if t_near is not None:
-            limits = []
-            for name, t in (("t_near", t_near), ("t_far", t_far)):
-                if isinstance(t, torch.Tensor):
-                    if t.shape != (b, r):
-                        raise ValueError(f"TriPlaneGenerator.render_rays: {name} must be [B, R] = [{b}, {r}] or a float, got "
-                                         f"{tuple(t.shape)}")
-                    if not t.is_floating_point():
-                        raise TypeError(f"TriPlaneGenerator.render_rays: {name} must be a floating-point tensor, got {t.dtype}")
-                    if torch.is_grad_enabled() and t.requires_grad:
-                        raise NotImplementedError(f"TriPlaneGenerator.render_rays: {name} requires grad, but the ray limits are not "
-                                                  f"differentiated (pass {name}.detach())")
-                    if not t.is_cuda:
-                        raise RuntimeError("TriPlaneGenerator.render_rays: the MI355X path needs CUDA/ROCm tensors; there is no CPU "
-                                           "fallback")
-                    limits.append(t.detach().float().contiguous())
-                else:
-                    limits.append(torch.full((b, r), float(t), device=dev, dtype=torch.float32))
-            limits = tuple(limits)
-        elif ray_limits is not None:
-            limits = "box" if occ is None else "grid"
-        params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
-        grad = torch.is_grad_enabled() and (ws.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad or
-                                            any(p.requires_grad for p in params))
-        if b == 0 or r == 0:
-            zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0      # keeps the autograd edges
-            return self._render_rays_empty(b, r, dev, zero, limits is not None, normals, normal_grad,
-                                           cfg.depth_resolution + cfg.depth_resolution_importance if samples else 0)
-        state_bytes = b * r * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
-        if grad and normal_grad and state_bytes > RAY_STATE_CAP_BYTES and not compact:      # (compact: the check of the inner call)
-            raise RuntimeError(f"TriPlaneGenerator.render_rays(normal_grad=True): the backward of 'normal' reads the ray marcher's "
-                               f"per-sample state, {state_bytes} bytes for {b} x {r} rays, above RAY_STATE_CAP_BYTES = "
-                               f"{RAY_STATE_CAP_BYTES}; {RAY_STATE_CAP_BYTES // (state_bytes // (b * r))} rays fit")
-        if limits == "box":
-            with torch.no_grad():
-                limits = ops.ray_limits_box(ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous(),
-                                            cfg.box_warp)
-        elif limits == "grid":
-            with torch.no_grad():
-                limits = ops.ray_limits_grid(ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous(),
-                                             occ)
-        if u_strat is None:
-            u_strat = torch.rand(b, r, cfg.depth_resolution, device=dev)
-        if u_imp is None:
-            u_imp = torch.rand(b * r, cfg.depth_resolution_importance, device=dev)
-        u_strat, u_imp = u_strat.detach().float().reshape(b, r, -1).contiguous(), u_imp.detach().float().contiguous()
-        if compact:
-            out = self._render_rays_compact(ws, ray_origins, ray_directions, u_strat, u_imp, limits, grad,
-                                            dict(normals=normals, normal_grad=normal_grad, normal_ray_grad=normal_ray_grad,
-                                                 samples=samples))
-            if out is not None:
-                return out
-        if grad:
-            if getattr(self, "_grad_sink", None) is not None or getattr(self, "_grad_inplace", False):
-                raise RuntimeError("TriPlaneGenerator.render_rays under grad inside a trainer step scope: its backward is a second "
-                                   "backbone pass and would release every parameter to the gradient sink twice")
-            if normals:
-                from .autograd import RenderRaysNormalFn, RenderRaysNormalSamplesFn
-                fn = RenderRaysNormalSamplesFn if samples else RenderRaysNormalFn
-                feat, depth, mask, normal, *ws_ts = fn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits,
-                                                             normal_ray_grad, *params)
-                if not normal_grad:
-                    normal = normal.detach()
-            elif samples:
-                from .autograd import RenderRaysSamplesFn
-                feat, depth, mask, *ws_ts = RenderRaysSamplesFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits,
-                                                                      *params)
-            else:
-                from .autograd import RenderRaysFn
-                feat, depth, mask = RenderRaysFn.apply(ws, ray_origins, ray_directions, u_strat, u_imp, self, limits, *params)
-        else:
-            with torch.no_grad():
-                planes, pam = self._query_planes(ws)
-                lim = {} if limits is None else dict(t_near=limits[0], t_far=limits[1])
-                o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
-                smp = dict(samples=True) if samples else {}
-                if normals and state_bytes > RAY_STATE_CAP_BYTES:        # above the cap: march and take the normals in ray chunks
-                    feat, depth, mask, tmm, normal, *ws_ts = self._render_rays_normals_chunked(
-                        planes, o, d, u_strat, u_imp, pam, lim, max(1, RAY_STATE_CAP_BYTES // (state_bytes // r)), **smp)
-                else:
-                    state = None
-                    if normals:
-                        state = ops.raymarch_rays_state(b, r, cfg.depth_resolution, cfg.depth_resolution_importance, dev)
-                    feat, depth, mask, tmm, *ws_ts = ops.raymarch_rays(planes, o, d, u_strat, u_imp, planes_absmax=pam, state=state,
-                                                                       **lim, **smp, **self._rays_kwargs())
-                    if normals:
-                        normal = self._timed("raymarch_rays_normals", float(b), ops.raymarch_rays_normals, planes, state,
-                                             ray_origins=o, ray_directions=d, u_strat=u_strat, u_imp=u_imp, planes_absmax=pam, **lim,
-                                             **self._rays_kwargs())
-                depth = ops.depth_clamp_(depth, tmm) if limits is None else ops.depth_clamp_(depth, tmm, empty_rays=True)
-        out = {"feature": feat, "rgb": feat[..., :3], "depth": depth, "mask": mask}
-        if normals:
-            out["normal"] = normal
-        if samples:
-            out["sample_weights"], out["sample_depths"] = ws_ts[0], ws_ts[1].detach()
-        if limits is not None:
-            from .cam_utils import ray_limits_valid
-            out["valid"] = ray_limits_valid(*limits)
-        return out
-
-    def _render_rays_compact(self, ws, ray_origins, ray_directions, u_strat, u_imp, limits, grad: bool, kw: dict):
-        """`render_rays(compact=True)` once the limits are tensors: the valid rays of every frame first (stable), the first R' + 1 of
-        them marched by a plain `render_rays(t_near=, t_far=)` call, the results scattered back over the empty-ray values.  None when
-        a frame has no empty ray (nothing to leave out: the caller goes on as without the keyword).  The + 1: an empty ray is not
-        marched, and its 'depth' is what every empty ray of the call gets — the upper end of the clamp range over the valid rays,
-        which are the same rays in both calls."""
-        from .cam_utils import ray_limits_valid
-        cfg = self.cfg
-        b, r = ray_origins.shape[:2]
-        dev = ws.device
-        valid = ray_limits_valid(*limits)
-        n_valid = int(valid.sum(1).max())                  # (the one host sync)
-        if n_valid == r:
-            return None
-        s = cfg.depth_resolution + cfg.depth_resolution_importance
-        if n_valid == 0:
-            zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0
-            out = self._render_rays_empty(b, r, dev, zero, True, kw["normals"], kw["normal_grad"], s if kw["samples"] else 0)
-            out["feature"] = out["feature"] + (1.0 if cfg.white_back else -1.0)
-            out["rgb"] = out["feature"][..., :3]
-            return out
-        m = n_valid + 1
-        idx = torch.argsort((~valid).to(torch.uint8), dim=1, stable=True)[:, :m]              # [B, m]: the valid rays, then empty ones
-        idx3 = idx[..., None].expand(b, m, 3)
-        sf = u_imp.shape[-1]
-        sub = self.render_rays(ws, ray_origins.gather(1, idx3), ray_directions.gather(1, idx3),
-                               u_strat.gather(1, idx[..., None].expand(b, m, u_strat.shape[-1])),
-                               u_imp.view(b, r, sf).gather(1, idx[..., None].expand(b, m, sf)).reshape(b * m, sf),
-                               t_near=limits[0].gather(1, idx), t_far=limits[1].gather(1, idx), **kw)
-        background = 1.0 if cfg.white_back else -1.0
-        fill = {"feature": background, "depth": sub["depth"][0, -1].detach(), "mask": 0.0, "normal": 0.0, "sample_weights": 0.0,
-                "sample_depths": 0.0}
-        out = {}
-        for key, val in sub.items():
-            if key in ("rgb", "valid"):
-                continue
-            full = torch.empty(b, r, *val.shape[2:], device=dev, dtype=val.dtype)
-            full[...] = fill[key]
-            out[key] = full.scatter(1, idx.reshape(b, m, *([1] * (val.dim() - 2))).expand_as(val), val)
-        out["rgb"] = out["feature"][..., :3]
-        out["valid"] = valid
-        return out
+        from . import ray_list
+        return ray_list.render_rays(self, ws, ray_origins, ray_directions, u_strat, u_imp, noise_mode, t_near, t_far, ray_limits,
+                                    normals, normal_grad, normal_ray_grad, samples, compact)
 
     def sample(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], z: torch.Tensor, c: torch.Tensor,
                truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:

@@ -719,12 +719,20 @@ def _ray_args(who: str, f, planes, cam2world, intrinsics, u_strat, u_imp, dec_w0
         raise RuntimeError(f"{who}: state must be [B, R, {(sc + sf) * 35}] (raymarch_state), got {tuple(state.shape)}")
     for name, t in (("cam2world", cam2world), ("intrinsics", intrinsics), ("u_strat", u_strat), ("u_imp", u_imp)):
         setattr(f, name, _ptr(_chk(t, f"{who}: {name}")))
+    _fill_scene(who, f, planes, state, (b, h, w, res, sc, sf), (dec_w0, dec_b0, dec_w1, dec_b1), ray_start, ray_end, box_warp,
+                decoder_lr_mul, plane_axes, white_back, decoder_precision, planes_absmax)
+    return b, h, w, r, sc, sf
+
+
+def _fill_scene(who: str, f, planes, state, dims, dec, ray_start: float, ray_end: float, box_warp: float, decoder_lr_mul: float,
+                plane_axes, white_back: bool, decoder_precision: str, planes_absmax):
+    """What the RaymarchArgs ``f`` of a grid and of a list have in common: planes, state, the decoder ``dec`` with its bound,
+    ``dims`` = (B, H, W, res, Sc, Sf) and the scalars."""
     f.planes, f.state = _ptr(planes), _ptr(state)
-    _fill_decoder(who, f, planes, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_precision, planes_absmax)
-    f.B, f.H, f.W, f.res, f.Sc, f.Sf = b, h, w, res, sc, sf
+    _fill_decoder(who, f, planes, dec, decoder_precision, planes_absmax)
+    f.B, f.H, f.W, f.res, f.Sc, f.Sf = dims
     f.plane_axes, f.white_back = _plane_axes_id(plane_axes), int(white_back)
     f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
-    return b, h, w, r, sc, sf
 
 
 def _ray_list_args(who: str, l, planes, ray_origins, ray_directions, u_strat, u_imp, dec_w0, dec_b0, dec_w1, dec_b1, ray_start: float,
@@ -750,11 +758,8 @@ def _ray_list_args(who: str, l, planes, ray_origins, ray_directions, u_strat, u_
         raise RuntimeError(f"{who}: state must be [B, R, {(sc + sf) * 35}] (raymarch_rays_state), got {tuple(state.shape)}")
     for name, t in (("u_strat", u_strat), ("u_imp", u_imp)):
         setattr(f, name, _ptr(_chk(t, f"{who}: {name}")))
-    f.planes, f.state = _ptr(planes), _ptr(state)
-    _fill_decoder(who, f, planes, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_precision, planes_absmax)
-    f.B, f.H, f.W, f.res, f.Sc, f.Sf = b, h, w, 0, sc, sf
-    f.plane_axes, f.white_back = _plane_axes_id(plane_axes), int(white_back)
-    f.ray_start, f.ray_end, f.box_warp, f.decoder_lr_mul = ray_start, ray_end, box_warp, decoder_lr_mul
+    _fill_scene(who, f, planes, state, (b, h, w, 0, sc, sf), (dec_w0, dec_b0, dec_w1, dec_b1), ray_start, ray_end, box_warp,
+                decoder_lr_mul, plane_axes, white_back, decoder_precision, planes_absmax)
     l.ray_origins, l.ray_directions, l.R = _ptr(ray_origins), _ptr(ray_directions), r
     if (t_near is None) != (t_far is None):
         raise RuntimeError(f"{who}: t_near and t_far go together (both or neither)")
@@ -1937,6 +1942,52 @@ def depth_range(tminmax: torch.Tensor, empty_rays: bool = False) -> torch.Tensor
     return torch.where(torch.isfinite(rng), rng, torch.zeros_like(rng)) if empty_rays else rng
 
 
+def _check_upstream(who: str, b: int, r: int, g_feat, g_depth, g_wsum, depth_range) -> None:
+    """The upstream gradients of `raymarch_bwd` / `raymarch_rays_bwd`: each None or a checked tensor of its shape."""
+    if g_feat is not None and _chk(g_feat, f"{who}: g_feat").shape != (b, r, 32):
+        raise RuntimeError(f"{who}: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
+    for t, name in ((g_depth, "g_depth"), (g_wsum, "g_wsum")):
+        if t is not None and _chk(t, f"{who}: {name}").shape != (b, r):
+            raise RuntimeError(f"{who}: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
+    if depth_range is not None and _chk(depth_range, f"{who}: depth_range").shape != (2,):
+        raise RuntimeError(f"{who}: depth_range must be [2] (ops.depth_range), got {tuple(depth_range.shape)}")
+
+
+def _geom_grads(g_depth, g_wsum, depth_range):
+    """The RaymarchGeomGrads of a backward call, or None when it has neither a depth nor an opacity gradient."""
+    if g_depth is None and g_wsum is None and depth_range is None:
+        return None
+    gg = L.RaymarchGeomGrads()
+    gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
+    return gg
+
+
+def _rows_scratch(who: str, a, need: int, device, divisible: bool, what: str):
+    """The scratch plan of pass 2 as sort + gather for the RaymarchBwdArgs ``a``, whose call needs ``need`` bytes (0: the sort does
+    not take ``what``) → (cap, None) when the call needs more than `rows_scratch_cap()` allows and is ``divisible``: the caller runs
+    it in chunks and reports them to ROWS_STATS; else (None, scratch) — the allocation, set in ``a`` and to be held until the
+    launch, or None where the scatter kernels run, which is said once.  The free-memory query is a driver call: only calls that
+    could matter pay it (a fitting step's 1.8 GB does not)."""
+    cap = rows_scratch_cap(device) if need > (4 << 30) or "HFAGP_RAYBWD_SCRATCH_GIB" in os.environ else (16 << 30)
+    if need > cap and divisible:
+        return cap, None
+    scratch = None
+    if need > 0:
+        try:
+            scratch = torch.empty(need, device=device, dtype=torch.uint8)
+            a.rows_scratch, a.rows_scratch_bytes = _ptr(scratch), need
+            ROWS_STATS.update(bytes=need, chunks=1, path="rows")
+        except torch.cuda.OutOfMemoryError:
+            _warn_once("rows_oom", f"{who}: {need / 2**30:.2f} GiB of sort scratch could not be allocated: this call runs the "
+                                   f"(~2 x slower) scatter kernels")
+    else:
+        _warn_once("rows_unsupported", f"{who}: the sort + gather backward does not take {what} (more than 8192 bins per frame): the "
+                                       f"(~2 x slower) scatter kernels run")
+    if scratch is None:
+        ROWS_STATS.update(bytes=0, chunks=1, path="scatter")
+    return None, scratch
+
+
 def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world, intrinsics, u_strat, u_imp, dec_w0, dec_b0,
                  dec_w1, dec_b1, res: int, ray_start: float, ray_end: float, box_warp: float,
                  decoder_lr_mul: float = 1.0, plane_axes: int = 0, white_back: bool = False,
@@ -1959,13 +2010,7 @@ def raymarch_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, cam2world
     who = "raymarch_bwd"
     b, _, _ = _planes_dims(who, planes)
     r = res * res
-    if g_feat is not None and _chk(g_feat, f"{who}: g_feat").shape != (b, r, 32):
-        raise RuntimeError(f"raymarch_bwd: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
-    for t, name in ((g_depth, "g_depth"), (g_wsum, "g_wsum")):
-        if t is not None and _chk(t, f"{who}: {name}").shape != (b, r):
-            raise RuntimeError(f"raymarch_bwd: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
-    if depth_range is not None and _chk(depth_range, f"{who}: depth_range").shape != (2,):
-        raise RuntimeError(f"raymarch_bwd: depth_range must be [2] (ops.depth_range), got {tuple(depth_range.shape)}")
+    _check_upstream(who, b, r, g_feat, g_depth, g_wsum, depth_range)
     d_planes, rec = _out if _out is not None else (
         torch.zeros_like(planes), torch.empty(b, r, u_strat.shape[-1] + u_imp.shape[-1], 4, device=planes.device, dtype=torch.float32))
     if rec_out is not None:
@@ -1997,9 +2042,8 @@ def _raymarch_bwd_frames(*, g_feat, planes, cam2world, intrinsics, u_strat, u_im
     scratch = None
     if rows:
         need = int(L.lib().hfagp_raymarch_bwd_rows_bytes(C.byref(f)))
-        # (the free-memory query is a driver call: only batches that could matter pay it — a fitting step's 1.8 GB does not)
-        cap = rows_scratch_cap(planes.device) if need > (4 << 30) or "HFAGP_RAYBWD_SCRATCH_GIB" in os.environ else (16 << 30)
-        if need > cap and b > 1:
+        cap, scratch = _rows_scratch("raymarch_bwd", a, need, planes.device, b > 1, f"{h} x {w} planes at {f.res}^2 rays")
+        if cap is not None:
             # frame chunks: every per-frame input / output is a contiguous slice of the batch; the decoder gradients accumulate
             # in the one `dec`; u_imp is [B * R, Sf]; the depth range is batch-global
             nb = max(1, min(b - 1, int(b * cap // need)))
@@ -2012,19 +2056,6 @@ def _raymarch_bwd_frames(*, g_feat, planes, cam2world, intrinsics, u_strat, u_im
                                      **scene)
             ROWS_STATS.update(bytes=min(need, cap), chunks=-(-b // nb), path="rows")
             return dec
-        if need > 0:
-            try:
-                scratch = torch.empty(need, device=planes.device, dtype=torch.uint8)
-                a.rows_scratch, a.rows_scratch_bytes = _ptr(scratch), need
-                ROWS_STATS.update(bytes=need, chunks=1, path="rows")
-            except torch.cuda.OutOfMemoryError:
-                _warn_once("rows_oom", f"raymarch_bwd: {need / 2**30:.2f} GiB of sort scratch could not be allocated: this call runs the "
-                                       f"(~2 x slower) scatter kernels")
-        else:
-            _warn_once("rows_unsupported", f"raymarch_bwd: the sort + gather backward does not take {h} x {w} planes at {f.res}^2 rays "
-                                           f"(more than 8192 bins per frame): the (~2 x slower) scatter kernels run")
-        if scratch is None:
-            ROWS_STATS.update(bytes=0, chunks=1, path="scatter")
     # pass 2 as two kernels (dL/dF through a scratch buffer, then the scatter alone: hfagp.h `df_scratch`) where the column
     # variant applies; 201 MB per frame at 128^2 rays x 96 samples.  OFF by default: measured SLOWER than the fused kernel
     # (B = 2: dL/dF 0.51 ms + scatter 1.41 ms against 1.58 ms fused — the scatter alone is the bound, the arithmetic already
@@ -2032,11 +2063,10 @@ def _raymarch_bwd_frames(*, g_feat, planes, cam2world, intrinsics, u_strat, u_im
     if scratch is None and two_kernel and f.plane_axes == 0 and h == w and h <= 256 and b * r * (sc + sf) * 128 <= (4 << 30):
         df = torch.empty(b, r, sc + sf, 32, device=planes.device, dtype=torch.float32)
         a.df_scratch = _ptr(df)
-    if g_depth is None and g_wsum is None and depth_range is None:
+    gg = _geom_grads(g_depth, g_wsum, depth_range)
+    if gg is None:
         L.check(L.lib().hfagp_raymarch_bwd(C.byref(a), _stream()), "raymarch_bwd")
     else:
-        gg = L.RaymarchGeomGrads()
-        gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
         L.check(L.lib().hfagp_raymarch_bwd_geom(C.byref(a), C.byref(gg), _stream()), "raymarch_bwd")
     return dec
 
@@ -2092,13 +2122,7 @@ def raymarch_rays_bwd(g_feat: Optional[torch.Tensor], planes: torch.Tensor, ray_
     who = "raymarch_rays_bwd"
     b, _, _ = _planes_dims(who, planes)
     r = ray_origins.shape[1] if ray_origins.dim() == 3 else -1
-    if g_feat is not None and _chk(g_feat, f"{who}: g_feat").shape != (b, r, 32):
-        raise RuntimeError(f"{who}: g_feat must be [B, R, 32] = [{b}, {r}, 32], got {tuple(g_feat.shape)}")
-    for t, name in ((g_depth, "g_depth"), (g_wsum, "g_wsum")):
-        if t is not None and _chk(t, f"{who}: {name}").shape != (b, r):
-            raise RuntimeError(f"{who}: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
-    if depth_range is not None and _chk(depth_range, f"{who}: depth_range").shape != (2,):
-        raise RuntimeError(f"{who}: depth_range must be [2] (ops.depth_range), got {tuple(depth_range.shape)}")
+    _check_upstream(who, b, r, g_feat, g_depth, g_wsum, depth_range)
     sc, sf = u_strat.shape[-1], u_imp.shape[-1]
     if g_weights is not None and _chk(g_weights, f"{who}: g_weights").shape != (b, r, sc + sf - 1):
         raise RuntimeError(f"{who}: g_weights must be [B, R, Sc + Sf - 1] = [{b}, {r}, {sc + sf - 1}], got {tuple(g_weights.shape)}")
@@ -2137,8 +2161,8 @@ def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_s
         fa = L.RayListArgs()
         fa.base, fa.R = a.bwd.fwd, r
         need = int(L.lib().hfagp_raymarch_rays_bwd_rows_bytes(C.byref(fa)))
-        cap = rows_scratch_cap(planes.device) if need > (4 << 30) or "HFAGP_RAYBWD_SCRATCH_GIB" in os.environ else (16 << 30)
-        if need > cap and b * r > 1:
+        cap, scratch = _rows_scratch(who, a.bwd, need, planes.device, b * r > 1, f"{h} x {w} planes")
+        if cap is not None:
             # every per-ray input / output is [B, R, ...]: frames are contiguous slices, and so are the rays r0:r1 of ONE frame; the
             # decoder gradients accumulate in the one `dec`, d_planes accumulates per frame, the depth range is the call's
             per_ray = dict(g_feat=g_feat, ray_origins=ray_origins, ray_directions=ray_directions, u_strat=u_strat, u_imp=u_imp,
@@ -2154,24 +2178,7 @@ def _raymarch_rays_bwd_chunk(*, g_feat, planes, ray_origins, ray_directions, u_s
                     chunks += 1
             ROWS_STATS.update(bytes=min(need, cap), chunks=chunks, path="rows")
             return dec
-        if need > 0:
-            try:
-                scratch = torch.empty(need, device=planes.device, dtype=torch.uint8)
-                a.bwd.rows_scratch, a.bwd.rows_scratch_bytes = _ptr(scratch), need
-                ROWS_STATS.update(bytes=need, chunks=1, path="rows")
-            except torch.cuda.OutOfMemoryError:
-                _warn_once("rows_oom", f"{who}: {need / 2**30:.2f} GiB of sort scratch could not be allocated: this call runs the "
-                                       f"(~2 x slower) scatter kernels")
-        else:
-            _warn_once("rows_unsupported", f"{who}: the sort + gather backward does not take {h} x {w} planes (more than 8192 bins "
-                                           f"per frame): the (~2 x slower) scatter kernels run")
-        if scratch is None:
-            ROWS_STATS.update(bytes=0, chunks=1, path="scatter")
-    if g_depth is None and g_wsum is None and depth_range is None:
-        gg = None
-    else:
-        gg = L.RaymarchGeomGrads()
-        gg.g_depth, gg.g_wsum, gg.depth_range = _ptr(g_depth), _ptr(g_wsum), _ptr(depth_range)
+    gg = _geom_grads(g_depth, g_wsum, depth_range)
     if g_weights is not None:
         L.check(L.lib().hfagp_raymarch_rays_samples_bwd(C.byref(a), C.byref(lim) if lim is not None else None,
                                                         C.byref(gg) if gg is not None else None, _ptr(g_weights), _stream()), who)

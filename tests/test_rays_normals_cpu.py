@@ -238,17 +238,17 @@ def test_render_rays_keywords_and_refusals_need_no_device():
 
 @pytest.mark.parametrize("b,r", [(0, 5), (2, 0), (0, 0)])
 def test_empty_call_shapes_and_edges(b, r):
-    """`_render_rays_empty` is what `render_rays` returns for B = 0 or R = 0: 'normal' [B,R,3] only when asked for, detached unless
+    """`ray_list._empty` is what `render_rays` returns for B = 0 or R = 0: 'normal' [B,R,3] only when asked for, detached unless
     normal_grad, with the autograd edge of the call's inputs under grad."""
-    g = _gen()
-    plain = g._render_rays_empty(b, r, "cpu", 0.0, False, False, False)
+    from hfa_gp_amd import ray_list
+    plain = ray_list._empty(b, r, "cpu", 0.0, False, False, False)
     assert set(plain) == {"feature", "rgb", "depth", "mask"}
     src = torch.zeros(3, requires_grad=True)
     zero = 0.0 * src.sum()
-    out = g._render_rays_empty(b, r, "cpu", zero, True, True, False)
+    out = ray_list._empty(b, r, "cpu", zero, True, True, False)
     assert set(out) == {"feature", "rgb", "depth", "mask", "valid", "normal"}
     assert out["normal"].shape == (b, r, 3) and not out["normal"].requires_grad and out["feature"].requires_grad
-    out = g._render_rays_empty(b, r, "cpu", zero, False, True, True)
+    out = ray_list._empty(b, r, "cpu", zero, False, True, True)
     assert out["normal"].shape == (b, r, 3) and out["normal"].requires_grad and out["normal"].dtype == torch.float32
     out["normal"].sum().backward()
     assert src.grad is not None and bool((src.grad == 0).all())
