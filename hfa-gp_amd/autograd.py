@@ -368,68 +368,49 @@ def _query_normals_backward(gen, planes, coords, pam, g_grad, g_normal, d_planes
 
 
 class SynthesisFn(torch.autograd.Function):
-    """inputs: ws, c, u_strat, u_imp, gen, *generator parameters (listed only so that autograd can hand their
-    gradients back when the generator is being tuned; the forward reads them from `gen`)."""
+    """`synthesis` under grad, whatever the call asked for.  Inputs: ws, c, u_strat, u_imp, the query points or None, the
+    synthesis_call.SynthesisCall, gen, *generator parameters (listed only so that autograd can hand their gradients back when the
+    generator is being tuned; the forward reads them from `gen`).  Outputs, a fixed nine: image, image_raw, image_depth, image_mask
+    [B,1,r,r], query_sigma [B,M,1], query_rgb [B,M,32], query_sigma_grad [B,M,3], query_normal [B,M,3], image_normal [B,3,r,r] —
+    what the call did not ask for is empty and non-differentiable (a detached 'image_normal' is left in the record instead), and
+    without `geometry` 'image_depth' carries no gradient.
+    Backward: the super-resolution blocks, the compositing adjoint of the ray marcher (ops.raymarch_bwd; the gradients of
+    image_depth / image_mask join it as g_depth / g_wsum), the camera label's passes, then — each only if its gradient arrived,
+    each adding into the renderer's d_planes and decoder gradients, and after raymarch_bwd, which overwrites plane 2 on mirrored
+    planes — ops.planes_query_bwd, ops.planes_query_normals_bwd, ops.raymarch_normals_bwd; last the one backbone pass, which serves
+    every loss term and releases every parameter to the gradient sink once."""
 
     @staticmethod
-    def forward(ctx, ws, c, u_strat, u_imp, gen, *params):
-        return SynthesisFn._forward(ctx, False, ws, c, u_strat, u_imp, gen, params)
-
-    @staticmethod
-    def _forward(ctx, geometry, ws, c, u_strat, u_imp, gen, params, query=None, normal=False, query_normals=False):
+    def forward(ctx, ws, c, u_strat, u_imp, query, call, gen, *params):
         tape = {}
         ws_c = ws.detach().float().contiguous()
         with torch.no_grad():
-            img, rgb_raw, depth, planes, feat_img, *mask = gen._forward_impl(ws_c, c.detach().float().contiguous(), u_strat,
-                                                                             u_imp, tape, geometry)
-            if query is not None:                    # points evaluated on this call's planes (synthesis(query=))
-                tape["query"] = query.detach().float().contiguous()
-                if query_normals:                    # synthesis(query_normals=True): the same launch slot, four outputs
-                    q = gen._timed("planes_query_normals", float(planes.shape[0]), ops.planes_query_normals, planes, tape["query"],
-                                   planes_absmax=tape.get("planes_absmax"), **gen._query_kwargs())
-                    q_sigma, q_rgb, q_grad, q_normal = q["sigma"], q["rgb"], q["grad"], q["normal"]
-                else:
-                    q_sigma, q_rgb = ops.planes_query(planes, tape["query"], planes_absmax=tape.get("planes_absmax"),
-                                                      **gen._query_kwargs())
-        gen._last_extras = (planes, feat_img)        # for synthesis(return_planes=True)
-        ctx.gen, ctx.tape, ctx.ws_c = gen, tape, ws_c
+            outs = list(gen._forward_impl(call, ws_c, c.detach().float().contiguous(), tape))
+        if not call.normal_grad:
+            call.image_normal, outs[8] = outs[8], None
+        ctx.call, ctx.gen, ctx.tape, ctx.ws_c = call, gen, tape, ws_c
         ctx.params = params
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape = ws.shape
         ctx.c_dtype = c.dtype
-        ctx.normal_camera = bool(getattr(gen, "_want_normal_camera_grad", False))      # synthesis(normal_camera_grad=True)
-        if normal:                                   # synthesis(normal_grad=True): a fixed seven outputs, the unused ones empty
-            ctx.set_materialize_grads(False)
-            ctx.q_dtype = None if query is None else query.dtype
-            outs = (img, rgb_raw, depth, mask[0] if geometry else depth.new_empty(0),
-                    q_sigma if query is not None else depth.new_empty(0), q_rgb if query is not None else depth.new_empty(0),
-                    gen._last_normal)        # (the body took the normals from the state the tape keeps: generator._forward_body)
-            ctx.mark_non_differentiable(*([] if geometry else outs[2:4]), *([] if query is not None else outs[4:6]))
-            return outs
-        if query is not None:
-            ctx.set_materialize_grads(False)
-            ctx.q_dtype = query.dtype
-            q_more = (q_grad, q_normal) if query_normals else ()
-            if geometry:
-                return (img, rgb_raw, depth, mask[0], q_sigma, q_rgb) + q_more
-            no_mask = depth.new_empty(0)             # (a fixed number of outputs; without geometry=True the dict has no 'image_mask'
-            ctx.mark_non_differentiable(depth, no_mask)      # and the depth carries no gradient, as in a call without query)
-            return (img, rgb_raw, depth, no_mask, q_sigma, q_rgb) + q_more
-        if geometry:
-            ctx.set_materialize_grads(False)         # an output the loss does not use hands backward None, not a zero image
-            return img, rgb_raw, depth, mask[0]
-        ctx.mark_non_differentiable(depth)
-        return img, rgb_raw, depth
+        ctx.q_dtype = None if query is None else query.dtype
+        has_query = call.query is not None
+        # which outputs carry a gradient; an unused one hands backward None, not a zero image — but in the plain call, which has always
+        # had its unused gradients materialised (a loss on 'image' alone: a zero g_raw goes through the fused pass)
+        ctx.asked = (True, True, call.geometry, call.geometry, has_query, has_query, call.query_normals, call.query_normals,
+                     call.normal_grad)
+        ctx.set_materialize_grads(not (call.geometry or has_query or call.normal_grad))
+        outs = tuple(outs[0].new_empty(0) if t is None else t for t in outs)
+        ctx.mark_non_differentiable(*(t for t, asked in zip(outs, ctx.asked) if not asked))
+        return outs
 
     @staticmethod
     @torch.no_grad()
-    def backward(ctx, g_img, g_raw, g_depth, g_mask=None):
-        d_ws, d_c, _, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask)
-        return (d_ws, d_c, None, None, None) + pgrads
-
-    @staticmethod
-    def _backward(ctx, g_img, g_raw, g_depth, g_mask=None, g_qsigma=None, g_qrgb=None, need_coords=False, g_normal=None,
-                  g_qgrad=None, g_qnormal=None):
+    def backward(ctx, *grads):
+        g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, g_qgrad, g_qnormal, g_normal = (
+            g if asked else None for g, asked in zip(grads, ctx.asked))
+        call = ctx.call
+        need_coords = ctx.needs_input_grad[4] and (g_qsigma is not None or g_qrgb is not None)
         gen, tape = ctx.gen, ctx.tape
         if tape is None:
             raise RuntimeError("TriPlaneGenerator.synthesis: backward called a second time — the saved activations "
@@ -491,7 +472,7 @@ class SynthesisFn(torch.autograd.Function):
         if g_normal is not None:
             g_nrm = g_normal.float().permute(0, 2, 3, 1).reshape(b, res * res, 3).contiguous()
         if need_c:      # the camera label: positional derivative of the gather along every ray, then the adjoint of the ray generation
-            nrm_c = g_nrm is not None and ctx.normal_camera       # the normal term joins the per-ray records: one reduction for the loss
+            nrm_c = g_nrm is not None and call.normal_camera_grad       # the normal term joins the per-ray records: one reduction for the loss
             d_c2w, d_intr, ray_grad = gen._timed("raymarch_bwd_camera", float(b), ops.raymarch_bwd_camera, g_feat.view(b, res * res, 32),
                                                  tape["planes"], rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
                                                  planes_absmax=tape.get("planes_absmax"), reduce=not nrm_c,
@@ -507,13 +488,13 @@ class SynthesisFn(torch.autograd.Function):
             # the point query of synthesis(query=): its plane gradient joins the renderer's BEFORE the one backbone pass, its decoder
             # gradients land in the renderer's four tensors.  After raymarch_bwd has returned: that call overwrites plane 2 on
             # mirrored planes (mirror_plane_kernel), this one adds to every plane.
-            _, d_coords = gen._timed("planes_query_bwd", float(b), _query_backward, gen, tape["planes"], tape["query"],
+            _, d_coords = gen._timed("planes_query_bwd", float(b), _query_backward, gen, tape["planes"], call.query,
                                      tape.get("planes_absmax"), g_qsigma, g_qrgb, rb[0] if ctx.pg else rb, need_coords,
                                      rb[1] if ctx.pg else None)
         if g_qgrad is not None or g_qnormal is not None:
             # 'query_sigma_grad' / 'query_normal' of synthesis(query_normals=True): one launch that adds into the same d_planes and
             # decoder gradients, after raymarch_bwd for the point query's reason (it adds to every plane at its true texels)
-            gen._timed("planes_query_normals_bwd", float(b), _query_normals_backward, gen, tape["planes"], tape["query"],
+            gen._timed("planes_query_normals_bwd", float(b), _query_normals_backward, gen, tape["planes"], call.query,
                        tape.get("planes_absmax"), g_qgrad, g_qnormal, rb[0] if ctx.pg else rb, rb[1] if ctx.pg else None)
         if g_normal is not None:
             # 'image_normal' of synthesis(normal_grad=True): one launch that adds into the renderer's d_planes and decoder gradients,
@@ -533,145 +514,40 @@ class SynthesisFn(torch.autograd.Function):
         else:
             d_planes = rb
         _backbone_backward(bw, gen, tape["backbone"], d_planes, b, dev)
-        ctx.tape = None
+        ctx.tape = ctx.call = None
+        if d_coords is not None:
+            d_coords = d_coords.to(ctx.q_dtype)
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return d_ws, d_c, d_coords, pgrads
-
-
-class SynthesisGeomFn(SynthesisFn):
-    """`synthesis(geometry=True)`: outputs image, image_raw, image_depth, image_mask; the gradients of the last two join the
-    compositing adjoint of the ray marcher (ops.raymarch_bwd g_depth / g_wsum)."""
-    @staticmethod
-    def forward(ctx, ws, c, u_strat, u_imp, gen, *params):
-        return SynthesisFn._forward(ctx, True, ws, c, u_strat, u_imp, gen, params)
-
-
-
-class SynthesisQueryFn(SynthesisFn):
-    """`synthesis(query=coords)`: inputs ws, c, u_strat, u_imp, coords, geometry, gen, *parameters; outputs image, image_raw,
-    image_depth, image_mask, query_sigma [B,M,1], query_rgb [B,M,32].  The gradients of the last two reach the planes through
-    ops.planes_query_bwd right after ops.raymarch_bwd, into its d_planes and decoder gradients: one backbone pass serves the
-    image and the point losses, and every parameter is released to the gradient sink once."""
-    @staticmethod
-    def forward(ctx, ws, c, u_strat, u_imp, coords, geometry, gen, *params):
-        return SynthesisFn._forward(ctx, bool(geometry), ws, c, u_strat, u_imp, gen, params, query=coords)
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb):
-        need_coords = ctx.needs_input_grad[4] and (g_qsigma is not None or g_qrgb is not None)
-        d_ws, d_c, d_coords, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, need_coords)
-        if d_coords is not None:
-            d_coords = d_coords.to(ctx.q_dtype)
-        return (d_ws, d_c, None, None, d_coords, None, None) + pgrads
-
-
-class SynthesisQueryNormalFn(SynthesisFn):
-    """`synthesis(query=coords, query_normals=True)`: the inputs of SynthesisQueryFn; outputs image, image_raw, image_depth,
-    image_mask, query_sigma, query_rgb, query_sigma_grad [B,M,3], query_normal [B,M,3].  The gradients of the last two reach the
-    planes and the decoder through ops.planes_query_normals_bwd after ops.raymarch_bwd and the point query's backward, into their
-    d_planes and decoder gradients: one backbone pass serves every loss term.  The points get no gradient from these two outputs
-    (synthesis refuses points that require grad)."""
-    @staticmethod
-    def forward(ctx, ws, c, u_strat, u_imp, coords, geometry, gen, *params):
-        return SynthesisFn._forward(ctx, bool(geometry), ws, c, u_strat, u_imp, gen, params, query=coords, query_normals=True)
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, g_qgrad, g_qnormal):
-        d_ws, d_c, _, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, False, None,
-                                                     g_qgrad, g_qnormal)
-        return (d_ws, d_c, None, None, None, None, None) + pgrads
-
-
-class SynthesisNormalFn(SynthesisFn):
-    """`synthesis(normal_grad=True)`: the inputs of SynthesisQueryFn (coords may be None); outputs image, image_raw, image_depth,
-    image_mask, query_sigma, query_rgb, image_normal [B,3,r,r] (what `geometry` / `query` do not ask for: empty, non-differentiable).
-    The gradient of the last reaches the planes and the decoder through ops.raymarch_normals_bwd after ops.raymarch_bwd and the
-    point query's backward, into their d_planes and decoder gradients: one backbone pass serves every loss term."""
-    @staticmethod
-    def forward(ctx, ws, c, u_strat, u_imp, coords, geometry, gen, *params):
-        return SynthesisFn._forward(ctx, bool(geometry), ws, c, u_strat, u_imp, gen, params, query=coords, normal=True)
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, g_normal):
-        need_coords = ctx.needs_input_grad[4] and (g_qsigma is not None or g_qrgb is not None)
-        d_ws, d_c, d_coords, pgrads = SynthesisFn._backward(ctx, g_img, g_raw, g_depth, g_mask, g_qsigma, g_qrgb, need_coords,
-                                                            g_normal)
-        if d_coords is not None:
-            d_coords = d_coords.to(ctx.q_dtype)
         return (d_ws, d_c, None, None, d_coords, None, None) + pgrads
 
 
 class SampleMixedFn(torch.autograd.Function):
-    """`sample_mixed(..., differentiable=True)` on its own: inputs ws, coords, gen, *parameters; outputs sigma, rgb.  A backbone
-    forward with a tape, the query; backward = ops.planes_query_bwd, then the backbone backward `synthesis` runs."""
+    """`sample_mixed(..., differentiable=True)` on its own: inputs ws, coords, normals, gen, *parameters; outputs, a fixed four: sigma,
+    rgb, sigma_grad [B,M,3], normal [B,M,3] — the last two empty and non-differentiable without `normals`.  A backbone forward with a
+    tape, one launch (ops.planes_query, with `normals` ops.planes_query_normals); backward = ops.planes_query_bwd for sigma / rgb if the
+    loss used them, then ops.planes_query_normals_bwd into the same buffers if it used the other two, then the backbone backward
+    `synthesis` runs.  With `normals` the points get no gradient (sample_mixed refuses points that require grad)."""
     @staticmethod
-    def forward(ctx, ws, coords, gen, *params):
+    def forward(ctx, ws, coords, normals, gen, *params):
         ws_c = ws.detach().float().contiguous()
         co = coords.detach().float().contiguous()
         tape = []
         with torch.no_grad():
             planes = gen.backbone_planes(ws_c, tape)
             pam = getattr(gen, "_planes_absmax", None)
-            sigma, rgb = ops.planes_query(planes, co, planes_absmax=pam, **gen._query_kwargs())
+            if normals:
+                q = gen._timed("planes_query_normals", float(planes.shape[0]), ops.planes_query_normals, planes, co, planes_absmax=pam,
+                               **gen._query_kwargs())
+                outs = q["sigma"], q["rgb"], q["grad"], q["normal"]
+            else:
+                outs = ops.planes_query(planes, co, planes_absmax=pam, **gen._query_kwargs()) + (planes.new_empty(0), planes.new_empty(0))
+                ctx.mark_non_differentiable(*outs[2:])
         ctx.gen, ctx.tape, ctx.ws_c, ctx.co, ctx.planes, ctx.pam = gen, tape, ws_c, co, planes, pam
         ctx.params = params
         ctx.pg = any(p.requires_grad for p in params)
         ctx.ws_shape, ctx.q_dtype = ws.shape, coords.dtype
         ctx.set_materialize_grads(False)
-        return sigma, rgb
-
-    @staticmethod
-    @torch.no_grad()
-    def backward(ctx, g_sigma, g_rgb):
-        gen = ctx.gen
-        if ctx.tape is None:
-            raise RuntimeError("TriPlaneGenerator.sample_mixed: backward called a second time — the saved activations are released "
-                               "by the first backward pass (retain_graph is not supported)")
-        none = (None,) * (3 + len(ctx.params))
-        if g_sigma is None and g_rgb is None:
-            return none
-        planes = ctx.planes
-        b, dev = planes.shape[0], planes.device
-        d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
-        bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
-        dec_prm = gen.decoder_params()
-        dec = tuple(torch.zeros_like(p) for p in dec_prm) if ctx.pg else None
-        d_planes, d_coords = _query_backward(gen, planes, ctx.co, ctx.pam, g_sigma, g_rgb, None, ctx.needs_input_grad[1], dec)
-        if ctx.pg:
-            for prm, g in zip(dec_prm, dec):
-                bw._acc(prm, g)
-        _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
-        ctx.tape = ctx.planes = None
-        if d_coords is not None:
-            d_coords = d_coords.to(ctx.q_dtype)
-        pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return (d_ws, d_coords, None) + pgrads
-
-
-class SampleMixedNormalFn(torch.autograd.Function):
-    """`sample_mixed(..., normals=True, differentiable=True)` on its own: inputs ws, coords, gen, *parameters; outputs sigma, rgb,
-    sigma_grad [B,M,3], normal [B,M,3].  A backbone forward with a tape, one launch (ops.planes_query_normals); backward =
-    ops.planes_query_bwd for sigma / rgb if the loss used them, then ops.planes_query_normals_bwd into the same buffers, then the
-    backbone backward `synthesis` runs.  The points get no gradient (sample_mixed refuses points that require grad)."""
-    @staticmethod
-    def forward(ctx, ws, coords, gen, *params):
-        ws_c = ws.detach().float().contiguous()
-        co = coords.detach().float().contiguous()
-        tape = []
-        with torch.no_grad():
-            planes = gen.backbone_planes(ws_c, tape)
-            pam = getattr(gen, "_planes_absmax", None)
-            q = gen._timed("planes_query_normals", float(planes.shape[0]), ops.planes_query_normals, planes, co, planes_absmax=pam,
-                           **gen._query_kwargs())
-        ctx.gen, ctx.tape, ctx.ws_c, ctx.co, ctx.planes, ctx.pam = gen, tape, ws_c, co, planes, pam
-        ctx.params = params
-        ctx.pg = any(p.requires_grad for p in params)
-        ctx.ws_shape = ws.shape
-        ctx.set_materialize_grads(False)
-        return q["sigma"], q["rgb"], q["grad"], q["normal"]
+        return outs
 
     @staticmethod
     @torch.no_grad()
@@ -680,7 +556,7 @@ class SampleMixedNormalFn(torch.autograd.Function):
         if ctx.tape is None:
             raise RuntimeError("TriPlaneGenerator.sample_mixed: backward called a second time — the saved activations are released "
                                "by the first backward pass (retain_graph is not supported)")
-        none = (None,) * (3 + len(ctx.params))
+        none = (None,) * (4 + len(ctx.params))
         if g_sigma is None and g_rgb is None and g_grad is None and g_normal is None:
             return none
         planes = ctx.planes
@@ -689,9 +565,9 @@ class SampleMixedNormalFn(torch.autograd.Function):
         bw = _Backward(gen, None, d_ws, ctx.ws_c, ctx.pg)
         dec_prm = gen.decoder_params()
         dec = tuple(torch.zeros_like(p) for p in dec_prm) if ctx.pg else None
-        d_planes = None
+        d_planes = d_coords = None
         if g_sigma is not None or g_rgb is not None:
-            d_planes, _ = _query_backward(gen, planes, ctx.co, ctx.pam, g_sigma, g_rgb, None, False, dec)
+            d_planes, d_coords = _query_backward(gen, planes, ctx.co, ctx.pam, g_sigma, g_rgb, None, ctx.needs_input_grad[1], dec)
         if g_grad is not None or g_normal is not None:
             d_planes = gen._timed("planes_query_normals_bwd", float(b), _query_normals_backward, gen, planes, ctx.co, ctx.pam, g_grad,
                                   g_normal, d_planes, dec)
@@ -700,5 +576,7 @@ class SampleMixedNormalFn(torch.autograd.Function):
                 bw._acc(prm, g)
         _backbone_backward(bw, gen, ctx.tape, d_planes, b, dev)
         ctx.tape = ctx.planes = None
+        if d_coords is not None:
+            d_coords = d_coords.to(ctx.q_dtype)
         pgrads = tuple(bw.grads.get(id(p)) if p.requires_grad else None for p in ctx.params)
-        return (d_ws, None, None) + pgrads
+        return (d_ws, d_coords, None, None) + pgrads

@@ -24,7 +24,7 @@ from typing import Dict, Optional
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, synthesis_call
 from .config import GeneratorConfig, ffhq512_128
 
 
@@ -171,10 +171,6 @@ class TriPlaneGenerator(nn.Module):
         self._absmax = None                      # (slot buffers, layer names) of the last pass: f16_range_report()
         self._rgb_part = None                    # partial toRGB sums of the conv just run (fused toRGB, ops.modconv)
         self._planes_absmax = None               # [64] slots with max |planes| of the pass in flight (16-bit decoder)
-        self._want_normals = False               # synthesis(normals=True) in flight: _forward_body takes the normal pass too ...
-        self._last_normal = None                 # ... and leaves 'image_normal' here for synthesis to pick up
-        self._want_normal_camera_grad = False    # synthesis(normal_camera_grad=True) in flight: its gradient reaches the label c too
-        self._want_normal_grad = False           # synthesis(normal_grad=True) in flight: 'image_normal' is an autograd output
         self._scalars: Dict[int, tuple] = {}     # id(param) -> (version, data_ptr, python float)
         self._const_nhwc: Optional[tuple] = None
         self.timing: Optional[Dict[str, list]] = None   # bench.py: {'raymarch': [(ev0, ev1, units)], 'modconv': [...]}
@@ -772,18 +768,30 @@ class TriPlaneGenerator(nn.Module):
                                f"per-sample state, {ws.shape[0] * frame_bytes} bytes for {ws.shape[0]} frames, above "
                                f"RAY_STATE_CAP_BYTES = {RAY_STATE_CAP_BYTES}; {RAY_STATE_CAP_BYTES // frame_bytes} frames fit")
 
-    def _forward_impl(self, ws, c, u_strat, u_imp, tape, geometry=False):
-        """ws, c: detached contiguous fp32 CUDA tensors.  Returns image, image_raw, depth, planes, feat_img — and, with
-        `geometry`, the opacity image [B,1,r,r] as a sixth; when `tape` is a dict it is filled with everything the backward
-        pass needs."""
+    def _forward_impl(self, call, ws, c, tape):
+        """The one forward of `synthesis`, under no_grad.  call: the synthesis_call.SynthesisCall; ws, c: detached contiguous fp32
+        CUDA tensors.  Returns image, image_raw, image_depth, image_mask, query_sigma, query_rgb, query_sigma_grad, query_normal,
+        image_normal — None for what the call did not ask for — and leaves the planes and the feature image in the record; when
+        `tape` is a dict it is filled with everything the backward pass needs."""
         self._refresh_tuned(tape is not None)
         self._in_forward = True          # (backbone_planes / superres below must not rebuild the images a second time)
         try:
-            return self._forward_body(ws, c, u_strat, u_imp, tape, geometry)
+            img, rgb_raw, depth, mask, normal, call.planes, call.feature_image = self._forward_body(
+                ws, c, call.u_strat, call.u_imp, tape, call.geometry, call.normals)
         finally:
             self._in_forward = False
+        q = {}
+        pam = getattr(self, "_planes_absmax", None)
+        if call.query is not None and call.query_normals:        # the same launch slot, four outputs
+            q = self._timed("planes_query_normals", float(ws.shape[0]), ops.planes_query_normals, call.planes, call.query,
+                            planes_absmax=pam, **self._query_kwargs())
+        elif call.query is not None:            # points evaluated on this call's planes
+            q["sigma"], q["rgb"] = ops.planes_query(call.planes, call.query, planes_absmax=pam, **self._query_kwargs())
+        return img, rgb_raw, depth, mask, q.get("sigma"), q.get("rgb"), q.get("grad"), q.get("normal"), normal
 
-    def _forward_body(self, ws, c, u_strat, u_imp, tape, geometry=False):
+    def _forward_body(self, ws, c, u_strat, u_imp, tape, geometry, normals):
+        """→ image, image_raw, depth, the opacity image [B,1,r,r] (`geometry`; else None), 'image_normal' (`normals`: the same
+        per-sample results feed the normal pass; else None), planes, feat_img."""
         cfg = self.cfg
         b = ws.shape[0]
         res, res_sr = self.neural_rendering_resolution, cfg.neural_rendering_resolution      # rays marched; the SR blocks' input
@@ -794,8 +802,7 @@ class TriPlaneGenerator(nn.Module):
         pam = getattr(self, "_planes_absmax", None)
         # a step that will be differentiated keeps the ray marcher's per-sample results (220 MB per frame at 128^2 rays x 96
         # samples; skipped above 8 GB): the compositing adjoint then reads them instead of marching every ray again
-        ray_state = None
-        normals = getattr(self, "_want_normals", False)       # synthesis(normals=True): the same per-sample results feed the normal pass
+        ray_state = normal = None
         frame_bytes = res * res * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
         if (tape is not None or normals) and b * frame_bytes <= RAY_STATE_CAP_BYTES:
             ray_state = ops.raymarch_state(b, res, cfg.depth_resolution, cfg.depth_resolution_importance, ws.device)
@@ -808,7 +815,7 @@ class TriPlaneGenerator(nn.Module):
                 normal = ops.raymarch_normals(planes, ray_state, u_strat=u_strat, u_imp=u_imp, planes_absmax=pam,
                                               **self._render_args(c))
         if normals:
-            self._last_normal = normal.view(b, res, res, 3).permute(0, 3, 1, 2).contiguous()      # NCHW, 'image_normal'
+            normal = normal.view(b, res, res, 3).permute(0, 3, 1, 2).contiguous()      # NCHW, 'image_normal'
             if tape is None:
                 ray_state = None                  # (not needed again: released before the super-resolution allocates)
         # MipRayMarcher2 clamps the expected depth to the GLOBAL min/max sample depth of the batch
@@ -828,9 +835,7 @@ class TriPlaneGenerator(nn.Module):
                         feat_img=feat_sr, res=res, batch=b, planes_absmax=pam, ray_state=ray_state)
             if geometry:      # the clamp range of the depth, for its adjoint (autograd.SynthesisFn.backward)
                 tape["depth_range"] = ops.depth_range(tmm)
-        if geometry:
-            return img, rgb_raw, depth.view(b, 1, res, res), planes, feat_img, wsum.view(b, 1, res, res)
-        return img, rgb_raw, depth.view(b, 1, res, res), planes, feat_img
+        return img, rgb_raw, depth.view(b, 1, res, res), wsum.view(b, 1, res, res) if geometry else None, normal, planes, feat_img
 
     def synthesis(self, ws: torch.Tensor, c: torch.Tensor, noise_mode: str = "const",
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
@@ -883,124 +888,8 @@ class TriPlaneGenerator(nn.Module):
         back to the N x N rays, so every mode above composes.  N = 2 r0 supersamples (four rays per SR input pixel), N = r0 / 2 is
         EG3D's cheap training regime.  N outside [r0 / 4, 4 r0], or caller-given `u_strat` / `u_imp` that are not sized for N x N
         rays, raise ValueError before anything is launched; N = r0 launches exactly what a call without the keyword does."""
-        self._check_inputs(ws, c, noise_mode)
-        self._set_resolution(ws.shape[0], neural_rendering_resolution, u_strat, u_imp)
-        normal_grad = normal_grad or normal_camera_grad
-        if query_normals:
-            if query is None:
-                raise ValueError("TriPlaneGenerator.synthesis: query_normals=True needs query=coords")
-            if normal_grad:
-                raise NotImplementedError("TriPlaneGenerator.synthesis: query_normals=True together with normal_grad=True / "
-                                          "normal_camera_grad=True is not implemented")
-            if torch.is_grad_enabled() and query.requires_grad:
-                raise NotImplementedError("TriPlaneGenerator.synthesis: 'query_sigma_grad' / 'query_normal' have no gradient w.r.t. the "
-                                          "points (it needs the mixed second derivative of the gather); detach `query`")
-        if normals or normal_grad:    # one pass of the body below with the request set (the state of the ray marcher is shared)
-            if normal_grad and torch.is_grad_enabled():
-                self._check_normal_grad(ws, c, normal_camera_grad)
-            self._want_normals, self._last_normal = True, None
-            self._want_normal_grad = bool(normal_grad)
-            self._want_normal_camera_grad = bool(normal_camera_grad)
-            try:
-                out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query, query_normals=query_normals)
-            finally:
-                self._want_normals = self._want_normal_grad = self._want_normal_camera_grad = False
-            if "image_normal" not in out:         # (a differentiable one is an output of the autograd function itself)
-                r = self.neural_rendering_resolution
-                out["image_normal"] = self._last_normal if ws.shape[0] else torch.zeros(0, 3, r, r, device=ws.device)
-                if normal_grad and not ws.shape[0] and torch.is_grad_enabled():
-                    out["image_normal"] = out["image_normal"] + 0.0 * ws.sum()      # keeps the autograd edge to ws
-            self._last_normal = None
-            return out
-        if query is not None:
-            if query.dim() != 3 or query.shape[-1] != 3 or query.shape[0] not in (1, ws.shape[0]) or not query.is_cuda:
-                raise ValueError(f"expected query [B or 1, M, 3] on the device for ws of batch {ws.shape[0]}, got "
-                                 f"{tuple(query.shape)} on {query.device}")
-            if query.shape[1] == 0 or ws.shape[0] == 0:       # nothing to evaluate: the keys, with the autograd edge of the points
-                out = self.synthesis(ws, c, noise_mode, u_strat, u_imp, return_planes, geometry)
-                zero = 0.0 * query.sum() if query.requires_grad else 0.0
-                out["query_sigma"] = torch.zeros(ws.shape[0], query.shape[1], 1, device=ws.device) + zero
-                out["query_rgb"] = torch.zeros(ws.shape[0], query.shape[1], 32, device=ws.device) + zero
-                if query_normals:
-                    for k in ("query_sigma_grad", "query_normal"):
-                        out[k] = torch.zeros(ws.shape[0], query.shape[1], 3, device=ws.device)
-                return out
-        if ws.shape[0] == 0:          # empty batch (ragged last batch of a frame shard): nothing to launch
-            cfg, dev = self.cfg, ws.device
-            r = self.neural_rendering_resolution
-            out = {"image": torch.zeros(0, cfg.img_channels, cfg.img_resolution, cfg.img_resolution, device=dev),
-                   "image_raw": torch.zeros(0, 3, r, r, device=dev), "image_depth": torch.zeros(0, 1, r, r, device=dev)}
-            if geometry:
-                out["image_mask"] = torch.zeros(0, 1, r, r, device=dev)
-            out["image"] = out["image"] + 0.0 * ws.sum() + 0.0 * c.sum()      # keeps the autograd edges to ws and c
-            return out
-        params = [p for n, p in self.named_parameters() if not n.startswith("backbone.mapping.")]
-        cam_grad = torch.is_grad_enabled() and c.requires_grad
-        need_grad = torch.is_grad_enabled() and (ws.requires_grad or cam_grad or any(p.requires_grad for p in params) or
-                                                 (query is not None and query.requires_grad))
-        c_in = c if cam_grad else c.detach()
-        if need_grad:
-            from .autograd import SynthesisFn
-            if getattr(self, "_want_normal_grad", False):
-                from .autograd import SynthesisNormalFn
-                img, rgb_raw, depth, mask, q_sigma, q_rgb, normal = SynthesisNormalFn.apply(ws, c_in, u_strat, u_imp, query, geometry,
-                                                                                            self, *params)
-                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
-                if geometry:
-                    out["image_mask"] = mask
-                if query is not None:
-                    out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
-                out["image_normal"] = normal
-            elif query is not None and query_normals:
-                from .autograd import SynthesisQueryNormalFn
-                img, rgb_raw, depth, mask, q_sigma, q_rgb, q_grad, q_normal = SynthesisQueryNormalFn.apply(
-                    ws, c_in, u_strat, u_imp, query, geometry, self, *params)
-                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
-                if geometry:
-                    out["image_mask"] = mask
-                out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
-                out["query_sigma_grad"], out["query_normal"] = q_grad, q_normal
-            elif query is not None:
-                from .autograd import SynthesisQueryFn
-                img, rgb_raw, depth, mask, q_sigma, q_rgb = SynthesisQueryFn.apply(ws, c_in, u_strat, u_imp, query, geometry, self,
-                                                                                   *params)
-                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
-                if geometry:
-                    out["image_mask"] = mask
-                out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
-            elif geometry:
-                from .autograd import SynthesisGeomFn
-                img, rgb_raw, depth, mask = SynthesisGeomFn.apply(ws, c_in, u_strat, u_imp, self, *params)
-                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth, "image_mask": mask}
-            else:
-                img, rgb_raw, depth = SynthesisFn.apply(ws, c_in, u_strat, u_imp, self, *params)
-                out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
-            if return_planes:
-                out["planes"], out["feature_image"] = self._last_extras
-            self._last_extras = None
-            return out
-        with torch.no_grad():
-            img, rgb_raw, depth, planes, feat_img, *mask = self._forward_impl(
-                ws.detach().float().contiguous(), c.detach().float().contiguous(), u_strat, u_imp, None, geometry)
-            if query is not None and query_normals:
-                q = self._timed("planes_query_normals", float(ws.shape[0]), ops.planes_query_normals, planes,
-                                query.detach().float().contiguous(), planes_absmax=getattr(self, "_planes_absmax", None),
-                                **self._query_kwargs())
-                q_sigma, q_rgb = q["sigma"], q["rgb"]
-            elif query is not None:
-                q_sigma, q_rgb = ops.planes_query(planes, query.detach().float().contiguous(),
-                                                  planes_absmax=getattr(self, "_planes_absmax", None), **self._query_kwargs())
-        out = {"image": img, "image_raw": rgb_raw, "image_depth": depth}
-        if geometry:
-            out["image_mask"] = mask[0]
-        if query is not None:
-            out["query_sigma"], out["query_rgb"] = q_sigma, q_rgb
-            if query_normals:
-                out["query_sigma_grad"], out["query_normal"] = q["grad"], q["normal"]
-        if return_planes:
-            out["planes"] = planes
-            out["feature_image"] = feat_img
-        return out
+        return synthesis_call.synthesis(self, ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query, normals, normal_grad,
+                                        normal_camera_grad, query_normals, neural_rendering_resolution)
 
     @torch.no_grad()
     def mapping(self, z: torch.Tensor, c: torch.Tensor, truncation_psi: float = 1.0) -> torch.Tensor:
@@ -1100,13 +989,12 @@ class TriPlaneGenerator(nn.Module):
                                    "evaluate the points with `synthesis(..., query=coordinates)` instead")
             if not coordinates.is_cuda:
                 raise RuntimeError("TriPlaneGenerator.sample_mixed: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
-            if normals:
-                from .autograd import SampleMixedNormalFn
-                sigma, rgb, sigma_grad, normal = SampleMixedNormalFn.apply(ws, coordinates, self, *params)
-                return {"rgb": rgb, "sigma": sigma, "sigma_grad": sigma_grad, "normal": normal}
             from .autograd import SampleMixedFn
-            sigma, rgb = SampleMixedFn.apply(ws, coordinates, self, *params)
-            return {"rgb": rgb, "sigma": sigma}
+            sigma, rgb, sigma_grad, normal = SampleMixedFn.apply(ws, coordinates, bool(normals), self, *params)
+            out = {"rgb": rgb, "sigma": sigma}
+            if normals:
+                out.update(sigma_grad=sigma_grad, normal=normal)
+            return out
         with torch.no_grad():
             planes, pam = self._query_planes(ws)
             if normals:

@@ -17,7 +17,7 @@ from tests import normal_camera_ref as NC
 from tests import normal_grad_ref as G
 from tests import normals_ref as N
 from tests.test_gpu_normal_grad import B, _cfg, _gen, _gen_cpu, _inputs, _target, forward_state, state_depths
-from tests.util import FLIP_COLUMNS, make_inputs, state_cpu
+from tests.util import FLIP_COLUMNS, SYNTHESIS_CALL_STATE, make_inputs, state_cpu
 
 pytestmark = pytest.mark.gpu
 
@@ -363,6 +363,8 @@ def test_refusal_and_silence(dev, monkeypatch):
     from hfa_gp_amd import ops
     gen, cfg = _gen(dev), _cfg()
     ws, c, us, ui = _inputs(dev)
+    with torch.no_grad():
+        before = gen.synthesis(ws, c, noise_mode="const", u_strat=us, u_imp=ui)
     with pytest.raises(NotImplementedError, match="camera gradient of the normal term.*normal_camera_grad"):
         gen.synthesis(ws.clone().requires_grad_(True), c.clone().requires_grad_(True), noise_mode="const", u_strat=us, u_imp=ui,
                       normal_grad=True)
@@ -377,7 +379,12 @@ def test_refusal_and_silence(dev, monkeypatch):
     assert calls == []
     _step(gen, dev, image=True, t_nrm=t_nrm, normal_camera_grad=True, geometry=True)
     assert calls == [1]
-    assert gen._want_normals is False and gen._want_normal_grad is False and gen._want_normal_camera_grad is False
+    assert not SYNTHESIS_CALL_STATE & set(vars(gen))          # (the request lives in the call's record, not on the module)
+    with torch.no_grad():
+        plain = gen.synthesis(ws, c, noise_mode="const", u_strat=us, u_imp=ui)
+    assert list(plain) == ["image", "image_raw", "image_depth"]
+    for k in plain:
+        assert torch.equal(plain[k], before[k]), k
 
 
 def test_get_image_with_non_leaf_label(dev):

@@ -15,7 +15,7 @@ import torch
 
 from tests import normal_grad_ref as G
 from tests import normals_ref as N
-from tests.util import FLIP_COLUMNS, make_inputs, perturb_state, state_cpu
+from tests.util import FLIP_COLUMNS, SYNTHESIS_CALL_STATE, make_inputs, perturb_state, state_cpu
 
 pytestmark = pytest.mark.gpu
 
@@ -371,6 +371,8 @@ def test_refusals(dev, monkeypatch):
     from hfa_gp_amd import ops
     gen, cfg = _gen(dev), _cfg()
     ws, c, us, ui = _inputs(dev)
+    with torch.no_grad():
+        before = gen.synthesis(ws, c, noise_mode="const", u_strat=us, u_imp=ui)
 
     def boom(*a, **k):
         raise AssertionError("launched before the refusal")
@@ -383,8 +385,13 @@ def test_refusals(dev, monkeypatch):
     monkeypatch.setattr(Gn, "RAY_STATE_CAP_BYTES", frame)
     with pytest.raises(RuntimeError, match=rf"RAY_STATE_CAP_BYTES = {frame}; 1 frames fit"):
         gen.synthesis(ws.clone().requires_grad_(True), c, noise_mode="const", u_strat=us, u_imp=ui, normal_grad=True)
-    assert gen._want_normals is False and gen._want_normal_grad is False
+    assert not SYNTHESIS_CALL_STATE & set(vars(gen))          # (the request lives in the call's record, not on the module)
     monkeypatch.undo()
+    with torch.no_grad():
+        plain = gen.synthesis(ws, c, noise_mode="const", u_strat=us, u_imp=ui)
+    assert list(plain) == ["image", "image_raw", "image_depth"]
+    for k in plain:
+        assert torch.equal(plain[k], before[k]), k
     monkeypatch.setattr(Gn, "RAY_STATE_CAP_BYTES", frame)
     with torch.no_grad():                                     # without grad it is `normals=True`: rendered in frame chunks
         out = gen.synthesis(ws, c, noise_mode="const", u_strat=us, u_imp=ui, normal_grad=True)

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from tests import normals_ref as N
-from tests.util import FLIP_COLUMNS, make_inputs, perturb_state, state_cpu
+from tests.util import FLIP_COLUMNS, SYNTHESIS_CALL_STATE, make_inputs, perturb_state, state_cpu
 
 pytestmark = pytest.mark.gpu
 
@@ -336,4 +336,8 @@ def test_no_normal_pass_without_normals(dev, monkeypatch):
     assert "image_normal" not in _step(gen, dev)[0]
     with pytest.raises(AssertionError, match="raymarch_normals called"), torch.no_grad():
         _call(gen, dev, normals=True)
-    assert gen._want_normals is False
+    assert not SYNTHESIS_CALL_STATE & set(vars(gen))          # (the request lives in the call's record, not on the module)
+    with torch.no_grad():
+        after = _call(gen, dev)
+    assert list(after) == ["image", "image_raw", "image_depth"]
+    _same_images(after, _plain(dev))

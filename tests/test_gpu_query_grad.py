@@ -153,7 +153,7 @@ def test_query_gradient_joins_the_ray_marchers_on_mirrored_planes(dev):
     What is NOT checked: that plane 2 is "no transpose of plane 1", nor the launch order.  On these planes a free point's plane-2
     gradient is itself the transpose of its plane-1 gradient (same taps with row and column swapped, one dL/dF for the three planes),
     so the joined plane 2 is the transpose of the joined plane 1 up to atomic order, and query-first-then-mirror would give the same
-    sum: no assertion on the result can tell the two orders apart.  The order is fixed in autograd.SynthesisFn._backward."""
+    sum: no assertion on the result can tell the two orders apart.  The order is fixed in autograd.SynthesisFn.backward."""
     from tests.test_gpu_geometry_grad import case, device_call
     rc = case("small128")
     assert rc["cfg"].plane_axes == "eg3d_original" and rc["planes"].shape[-2:] == (20, 20)

@@ -11,3 +11,7 @@ if ROOT not in sys.path:
 
 from hfa_gp_amd.synthetic import (FLIP_COLUMNS, INTRINSICS, look_at_label, make_inputs, perturb_state,  # noqa: E402,F401
                                   state_cpu)
+
+# Attributes of the generator module that once carried the request and the results of one `synthesis` call (now a
+# synthesis_call.SynthesisCall, which lives as long as the call): none of them may exist on a generator, after any call or refusal.
+SYNTHESIS_CALL_STATE = frozenset(("_want_normals", "_want_normal_grad", "_want_normal_camera_grad", "_last_normal", "_last_extras"))
