@@ -286,6 +286,10 @@ SYMBOLS = {
     "hfagp_pool_mse_workspace_bytes": (C.c_size_t, []),
     "hfagp_pool_mse_fwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]),
     "hfagp_pool_mse_bwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] * 4 + [C.c_void_p]),
+    "hfagp_pool_wmse_workspace_bytes": (C.c_size_t, [C.c_int32]),
+    "hfagp_pool_wmse_sweep_elements": (C.c_int64, []),
+    "hfagp_pool_wmse_fwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p]),
+    "hfagp_pool_wmse_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [C.c_void_p]),
     "hfagp_upfirdn2d_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 12 + [C.c_float, C.c_void_p]),
     "hfagp_upfirdn2d_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 12 + [C.c_float, C.c_void_p]),
     "hfagp_bias_act_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_float,

@@ -2259,6 +2259,54 @@ def pool_mse(img: torch.Tensor, real: torch.Tensor):
     return PoolMSE.apply(img, real)
 
 
+class PoolWMSE(torch.autograd.Function):
+    """`PoolMSE` under a per-pixel weight [B,1,h,w] at the loss resolution, normalised per frame (hfagp_pool_wmse_fwd / _bwd):
+    loss = mean over frames of sum(weight (real - pooled)^2) / (C sum(weight)), a frame without weight contributing 0.  One pass
+    over `img` forward, one write pass backward, no atomics, no host sync; the pooled image is returned unmasked and carries no
+    gradient; there is no gradient w.r.t. `weight` or `real`."""
+
+    @staticmethod
+    def forward(ctx, img: torch.Tensor, real: torch.Tensor, weight: torch.Tensor):
+        _chk(img, "img"), _chk(real, "real")
+        b, c, hh, ww = img.shape
+        h, w = real.shape[-2:]
+        f = hh // h
+        if real.shape[:2] != (b, c) or hh != f * h or ww != f * w or f < 1:
+            raise RuntimeError(f"pool_wmse: image {tuple(img.shape)} is not an integer multiple of real {tuple(real.shape)}")
+        _chk_operand("pool_wmse", "weight", weight, (b, 1, h, w), img)
+        pooled = torch.empty_like(real)
+        loss = torch.empty((), device=img.device, dtype=torch.float32)
+        inv_d = torch.empty(b, device=img.device, dtype=torch.float32)
+        ws = torch.empty(L.lib().hfagp_pool_wmse_workspace_bytes(b) // 4, device=img.device, dtype=torch.float32)
+        L.check(L.lib().hfagp_pool_wmse_fwd(_ptr(img), _ptr(real), _ptr(weight), _ptr(pooled), _ptr(loss), _ptr(inv_d), _ptr(ws),
+                                            b, c, h, w, f, _stream()), "pool_wmse_fwd")
+        ctx.save_for_backward(pooled, real, weight, inv_d)
+        ctx.shape = (b, c, hh, ww, f)
+        ctx.mark_non_differentiable(pooled)
+        return loss, pooled
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_pooled):
+        pooled, real, weight, inv_d = ctx.saved_tensors
+        b, c, hh, ww, f = ctx.shape
+        d_img = torch.empty(b, c, hh, ww, device=pooled.device, dtype=torch.float32)
+        L.check(L.lib().hfagp_pool_wmse_bwd(_ptr(pooled), _ptr(real), _ptr(weight), _ptr(inv_d), _ptr(g_loss.contiguous().float()),
+                                            _ptr(d_img), b, c, real.shape[-2], real.shape[-1], f, _stream()), "pool_wmse_bwd")
+        return d_img, None, None
+
+
+def pool_wmse(img: torch.Tensor, real: torch.Tensor, weight: torch.Tensor):
+    """→ (weighted l2 loss scalar, pooled image [B,C,h,w]).  `weight` [B,1,h,w]: float32, contiguous, on the device, finite and
+    >= 0 (values above 1 allowed), no gradient.  Where the weight is 0 the pixel is skipped by a branch: NaN / inf in `img` or
+    `real` there reach neither the loss nor d img, which is exactly +0.0 there.  Negative or non-finite weights are NOT checked
+    (a check would need a host sync): the loss value is then undefined."""
+    if not isinstance(weight, torch.Tensor):
+        raise TypeError(f"pool_wmse: weight must be a tensor, got {type(weight).__name__}")
+    if weight.requires_grad:
+        raise RuntimeError("pool_wmse: weight requires grad, and the loss has no gradient w.r.t. the weight; pass weight.detach()")
+    return PoolWMSE.apply(img, real, weight)
+
+
 # ----------------------------------------------------------------------------- optimiser of the fitting step
 class AdamTables:
     """Device tables of hfagp_adam_step for one set of (param, grad, exp_avg, exp_avg_sq, step) tensors; built once per set."""

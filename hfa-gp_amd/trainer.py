@@ -28,18 +28,67 @@ from .cam_utils import create_cam2world_matrix, make_label, sample_camera_positi
 from .headnerf import AudioAttNet, AudioNet, HeadNeRF_3DMM, HeadNeRF_Audio, HeadNeRF_final
 
 
-def pooled_l2(face_pool: nn.Module, real_image: torch.Tensor, generated: torch.Tensor, need_pooled_grad: bool):
+def pooled_l2(face_pool: nn.Module, real_image: torch.Tensor, generated: torch.Tensor, need_pooled_grad: bool,
+              weight: Optional[torch.Tensor] = None):
     """(l2, pooled image) of the reference's  generated = face_pool(generated); l2 = MSE(real, generated)
     (trainer_rgb.py:84-86).  On the MI355X with an integer pooling factor and no LPIPS term this is the fused
-    pass of ops.pool_mse (one read of the image forward, one write backward); otherwise PyTorch-ROCm ops."""
-    if (generated.is_cuda and not need_pooled_grad and real_image.dtype == torch.float32
-            and real_image.shape[:2] == generated.shape[:2]
-            and generated.shape[-2] % real_image.shape[-2] == 0 and generated.shape[-1] % real_image.shape[-1] == 0
-            and generated.shape[-2] // real_image.shape[-2] == generated.shape[-1] // real_image.shape[-1]):
+    pass of ops.pool_mse (one read of the image forward, one write backward); otherwise PyTorch-ROCm ops.
+
+    `weight` [B,1,h,w] (float32, at the loss resolution, finite and >= 0, values above 1 allowed, broadcast over the channels)
+    weights the pixels and normalises PER FRAME, so that a frame with a small mask is not drowned by one with a large mask and the
+    mean over frames stays what `loss_weight` / `epoch_batches` make exact across ragged rank shards:
+        N_b = sum_{c,y,x} weight_b(y,x) (real - pooled)^2,   D_b = C sum_{y,x} weight_b(y,x),   l2 = (1/B) sum_b (D_b > 0 ? N_b / D_b : 0)
+    All-ones weights give the unweighted loss up to rounding.  Where the weight (or a frame's D_b) is 0 the pixel is skipped by a
+    BRANCH: it adds exactly 0 and its gradient is exactly 0, whatever (NaN, inf) image and target hold there.  The pooled image is
+    returned unmasked.  No gradient w.r.t. the weight (one that requires grad is refused) or the target.  Negative or non-finite
+    weights are NOT checked — that would cost a host sync per step — and leave the loss value undefined.  Under the conditions
+    that select ops.pool_mse this is the fused pass of ops.pool_wmse; otherwise the same definition in torch ops."""
+    fused = (generated.is_cuda and not need_pooled_grad and real_image.dtype == torch.float32
+             and real_image.shape[:2] == generated.shape[:2]
+             and generated.shape[-2] % real_image.shape[-2] == 0 and generated.shape[-1] % real_image.shape[-1] == 0
+             and generated.shape[-2] // real_image.shape[-2] == generated.shape[-1] // real_image.shape[-1])
+    if weight is None:
+        if fused:
+            from . import ops
+            return ops.pool_mse(generated.contiguous(), real_image.contiguous())
+        pooled = face_pool(generated)
+        return F.mse_loss(real_image, pooled, reduction="mean"), pooled
+    b, c, h, w = real_image.shape
+    if tuple(weight.shape) != (b, 1, h, w) or weight.dtype != torch.float32 or weight.device != real_image.device:
+        raise ValueError(f"pooled_l2: weight must be a float32 tensor [{b}, 1, {h}, {w}] on {real_image.device}, got "
+                         f"{list(weight.shape)} {weight.dtype} on {weight.device}")
+    if weight.requires_grad:
+        raise RuntimeError("pooled_l2: weight requires grad, and the loss has no gradient w.r.t. the weight; pass weight.detach()")
+    if fused:
         from . import ops
-        return ops.pool_mse(generated.contiguous(), real_image.contiguous())
+        return ops.pool_wmse(generated.contiguous(), real_image.contiguous(), weight.contiguous())
     pooled = face_pool(generated)
-    return F.mse_loss(real_image, pooled, reduction="mean"), pooled
+    on = weight > 0
+    # (the difference is masked BEFORE it is squared: torch.where after the arithmetic would still send 0 * NaN backwards)
+    diff = torch.where(on, real_image.detach() - pooled, torch.zeros((), dtype=pooled.dtype, device=pooled.device))
+    n_b = (weight * diff * diff).sum(dim=(1, 2, 3))
+    d_b = c * weight.sum(dim=(1, 2, 3))
+    return (n_b / torch.where(d_b > 0, d_b, torch.ones_like(d_b))).sum() / b, pooled      # (an empty frame: N_b is exactly 0)
+
+
+def matte_composite(real_image: torch.Tensor, generated: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """`generated` composited onto the target under the matte m = weight.clamp(max=1): real + m (generated - real) — what LPIPS
+    sees of a masked fit, so that its two inputs agree outside the matte and the mask edge is no feature of either.  `generated`
+    may be an integer factor larger than the target (LPIPSAlex's folded 2 x 2 pool): matte and target are then repeated, which is
+    exact — pool(m↑ gen + (1 - m↑) real↑) = m pool(gen) + (1 - m) real."""
+    m = weight.clamp(max=1)
+    f = generated.shape[-1] // real_image.shape[-1]
+    if f > 1:
+        m = m.repeat_interleave(f, -1).repeat_interleave(f, -2)
+        real_image = real_image.repeat_interleave(f, -1).repeat_interleave(f, -2)
+    return real_image + m * (generated - real_image)
+
+
+def silhouette_bce(image_mask: torch.Tensor, matte: torch.Tensor) -> torch.Tensor:
+    """Opacity supervision of a masked fit: BCE between the renderer's per-ray opacity 'image_mask'
+    [B,1,r,r] and the matte [B,1,s,s] in [0,1] area-averaged to r x r.  Plain torch: r^2 = 16 K elements per frame."""
+    target = F.interpolate(matte, size=image_mask.shape[-2:], mode="area")
+    return F.binary_cross_entropy(image_mask.clamp(1e-4, 1 - 1e-4), target)
 
 
 class MultiTensorAdam(torch.optim.Adam):
@@ -531,6 +580,7 @@ class Trainer(nn.Module):
         self.lpips_loss = None if (lpips is None or (isinstance(lpips, str) and lpips == "none")) else lpips
         self.face_pool = nn.AdaptiveAvgPool2d((args.size, args.size))
         self.timing: Optional[dict] = None   # bench.py: {'fwd': [(ev0, ev1)], 'bwd': ..., 'allreduce': ..., 'optim': ...}
+        self.last_silhouette: Optional[torch.Tensor] = None   # gen_update(matte=): the silhouette term of the last step (device scalar)
         if world_size > 1:
             self.broadcast_parameters()
         self._flat: Optional[FlatGrads] = None
@@ -617,16 +667,27 @@ class Trainer(nn.Module):
             self.timing.setdefault(key, []).append((e0, e1))
 
     def gen_update(self, real_image, label, params=None, person_2=False, loss_weight: float = 1.0, *,
-                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None):
+                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
+                   mask: Optional[torch.Tensor] = None, matte: Optional[torch.Tensor] = None, silhouette_weight: float = 0.1):
         """One optimisation step.  rgb mode: `gen_update(real, label, person_2=...)` → (l2, lpips, image);
         3dmm mode: `gen_update(real, label, params, person_2)` → (l2_3dmm, l2, lpips, image) — the reference's
         signatures and return arity (trainer_rgb.py:73-98, trainer_3dmm.py:43-67; train_3dmm.py:128 unpacks four).
         `loss_weight` rescales this rank's loss before the all-reduce mean (ragged frame shards, `epoch_batches`);
         an EMPTY batch skips the forward/backward and contributes zero gradients to the collective.
         `u_strat` / `u_imp` (keyword-only, TEST HOOK): the renderer's uniforms for this step instead of fresh draws
-        (`_LatentBasis._synthesis`) — parity tests and the exact multi-rank equalities need two steps to sample alike."""
+        (`_LatentBasis._synthesis`) — parity tests and the exact multi-rank equalities need two steps to sample alike.
+        `mask` [B,1,s,s] (the slot the reference's signature has and never uses, trainer_rgb.py:73): per-pixel weight of the L2
+        term, normalised per frame (`pooled_l2(weight=)`: float32, >= 0, values above 1 allowed), and — clamped to 1 — the matte
+        under which LPIPS sees the generated image composited onto the target (`matte_composite`).
+        `matte` [B,1,s,s] in [0,1] (with `silhouette_weight` > 0): the step renders with `geometry=True` and adds
+        silhouette_weight * BCE(image_mask, matte at the rendering resolution) (`silhouette_bce`) before its one backward pass — a
+        masked photometric term alone leaves the generator free to put density where nothing is looked at.  The value is kept as
+        a detached device scalar in `self.last_silhouette` (None when the term is off).  The returned tuple is unchanged; an empty
+        batch ignores both; with both None the step is the one it always was."""
         if self.mode == "rgb" and isinstance(params, bool):          # reference call form gen_update(real, label, person_2)
             params, person_2 = None, params
+        self.last_silhouette = None
+        geo = {"geometry": True} if (matte is not None and silhouette_weight > 0) else {}
         self.gen.train()
         flat = self.flat_grads()
         bucketer = self._overlap(flat)
@@ -647,21 +708,31 @@ class Trainer(nn.Module):
                     if isinstance(weights, tuple):
                         weights = weights[0]
                     latent = self.gen.get_latent(weights, person_2)
-                    generated = self.gen.get_image(latent, label, u_strat=u_strat, u_imp=u_imp)
+                    generated = self.gen.get_image(latent, label, u_strat=u_strat, u_imp=u_imp, **geo)
                 else:
-                    generated = self.gen(params, label, person_2, u_strat=u_strat, u_imp=u_imp)
+                    generated = self.gen(params, label, person_2, u_strat=u_strat, u_imp=u_imp, **geo)
+                if geo:                # the synthesis dict: 'image' for the photometric terms, 'image_mask' for the silhouette
+                    opacity, generated = generated["image_mask"], generated["image"]
                 full = generated
                 # LPIPSAlex folds a 2 x 2 pool into its first conv: the L2 term then keeps the fused pool + MSE pass and no
                 # pooled image with a gradient is needed (lpips_alex.LPIPSAlex._features_of_unpooled)
                 fold = (self.lpips_loss is not None and getattr(self.lpips_loss, "accepts_unpooled", False)
                         and full.shape[-1] == 2 * real_image.shape[-1] and full.shape[-2] == 2 * real_image.shape[-2])
-                l2, generated = pooled_l2(self.face_pool, real_image, generated, self.lpips_loss is not None and not fold)
+                l2, generated = pooled_l2(self.face_pool, real_image, generated, self.lpips_loss is not None and not fold, mask)
                 if self.lpips_loss is not None:
-                    lp = torch.squeeze(self.lpips_loss(real_image, full if fold else generated)).mean()
+                    fake = full if fold else generated
+                    if mask is not None:
+                        fake = matte_composite(real_image, fake, mask)
+                    lp = torch.squeeze(self.lpips_loss(real_image, fake)).mean()
                 else:
                     lp = torch.zeros((), device=l2.device)
+                if geo:
+                    sil = silhouette_bce(opacity, matte)
+                    self.last_silhouette = sil.detach()
                 t1 = self._mark()
                 g_loss = l2 + lp
+                if geo:
+                    g_loss = g_loss + silhouette_weight * sil
                 if loss_weight != 1.0:
                     g_loss = g_loss * loss_weight
                 g_loss.backward()
@@ -725,7 +796,8 @@ class Trainer(nn.Module):
 def fit_frames(trainer: "Trainer", reals: torch.Tensor, labels: torch.Tensor, params: Optional[torch.Tensor] = None,
                epochs: int = 1, batch: Optional[int] = None, tune_iter: Optional[int] = None,
                start_iter: int = 0, on_step: Optional[Callable] = None,
-               uniforms: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> List[torch.Tensor]:
+               uniforms: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+               masks: Optional[torch.Tensor] = None, mattes: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
     """The fitting loop of train_rgb.py:114-154 / train_3dmm.py:113-150 over a frame set resident on the device:
     frames are sharded in contiguous blocks over the ranks (`shard_range`), every rank walks its shard in
     batches of `batch` (default: args.batch_size // world_size, at least 1 — the reference's integer division can
@@ -734,6 +806,8 @@ def fit_frames(trainer: "Trainer", reals: torch.Tensor, labels: torch.Tensor, pa
     `reals` [N,3,s,s], `labels` [N,25] (un-flipped, as the data set yields them), `params` [N,P] (3dmm mode).
     `uniforms` (TEST HOOK) = (u_strat [N,R,Sc], u_imp [N,R,Sf]): per-FRAME renderer uniforms, so that a frame samples alike
     whichever rank and batch position renders it (exact multi-rank equalities); default: fresh draws per call.
+    `masks` / `mattes` [N,1,s,s]: per-frame `mask=` / `matte=` of `gen_update` (masked fits), resident on the
+    device like `reals` and sliced by the same contiguous block.
     Returns the per-step L2 losses of THIS rank (device scalars; no host sync inside the loop)."""
     tr = trainer
     n = reals.shape[0]
@@ -752,6 +826,10 @@ def fit_frames(trainer: "Trainer", reals: torch.Tensor, labels: torch.Tensor, pa
             if uniforms is not None and idx.numel():
                 kw = dict(u_strat=uniforms[0][sl].contiguous(),
                           u_imp=uniforms[1][sl].reshape(-1, uniforms[1].shape[-1]).contiguous())
+            if masks is not None:
+                kw["mask"] = masks[sl]
+            if mattes is not None:
+                kw["matte"] = mattes[sl]
             if tr.mode == "rgb":
                 out = tr.gen_update(real, label, loss_weight=weight, **kw)
                 l2 = out[0]
@@ -826,6 +904,7 @@ class AudioTrainer(nn.Module):
                           stacklevel=2)
         self.lpips_loss = None if (lpips is None or (isinstance(lpips, str) and lpips == "none")) else lpips
         self._flat: Optional[FlatGrads] = None
+        self.last_silhouette: Optional[torch.Tensor] = None
         self.auds = torch.as_tensor(auds).to(device).float()
         self.i_train = i_train
         self.face_pool = nn.AdaptiveAvgPool2d((args.size, args.size))
@@ -874,8 +953,13 @@ class AudioTrainer(nn.Module):
         return aud.unsqueeze(0) if aud.dim() == 1 else aud
 
     def gen_update(self, real_image, label, params, global_step: int, img_i: int, person_2: bool = False, *,
-                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None):
-        """trainer_audio.py:55-113.  `u_strat` / `u_imp`: the renderer-uniform test hook of `Trainer.gen_update`."""
+                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
+                   mask: Optional[torch.Tensor] = None, matte: Optional[torch.Tensor] = None, silhouette_weight: float = 0.1):
+        """trainer_audio.py:55-113.  `u_strat` / `u_imp`: the renderer-uniform test hook of `Trainer.gen_update`.
+        `mask` / `matte` / `silhouette_weight`: as in `Trainer.gen_update` — a weight map over the loss pixels (here typically
+        > 1 on the mouth region) and the opacity supervision under a matte; `self.last_silhouette` keeps the silhouette term."""
+        self.last_silhouette = None
+        geo = {"geometry": True} if (matte is not None and silhouette_weight > 0) else {}
         self.gen.train(), self.AudNet.train(), self.AudAttNet.train()
         flat = self.flat_grads()
         bucketer = self._overlap(flat)
@@ -888,12 +972,20 @@ class AudioTrainer(nn.Module):
             absent = absent + [p for p in self.AudAttNet.parameters() if p.requires_grad]
         with _StepScope(bucketer, [self.gen.generator], absent):
             generated = self.gen(self._drive(global_step, img_i, self.i_train), label, person_2,
-                                 u_strat=u_strat, u_imp=u_imp)
+                                 u_strat=u_strat, u_imp=u_imp, **geo)
+            if geo:
+                opacity, generated = generated["image_mask"], generated["image"]
             l2_3dmm = torch.zeros(1, device=self.device)
-            l2, generated = pooled_l2(self.face_pool, real_image, generated, self.lpips_loss is not None)
-            lp = (torch.squeeze(self.lpips_loss(real_image, generated)).mean() if self.lpips_loss is not None
+            l2, generated = pooled_l2(self.face_pool, real_image, generated, self.lpips_loss is not None, mask)
+            fake = generated if mask is None or self.lpips_loss is None else matte_composite(real_image, generated, mask)
+            lp = (torch.squeeze(self.lpips_loss(real_image, fake)).mean() if self.lpips_loss is not None
                   else torch.zeros((), device=l2.device))
-            (l2_3dmm + l2 + lp).backward()
+            g_loss = l2_3dmm + l2 + lp
+            if geo:
+                sil = silhouette_bce(opacity, matte)
+                self.last_silhouette = sil.detach()
+                g_loss = g_loss + silhouette_weight * sil
+            g_loss.backward()
             if bucketer is not None:
                 bucketer.finish()
         opts = [self.w_optim, self.optimizer_Aud] + ([self.optimizer_AudAtt] if smooth else [])

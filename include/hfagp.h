@@ -42,6 +42,8 @@
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
  *   hfagp_pool_mse_fwd/_bwd <- face_pool (AdaptiveAvgPool2d) + MSELoss of gen_update (code/trainer_rgb.py:63,84-85) and its backward
+ *   hfagp_pool_wmse_fwd/_bwd <- the same under a per-pixel weight, normalised per frame: the unused `mask=None` slot of gen_update
+ *                              (code/trainer_rgb.py:73)
  *   hfagp_blur_down_fwd/_bwd<- Blur + stride-2 sampling in front of the ResBlock skip (code/networks/encoder3d.py:59-73,142-199)
  *   hfagp_allreduce_f32     <- the gradient all-reduce DistributedDataParallel does for the reference
  *                              (code/trainer_rgb.py:56, code/trainer_3dmm.py:29, code/trainer_audio.py:30-34; NCCL group: code/train_rgb.py:57)
@@ -1081,6 +1083,25 @@ int hfagp_pool_mse_fwd(const float* img, const float* real, float* pooled, float
                        int32_t BC, int32_t h, int32_t w, int32_t f, void* stream);
 int hfagp_pool_mse_bwd(const float* pooled, const float* real, const float* g_loss, float* d_img,
                        int32_t BC, int32_t h, int32_t w, int32_t f, void* stream);
+
+/* The same pass with a per-pixel weight at the loss resolution (masked / region-weighted fits; additive to ABI 15):
+ *   img [B][C][f*h][f*w], real and pooled [B][C][h][w], weight [B][1][h][w] (finite, >= 0, values above 1 allowed; broadcast over C)
+ *   pooled = AdaptiveAvgPool2d((h, w))(img)                       (written unmasked)
+ *   N_b    = sum over c, y, x of weight_b(y,x) (real - pooled)^2,   D_b = C * sum over y, x of weight_b(y,x)
+ *   loss   = (1/B) sum over b of (D_b > 0 ? N_b / D_b : 0)         (normalised PER FRAME; deterministic reduction order, no atomics)
+ *   d_img[b,c,Y,X] = g_loss * 2 weight_b(y,x) (pooled - real) / (B D_b f^2)      (every element of d_img is written)
+ * Where weight == 0 or D_b == 0 the pixel adds exactly 0 to N_b and its d_img is exactly +0.0 — a branch, not a product: NaN / inf
+ * in img or real under zero weight reach neither.  A negative or non-finite weight is not checked (no host sync): undefined loss.
+ * inv_d: B floats on the device, written by _fwd (1 / D_b, 0 for a frame without weight) and read by _bwd;
+ * workspace: hfagp_pool_wmse_workspace_bytes(B) bytes; loss, g_loss: one float on the device; 1 <= B <= 65535.
+ * hfagp_pool_wmse_sweep_elements(): elements of ONE frame (C*h*w) that one sweep of the forward launch covers; a larger frame takes
+ * further sweeps of the same blocks. */
+size_t hfagp_pool_wmse_workspace_bytes(int32_t B);
+int64_t hfagp_pool_wmse_sweep_elements(void);
+int hfagp_pool_wmse_fwd(const float* img, const float* real, const float* weight, float* pooled, float* loss, float* inv_d,
+                        float* workspace, int32_t B, int32_t C, int32_t h, int32_t w, int32_t f, void* stream);
+int hfagp_pool_wmse_bwd(const float* pooled, const float* real, const float* weight, const float* inv_d, const float* g_loss,
+                        float* d_img, int32_t B, int32_t C, int32_t h, int32_t w, int32_t f, void* stream);
 
 /* ------------------------------------------------------------------ standalone ops (NCHW, test surface) */
 int hfagp_upfirdn2d_fwd(const float* x, const float* f, float* y,

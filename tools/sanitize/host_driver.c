@@ -66,6 +66,9 @@ int main(void) {
     EXPECT(hfagp_affine_grad(NULL, NULL, NULL, NULL, 2, 512, 512, 14, NULL) < 0, "affine_grad(NULL)");
     EXPECT(hfagp_pool_mse_fwd(NULL, NULL, NULL, NULL, NULL, 1, 3, 256, 2, NULL) < 0, "pool_mse_fwd(NULL)");
     EXPECT(hfagp_pool_mse_bwd(NULL, NULL, NULL, NULL, 1, 3, 256, 2, NULL) < 0, "pool_mse_bwd(NULL)");
+    EXPECT(hfagp_pool_wmse_fwd(NULL, NULL, NULL, NULL, NULL, NULL, NULL, 2, 3, 256, 256, 2, NULL) < 0, "pool_wmse_fwd(NULL)");
+    EXPECT(hfagp_pool_wmse_bwd(NULL, NULL, NULL, NULL, NULL, NULL, 2, 3, 256, 256, 2, NULL) < 0, "pool_wmse_bwd(NULL)");
+    EXPECT(hfagp_pool_wmse_workspace_bytes(0) == 0 && hfagp_pool_wmse_workspace_bytes(2) > 0, "pool_wmse_workspace_bytes");
     EXPECT(hfagp_upfirdn2d_fwd(NULL, NULL, NULL, 1, 1, 8, 8, 4, 4, 2, 1, 2, 1, 2, 1, 4.f, NULL) < 0, "upfirdn2d_fwd(NULL)");
     EXPECT(hfagp_upfirdn2d_bwd(NULL, NULL, NULL, 1, 1, 8, 8, 4, 4, 2, 1, 2, 1, 2, 1, 4.f, NULL) < 0, "upfirdn2d_bwd(NULL)");
     EXPECT(hfagp_bias_act_fwd(NULL, NULL, NULL, 16, 4, 4, HFAGP_ACT_LRELU, 0.2f, 1.f, -1.f, NULL) < 0, "bias_act_fwd(NULL)");
