@@ -49,6 +49,13 @@ class PlanesQueryBwdArgs(C.Structure):
         [("decoder_lr_mul", C.c_float), ("box_warp", C.c_double)]
 
 
+class TraceRaysArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("planes", "ray_origins", "ray_directions", "t_near", "t_far", "dec_w0", "dec_b0", "dec_w1",
+                                          "dec_b1", "planes_absmax", "hit", "cell", "t", "point", "sigma", "sigma_grad", "normal")] + \
+        [("R", C.c_int64)] + [(n, C.c_int32) for n in ("B", "H", "W", "plane_axes", "steps", "refine")] + \
+        [("level", C.c_float), ("decoder_lr_mul", C.c_float), ("box_warp", C.c_double)]
+
+
 class MarchingCubesArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("volume", "workspace", "counts", "verts", "faces")] + \
         [(n, C.c_int64) for n in ("workspace_bytes", "vert_capacity", "face_capacity")] + \
@@ -213,6 +220,7 @@ SYMBOLS = {
     "hfagp_planes_query_bwd": (C.c_int, [C.POINTER(PlanesQueryBwdArgs), C.c_void_p]),
     "hfagp_planes_query_normals": (C.c_int, [C.POINTER(PlanesQueryArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hfagp_planes_query_normals_bwd": (C.c_int, [C.POINTER(PlanesQueryBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hfagp_trace_rays": (C.c_int, [C.POINTER(TraceRaysArgs), C.c_void_p]),
     "hfagp_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "hfagp_marching_cubes_count": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),
     "hfagp_marching_cubes_emit": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),

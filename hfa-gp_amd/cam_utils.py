@@ -91,11 +91,6 @@ def ray_grid(c: torch.Tensor, res: int, window=None) -> Tuple[torch.Tensor, torc
     row, v down the rows; the whole image is (0, 0, 1, 1)): the res x res pixel centres of that rectangle instead — a crop, or a zoom
     at a higher ray density.  Differentiable w.r.t. c."""
     n = c.shape[0]
-    c2w, intr = c[:, :16].reshape(n, 4, 4), c[:, 16:25].reshape(n, 3, 3)
-    cam = c2w[:, :3, 3]
-    fx, fy = intr[:, 0, 0], intr[:, 1, 1]
-    cx, cy = intr[:, 0, 2], intr[:, 1, 2]
-    sk = intr[:, 0, 1]
     ar = torch.arange(res, dtype=c.dtype, device=c.device)
     uv = torch.stack(torch.meshgrid(ar, ar, indexing="ij")) * (1.0 / res) + (0.5 / res)
     uv = uv.flip(0).reshape(2, -1).transpose(1, 0)[None].repeat(n, 1, 1)
@@ -103,6 +98,18 @@ def ray_grid(c: torch.Tensor, res: int, window=None) -> Tuple[torch.Tensor, torc
     if window is not None:
         u0, v0, u1, v1 = (float(t) for t in window)
         xc, yc = u0 + xc * (u1 - u0), v0 + yc * (v1 - v0)
+    return _rays_through(c, xc, yc)
+
+
+def _rays_through(c: torch.Tensor, xc: torch.Tensor, yc: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The rays of the labels c [B,25] through the image points (xc, yc), each [B,P], in normalised image coordinates: the one
+    formula behind `ray_grid` and `pixel_rays`."""
+    n = c.shape[0]
+    c2w, intr = c[:, :16].reshape(n, 4, 4), c[:, 16:25].reshape(n, 3, 3)
+    cam = c2w[:, :3, 3]
+    fx, fy = intr[:, 0, 0], intr[:, 1, 1]
+    cx, cy = intr[:, 0, 2], intr[:, 1, 2]
+    sk = intr[:, 0, 1]
     zc = torch.ones_like(xc)
     xl = (xc - cx[:, None] + cy[:, None] * sk[:, None] / fy[:, None] - sk[:, None] * yc / fy[:, None]) / fx[:, None] * zc
     yl = (yc - cy[:, None]) / fy[:, None] * zc
@@ -111,6 +118,17 @@ def ray_grid(c: torch.Tensor, res: int, window=None) -> Tuple[torch.Tensor, torc
     dirs = torch.nn.functional.normalize(world - cam[:, None, :], dim=2)
     origins = cam[:, None, :].repeat(1, dirs.shape[1], 1)
     return origins, dirs.contiguous()          # (both contiguous: ops.raymarch_rays takes them as they are)
+
+
+def pixel_rays(c: torch.Tensor, uv: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The rays of a label through given image points: c [B,25], uv [B,P,2] in `ray_grid`'s normalised image coordinates (u along a
+    row, v down the rows, the whole image is [0,1]²; the centre of pixel (row i, column j) of a res x res image is
+    u = j·(1/res) + 0.5/res, v = i·(1/res) + 0.5/res) → (origins, directions), each [B,P,3], unit directions.  `ray_grid`'s formula,
+    so at its pixel centres the results are bit-equal to its rays.  Differentiable w.r.t. c and uv — a 2-D landmark becomes a 3-D
+    point on the head with `TriPlaneGenerator.trace_rays` on these rays."""
+    if uv.dim() != 3 or uv.shape[-1] != 2 or uv.shape[0] != c.shape[0]:
+        raise ValueError(f"pixel_rays: uv must be [B, P, 2] for c of batch {c.shape[0]}, got {tuple(uv.shape)}")
+    return _rays_through(c, uv[:, :, 0], uv[:, :, 1])
 
 
 def ray_grid_ortho(cam2world: torch.Tensor, res: int, extent: float) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -1073,6 +1073,36 @@ class TriPlaneGenerator(nn.Module):
         return ray_list.render_rays(self, ws, ray_origins, ray_directions, u_strat, u_imp, noise_mode, t_near, t_far, ray_limits,
                                     normals, normal_grad, normal_ray_grad, samples, compact)
 
+    def trace_rays(self, ws: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor, level: float = 10.0,
+                   steps: int = 128, refine: int = 8, t_near=None, t_far=None, ray_limits=None, normals: bool = True,
+                   differentiable: bool = False) -> Dict[str, torch.Tensor]:
+        """Where each ray of a list first meets the density iso-surface σ = `level` — the surface `extract_mesh(level=)` exports, in
+        the unit of `sample_mixed`'s 'sigma' (before any softplus): a 2-D landmark to a 3-D point on the head
+        (`cam_utils.pixel_rays`), a depth map that agrees with the mesh, shadow-ray origins, depth against a range scan.  Rays
+        [B,R,3] as `render_rays` takes them (directions not normalised: a point is o + t·d).  →
+          'hit' [B,R] bool, 'cell' [B,R] int32: the first node i of t_i = t_near + i·(t_far − t_near)/steps, i = 0 … steps, with
+                σ ≥ level; −1 for a miss, 0 when the ray starts inside (then t = t_near);
+          't' [B,R]: for cell > 0 the root inside [t_{cell−1}, t_cell] after `refine` bisections and one secant step — within
+                (t_far − t_near)/(steps·2^refine) of the crossing the coarse march bracketed; a surface thinner than one step
+                between two nodes is stepped over;
+          'point' [B,R,3] = o + t·d, 'sigma' [B,R] the density there, and with `normals` 'sigma_grad' [B,R,3] = ∂σ/∂x and 'normal'
+                [B,R,3] = −∇σ·rsqrt(‖∇σ‖² + 1e-12): the bits of `sample_mixed(point, normals=True)`.
+        A miss has exact zeros in every float entry.  One backbone pass, one launch (ops.trace_rays), no atomics: two calls give the
+        same bits.  R = 0 or B = 0: empty tensors, nothing is launched.
+        The limits resolve exactly as in `render_rays`: the config's [ray_start, ray_end], `t_near` / `t_far` (tensors [B,R] or
+        floats), `ray_limits="box"` or an `OccupancyGrid`; with any of them the dict has 'valid' [B,R], and a ray that is not valid
+        is a miss.  As there, the limits are NOT differentiated, and neither is `level`.
+        `differentiable=True`: under grad 't' and 'point' are differentiable w.r.t. `ws`, the generator parameters that require grad
+        and the rays, by the implicit function theorem — dt = −dσ(x*)/(g·d) at the traced root, evaluated through the differentiable
+        point query (`ray_losses.implicit_depth` on `sample_mixed(differentiable=True)`; no further kernel).  A ray carries this
+        gradient only if it is a hit with cell > 0 whose crossing is transversal, g·d ≥ 0.01·‖g‖‖d‖; every other ray — a miss, a start
+        inside, a grazing crossing — has constant 't' and 'point': exactly zero gradient.  The other entries are detached.  The call
+        pays a backbone backward pass of its own; inside a trainer step scope it raises, as `sample_mixed(differentiable=True)` does:
+        there, trace under no_grad and pass 'point' through `synthesis(query=)` with `ray_losses.implicit_depth`."""
+        from . import ray_list
+        return ray_list.trace_rays(self, ws, ray_origins, ray_directions, level, steps, refine, t_near, t_far, ray_limits, normals,
+                                   differentiable)
+
     def sample(self, coordinates: torch.Tensor, directions: Optional[torch.Tensor], z: torch.Tensor, c: torch.Tensor,
                truncation_psi=1, truncation_cutoff=None, update_emas=False, **synthesis_kwargs) -> Dict[str, torch.Tensor]:
         """EG3D TriPlaneGenerator.sample: `mapping(z, c, truncation_psi)` then `sample_mixed`.  Only truncation_cutoff=None

@@ -1340,6 +1340,61 @@ def planes_query_normals_bwd(planes: torch.Tensor, coords: torch.Tensor, g_grad:
     return d_planes, dec
 
 
+_TRACE_OUT = ("hit", "cell", "t", "point", "sigma", "sigma_grad", "normal")
+
+
+def trace_rays(planes: torch.Tensor, origins: torch.Tensor, directions: torch.Tensor, t_near: torch.Tensor, t_far: torch.Tensor,
+               level: float, steps: int = 128, refine: int = 8, planes_absmax: Optional[torch.Tensor] = None, want=_TRACE_OUT, *,
+               dec_w0: torch.Tensor, dec_b0: torch.Tensor, dec_w1: torch.Tensor, dec_b1: torch.Tensor, box_warp: float, plane_axes,
+               decoder_lr_mul: float, decoder_precision: str) -> dict:
+    """The first hit of every ray with the iso-surface σ = ``level`` of the raw density (hfagp_trace_rays), one launch → a dict with
+    the keys of ``want`` (any non-empty subset of 'hit', 'cell', 't', 'point', 'sigma', 'sigma_grad', 'normal'):
+
+      * 'hit' [B,R] uint8 and 'cell' [B,R] int32: the first node i of t_i = t_near + i·(t_far − t_near)/steps (t_steps = t_far) with
+        σ(o + t_i·d) ≥ level; −1 for a miss; 0 when the origin is inside already;
+      * 't' [B,R]: for cell > 0 the root in [t_{cell−1}, t_cell] after ``refine`` bisections and one secant step, t_near for cell 0;
+      * 'point' [B,R,3] = o + t·d; 'sigma' [B,R], 'sigma_grad' [B,R,3], 'normal' [B,R,3]: `planes_query_normals` at that point (its bits).
+    Rays [B,R,3] with limits [B,R] as `raymarch_rays(t_near=, t_far=)` takes them (directions not normalised); a ray whose limits
+    are not both finite with t_far > t_near is empty: a miss.  A miss has exact zeros in every float output.  ``level`` in the unit
+    of `planes_query`'s sigma (before any softplus), ``steps`` in [1, 4096], ``refine`` in [0, 30].  No atomics: two calls return
+    the same bits, whatever ``want`` is.  Nothing carries a gradient.  The decoder keywords are `planes_query`'s."""
+    who = "trace_rays"
+    b, h, w = _planes_dims(who, planes)
+    dev = planes.device
+    want = tuple(want)
+    if not want or any(k not in _TRACE_OUT for k in want):
+        raise ValueError(f"{who}: want must be a non-empty subset of {_TRACE_OUT}, got {want}")
+    if not 1 <= int(steps) <= 4096:
+        raise ValueError(f"{who}: steps must be in [1, 4096], got {steps}")
+    if not 0 <= int(refine) <= 30:
+        raise ValueError(f"{who}: refine must be in [0, 30], got {refine}")
+    for name, t in (("origins", origins), ("directions", directions)):
+        if _chk(t, f"{who}: {name}").dim() != 3 or t.shape[0] != b or t.shape[2] != 3:
+            raise RuntimeError(f"{who}: {name} must be [B={b}, R, 3], got {tuple(t.shape)}")
+    if origins.shape != directions.shape:
+        raise RuntimeError(f"{who}: origins {tuple(origins.shape)} and directions {tuple(directions.shape)} differ")
+    r = origins.shape[1]
+    for name, t in (("t_near", t_near), ("t_far", t_far)):
+        if _chk(t, f"{who}: {name}").shape != (b, r):
+            raise RuntimeError(f"{who}: {name} must be [B, R] = [{b}, {r}], got {tuple(t.shape)}")
+    shape = {"hit": ((b, r), torch.uint8), "cell": ((b, r), torch.int32), "t": ((b, r), torch.float32),
+             "point": ((b, r, 3), torch.float32), "sigma": ((b, r), torch.float32), "sigma_grad": ((b, r, 3), torch.float32),
+             "normal": ((b, r, 3), torch.float32)}
+    out = {k: torch.empty(shape[k][0], device=dev, dtype=shape[k][1]) for k in _TRACE_OUT if k in want}
+    if b == 0 or r == 0:
+        return out
+    a = L.TraceRaysArgs()
+    _fill_decoder(who, a, planes, (dec_w0, dec_b0, dec_w1, dec_b1), decoder_precision, planes_absmax)
+    a.planes, a.ray_origins, a.ray_directions, a.t_near, a.t_far = (_ptr(t) for t in (planes, origins, directions, t_near, t_far))
+    for k in _TRACE_OUT:
+        setattr(a, k, _ptr(out.get(k)))
+    a.R, a.B, a.H, a.W, a.plane_axes = r, b, h, w, _plane_axes_id(plane_axes)
+    a.steps, a.refine, a.level = int(steps), int(refine), float(level)
+    a.box_warp, a.decoder_lr_mul = box_warp, decoder_lr_mul
+    L.check(L.lib().hfagp_trace_rays(C.byref(a), _stream()), who)
+    return out
+
+
 def marching_cubes(volume: torch.Tensor, level: float, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     """Iso-surface ``volume > level`` of a float32 [n0, n1, n2] volume (hfagp_marching_cubes_count / _emit) → ``(verts [V, 3]
     float32, faces [F, 3] int32)`` on the volume's device.  Vertices ``origin + spacing * p`` at the crossed lattice edges,

@@ -1,7 +1,9 @@
 """The list renderer behind `TriPlaneGenerator.render_rays` (its docstring is the public description): `resolve` turns the call's
 keywords into a `RayCall`, `march` is the one forward path — with and without grad, whole or in ray chunks above
 generator.RAY_STATE_CAP_BYTES — and `RenderRaysFn` the one autograd function, whatever the call asked for.  Every launch is an
-`ops.<name>` looked up at call time, and the cap is read from the generator module at call time."""
+`ops.<name>` looked up at call time, and the cap is read from the generator module at call time.
+`trace_rays` (behind `TriPlaneGenerator.trace_rays`) takes the same lists with the same limits — the checks of `resolve` it shares
+are the four helpers in front of it — to the first hit with the density iso-surface."""
 from __future__ import annotations
 
 import dataclasses
@@ -38,6 +40,72 @@ class RayCall:
         return {} if self.limits is None else dict(t_near=self.limits[0], t_far=self.limits[1])
 
 
+def check_limit_keywords(who: str, t_near, t_far, ray_limits):
+    """The keyword rules of per-ray limits, shared by `render_rays` and `trace_rays` → the OccupancyGrid of ``ray_limits`` or None."""
+    from .occupancy import OccupancyGrid
+    occ = ray_limits if isinstance(ray_limits, OccupancyGrid) else None
+    if ray_limits is not None and occ is None and not (isinstance(ray_limits, str) and ray_limits == "box"):
+        raise ValueError(f"TriPlaneGenerator.{who}: ray_limits must be None or 'box' or an OccupancyGrid, got {ray_limits!r}")
+    if (t_near is None) != (t_far is None):
+        raise ValueError(f"TriPlaneGenerator.{who}: t_near and t_far go together (both or neither)")
+    if ray_limits is not None and t_near is not None:
+        raise ValueError(f"TriPlaneGenerator.{who}: ray_limits='box' / an OccupancyGrid and explicit t_near / t_far are "
+                         "mutually exclusive")
+    return occ
+
+
+def check_rays(who: str, gen, ws, ray_origins, ray_directions, occ) -> None:
+    """The checks of an occupancy grid against the call and of the rays' shapes and dtypes (before the device is looked at)."""
+    if occ is not None:
+        if occ.batch not in (1, ws.shape[0]):
+            raise ValueError(f"TriPlaneGenerator.{who}: the occupancy grid's batch must be B = {ws.shape[0]} or 1, got "
+                             f"{occ.batch}")
+        if float(occ.cube_length) != float(gen.cfg.box_warp):
+            raise ValueError(f"TriPlaneGenerator.{who}: the occupancy grid's cube_length {occ.cube_length} differs from "
+                             f"cfg.box_warp = {gen.cfg.box_warp}")
+        if not occ.bits.is_cuda or occ.bits.device != ws.device:
+            raise RuntimeError(f"TriPlaneGenerator.{who}: the occupancy grid lives on {occ.bits.device}, ws on {ws.device}; "
+                               f"the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
+    for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
+        if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] != ws.shape[0]:
+            raise ValueError(f"expected {name} [B, R, 3] for ws of batch {ws.shape[0]}, got {tuple(t.shape)}")
+        if not t.is_floating_point():
+            raise TypeError(f"TriPlaneGenerator.{who}: {name} must be a floating-point tensor, got {t.dtype}")
+    if ray_origins.shape != ray_directions.shape:
+        raise ValueError(f"ray_directions {tuple(ray_directions.shape)} must match ray_origins {tuple(ray_origins.shape)}")
+
+
+def limit_tensors(who: str, b: int, r: int, dev, t_near, t_far):
+    """Explicit t_near / t_far (tensors [B,R] or floats) as detached fp32 tensors; None when the call gave none."""
+    if t_near is None:
+        return None
+    limits = []
+    for name, t in (("t_near", t_near), ("t_far", t_far)):
+        if isinstance(t, torch.Tensor):
+            if t.shape != (b, r):
+                raise ValueError(f"TriPlaneGenerator.{who}: {name} must be [B, R] = [{b}, {r}] or a float, got "
+                                 f"{tuple(t.shape)}")
+            if not t.is_floating_point():
+                raise TypeError(f"TriPlaneGenerator.{who}: {name} must be a floating-point tensor, got {t.dtype}")
+            if torch.is_grad_enabled() and t.requires_grad:
+                raise NotImplementedError(f"TriPlaneGenerator.{who}: {name} requires grad, but the ray limits are not "
+                                          f"differentiated (pass {name}.detach())")
+            if not t.is_cuda:
+                raise RuntimeError(f"TriPlaneGenerator.{who}: the MI355X path needs CUDA/ROCm tensors; there is no CPU "
+                                   "fallback")
+            limits.append(t.detach().float().contiguous())
+        else:
+            limits.append(torch.full((b, r), float(t), device=dev, dtype=torch.float32))
+    return tuple(limits)
+
+
+def box_or_grid_limits(gen, ray_origins, ray_directions, occ):
+    """`ray_limits="box"` / an OccupancyGrid as tensors: one launch under no_grad, from detached rays."""
+    with torch.no_grad():
+        o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
+        return ops.ray_limits_box(o, d, gen.cfg.box_warp) if occ is None else ops.ray_limits_grid(o, d, occ)
+
+
 def resolve(gen, ws, ray_origins, ray_directions, u_strat, u_imp, noise_mode, t_near, t_far, ray_limits, normals, normal_grad,
             normal_ray_grad, samples, compact) -> RayCall:
     """Everything `render_rays` does before its first launch of the renderer: the checks (every refusal comes before the device is
@@ -47,35 +115,11 @@ def resolve(gen, ws, ray_origins, ray_directions, u_strat, u_imp, noise_mode, t_
         raise NotImplementedError("HFA-GP always passes noise_mode='const' (headnerf.py:112)")
     normal_grad = bool(normal_grad or normal_ray_grad)
     normals = bool(normals or normal_grad)
-    from .occupancy import OccupancyGrid
-    occ = ray_limits if isinstance(ray_limits, OccupancyGrid) else None
-    if ray_limits is not None and occ is None and not (isinstance(ray_limits, str) and ray_limits == "box"):
-        raise ValueError(f"TriPlaneGenerator.render_rays: ray_limits must be None or 'box' or an OccupancyGrid, got {ray_limits!r}")
-    if (t_near is None) != (t_far is None):
-        raise ValueError("TriPlaneGenerator.render_rays: t_near and t_far go together (both or neither)")
-    if ray_limits is not None and t_near is not None:
-        raise ValueError("TriPlaneGenerator.render_rays: ray_limits='box' / an OccupancyGrid and explicit t_near / t_far are "
-                         "mutually exclusive")
+    occ = check_limit_keywords("render_rays", t_near, t_far, ray_limits)
     if compact and ray_limits is None and t_near is None:
         raise ValueError("TriPlaneGenerator.render_rays: compact=True needs ray limits (t_near / t_far or ray_limits=): without "
                          "them every ray is marched")
-    if occ is not None:
-        if occ.batch not in (1, ws.shape[0]):
-            raise ValueError(f"TriPlaneGenerator.render_rays: the occupancy grid's batch must be B = {ws.shape[0]} or 1, got "
-                             f"{occ.batch}")
-        if float(occ.cube_length) != float(gen.cfg.box_warp):
-            raise ValueError(f"TriPlaneGenerator.render_rays: the occupancy grid's cube_length {occ.cube_length} differs from "
-                             f"cfg.box_warp = {gen.cfg.box_warp}")
-        if not occ.bits.is_cuda or occ.bits.device != ws.device:
-            raise RuntimeError(f"TriPlaneGenerator.render_rays: the occupancy grid lives on {occ.bits.device}, ws on {ws.device}; "
-                               f"the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
-    for name, t in (("ray_origins", ray_origins), ("ray_directions", ray_directions)):
-        if t.dim() != 3 or t.shape[-1] != 3 or t.shape[0] != ws.shape[0]:
-            raise ValueError(f"expected {name} [B, R, 3] for ws of batch {ws.shape[0]}, got {tuple(t.shape)}")
-        if not t.is_floating_point():
-            raise TypeError(f"TriPlaneGenerator.render_rays: {name} must be a floating-point tensor, got {t.dtype}")
-    if ray_origins.shape != ray_directions.shape:
-        raise ValueError(f"ray_directions {tuple(ray_directions.shape)} must match ray_origins {tuple(ray_origins.shape)}")
+    check_rays("render_rays", gen, ws, ray_origins, ray_directions, occ)
     if normal_grad and not normal_ray_grad and torch.is_grad_enabled() and (ray_origins.requires_grad or
                                                                              ray_directions.requires_grad):
         raise NotImplementedError("TriPlaneGenerator.render_rays(normal_grad=True): the rays' gradient of the normal term is opt-in "
@@ -87,26 +131,7 @@ def resolve(gen, ws, ray_origins, ray_directions, u_strat, u_imp, noise_mode, t_
     cfg = gen.cfg
     b, r = ray_origins.shape[0], ray_origins.shape[1]
     dev = ws.device
-    limits = None
-    if t_near is not None:
-        limits = []
-        for name, t in (("t_near", t_near), ("t_far", t_far)):
-            if isinstance(t, torch.Tensor):
-                if t.shape != (b, r):
-                    raise ValueError(f"TriPlaneGenerator.render_rays: {name} must be [B, R] = [{b}, {r}] or a float, got "
-                                     f"{tuple(t.shape)}")
-                if not t.is_floating_point():
-                    raise TypeError(f"TriPlaneGenerator.render_rays: {name} must be a floating-point tensor, got {t.dtype}")
-                if torch.is_grad_enabled() and t.requires_grad:
-                    raise NotImplementedError(f"TriPlaneGenerator.render_rays: {name} requires grad, but the ray limits are not "
-                                              f"differentiated (pass {name}.detach())")
-                if not t.is_cuda:
-                    raise RuntimeError("TriPlaneGenerator.render_rays: the MI355X path needs CUDA/ROCm tensors; there is no CPU "
-                                       "fallback")
-                limits.append(t.detach().float().contiguous())
-            else:
-                limits.append(torch.full((b, r), float(t), device=dev, dtype=torch.float32))
-        limits = tuple(limits)
+    limits = limit_tensors("render_rays", b, r, dev, t_near, t_far)
     params = [p for n, p in gen.named_parameters() if not n.startswith("backbone.mapping.")]
     grad = torch.is_grad_enabled() and (ws.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad or
                                         any(p.requires_grad for p in params))
@@ -122,9 +147,7 @@ def resolve(gen, ws, ray_origins, ray_directions, u_strat, u_imp, noise_mode, t_
                            f"per-sample state, {state_bytes} bytes for {b} x {r} rays, above RAY_STATE_CAP_BYTES = "
                            f"{cap}; {cap // (state_bytes // (b * r))} rays fit")
     if ray_limits is not None:
-        with torch.no_grad():
-            o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
-            call.limits = ops.ray_limits_box(o, d, cfg.box_warp) if occ is None else ops.ray_limits_grid(o, d, occ)
+        call.limits = box_or_grid_limits(gen, ray_origins, ray_directions, occ)
     if u_strat is None:
         u_strat = torch.rand(b, r, cfg.depth_resolution, device=dev)
     if u_imp is None:
@@ -373,4 +396,71 @@ def render_rays(gen, ws, ray_origins, ray_directions, *options) -> Dict[str, tor
     if call.limits is not None:
         from .cam_utils import ray_limits_valid
         out["valid"] = ray_limits_valid(*call.limits)
+    return out
+
+
+# ------------------------------------------------------------------ the first hit with the density iso-surface
+def trace_rays(gen, ws, ray_origins, ray_directions, level, steps, refine, t_near, t_far, ray_limits, normals,
+               differentiable) -> Dict[str, torch.Tensor]:
+    """`TriPlaneGenerator.trace_rays` (its docstring is the public description): the checks and the limits of `render_rays`, one
+    backbone pass, one launch (`ops.trace_rays`); with ``differentiable`` the root's implicit gradient (`ray_losses.implicit_depth`)
+    through the differentiable point query."""
+    who = "trace_rays"
+    occ = check_limit_keywords(who, t_near, t_far, ray_limits)
+    check_rays(who, gen, ws, ray_origins, ray_directions, occ)
+    if not 1 <= int(steps) <= 4096:
+        raise ValueError(f"TriPlaneGenerator.{who}: steps must be in [1, 4096], got {steps}")
+    if not 0 <= int(refine) <= 30:
+        raise ValueError(f"TriPlaneGenerator.{who}: refine must be in [0, 30], got {refine}")
+    params = [p for n, p in gen.named_parameters() if not n.startswith("backbone.mapping.")]
+    grad = bool(differentiable) and torch.is_grad_enabled() and (
+        ws.requires_grad or ray_origins.requires_grad or ray_directions.requires_grad or any(p.requires_grad for p in params))
+    gen._query_guard(who, ws, *(() if differentiable else (ray_origins, ray_directions)), differentiable=bool(differentiable))
+    if not (ray_origins.is_cuda and ray_directions.is_cuda):
+        raise RuntimeError(f"TriPlaneGenerator.{who}: the MI355X path needs CUDA/ROCm tensors; there is no CPU fallback")
+    cfg = gen.cfg
+    b, r = ray_origins.shape[0], ray_origins.shape[1]
+    dev = ws.device
+    limits = limit_tensors(who, b, r, dev, t_near, t_far)
+    has_limits = limits is not None or ray_limits is not None
+    if b == 0 or r == 0:
+        zero = 0.0 * ws.sum() + 0.0 * ray_origins.sum() + 0.0 * ray_directions.sum() if grad else 0.0     # keeps the autograd edges
+        out = {"hit": torch.zeros(b, r, device=dev, dtype=torch.bool), "cell": torch.zeros(b, r, device=dev, dtype=torch.int32),
+               "t": torch.zeros(b, r, device=dev) + zero, "point": torch.zeros(b, r, 3, device=dev) + zero,
+               "sigma": torch.zeros(b, r, device=dev)}
+        if normals or grad:
+            out.update(sigma_grad=torch.zeros(b, r, 3, device=dev), normal=torch.zeros(b, r, 3, device=dev))
+        if has_limits:
+            out["valid"] = torch.zeros(b, r, device=dev, dtype=torch.bool)
+        return out
+    if grad and (getattr(gen, "_grad_sink", None) is not None or getattr(gen, "_grad_inplace", False)):
+        raise RuntimeError("TriPlaneGenerator.trace_rays(differentiable=True) inside a trainer step scope: its backward is a second "
+                           "backbone pass and would release every parameter to the gradient sink twice — trace under no_grad and "
+                           "pass the points through `synthesis(..., query=)` with `ray_losses.implicit_depth` instead")
+    if ray_limits is not None:
+        limits = box_or_grid_limits(gen, ray_origins, ray_directions, occ)
+    elif limits is None:
+        limits = tuple(torch.full((b, r), float(v), device=dev, dtype=torch.float32) for v in (cfg.ray_start, cfg.ray_end))
+    want = ops._TRACE_OUT if (normals or grad) else tuple(k for k in ops._TRACE_OUT if k not in ("sigma_grad", "normal"))
+    with torch.no_grad():
+        planes, pam = gen._query_planes(ws)
+        o, d = ray_origins.detach().float().contiguous(), ray_directions.detach().float().contiguous()
+        out = gen._timed("trace_rays", float(b), ops.trace_rays, planes, o, d, limits[0], limits[1], float(level), int(steps),
+                         int(refine), pam, want, **gen._query_kwargs())
+    out["hit"] = out["hit"].bool()
+    if has_limits:
+        from .cam_utils import ray_limits_valid
+        out["valid"] = ray_limits_valid(*limits)
+    if grad:
+        from .ray_losses import implicit_depth, transversal
+        # the rays on the formula; every other ray keeps 't' and 'point' as constants
+        carries = out["hit"] & (out["cell"] > 0) & transversal(out["sigma_grad"], d)
+        t0, x0 = out["t"], out["point"]
+        # the hit point as a function of the rays (t held fixed), so that the point query's backward reaches them
+        x = torch.where(carries[..., None], ray_origins + t0[..., None] * ray_directions, x0)
+        sig = gen.sample_mixed(x, None, ws, differentiable=True)["sigma"]
+        out["t"] = t = implicit_depth(t0, sig, out["sigma_grad"], d, mask=carries)
+        out["point"] = torch.where(carries[..., None], ray_origins + t[..., None] * ray_directions, x0)
+        if not normals:
+            del out["sigma_grad"], out["normal"]
     return out

@@ -4,12 +4,14 @@ Plain torch, any device and dtype; differentiable w.r.t. ``sample_weights`` (``s
 Inputs throughout: ``sample_depths`` [..., S], ascending, and ``sample_weights`` [..., S-1], where w_e is the compositing weight
 of the interval [t_e, t_{e+1}] with midpoint t̄_e = (t_e + t_{e+1}) / 2 and width Δ_e = t_{e+1} - t_e.  An empty ray (all-zero rows
 in both) gives 0 in `distortion_loss` and `depth_variance`, and its upper end — 0 — in `quantile_depth`.
+`implicit_depth` is the odd one out: it works on the outputs of ``TriPlaneGenerator.trace_rays`` and makes a traced surface depth
+differentiable.
 """
 from __future__ import annotations
 
 import torch
 
-__all__ = ["distortion_loss", "quantile_depth", "depth_variance"]
+__all__ = ["distortion_loss", "quantile_depth", "depth_variance", "implicit_depth", "transversal"]
 
 
 def _check(sample_depths: torch.Tensor, sample_weights: torch.Tensor) -> None:
@@ -75,3 +77,39 @@ def depth_variance(sample_depths: torch.Tensor, sample_weights: torch.Tensor) ->
     d = (w * mid).sum(-1, keepdim=True) / safe
     var = (w * (mid - d) ** 2).sum(-1, keepdim=True) / safe
     return torch.where(hit, var, torch.zeros_like(var)).squeeze(-1)
+
+
+def transversal(sigma_grad: torch.Tensor, directions: torch.Tensor, slope_floor: float = 0.01) -> torch.Tensor:
+    """The rays that enter the surface at a slope `implicit_depth` accepts, bool [...]: g·d ≥ ``slope_floor``·‖g‖·‖d‖ and g·d > 0 for
+    g = ``sigma_grad`` [..., 3] and d = ``directions`` [..., 3] (the density rises along the ray; a grazing crossing is left out)."""
+    gd = (sigma_grad * directions).sum(-1)
+    return (gd >= slope_floor * sigma_grad.norm(dim=-1) * directions.norm(dim=-1)) & (gd > 0)
+
+
+def implicit_depth(t: torch.Tensor, sigma: torch.Tensor, sigma_grad: torch.Tensor, directions: torch.Tensor,
+                   slope_floor: float = 0.01, mask=None) -> torch.Tensor:
+    """A traced surface depth made differentiable by the implicit function theorem, [...]: the value of ``t`` with the gradient of
+    the root of σ(o + t·d) = level.  ``t`` [...]: the root a trace found (`TriPlaneGenerator.trace_rays` under no_grad), a constant
+    here; ``sigma`` [...] (or [..., 1]): the raw density at the hit point o + t·d, evaluated DIFFERENTIABLY — `sample_mixed(...,
+    differentiable=True)`, or `synthesis(query=)` inside a trainer step, so that the surface term shares the image's backward pass;
+    when the rays need a gradient too, form the point from them (t detached); ``sigma_grad`` [..., 3]: g = ∂σ/∂x there, a constant;
+    ``directions`` [..., 3]: d, a constant.  Returns
+
+        t − (σ − σ.detach()) / (g·d)        dt = −dσ / (g·d): moving the field by dσ at the hit moves the root by that much
+
+    A ray carries this gradient only where the crossing is transversal, g·d ≥ ``slope_floor``·‖g‖·‖d‖ (and g·d > 0), and, with
+    ``mask`` (bool [...]), inside the mask — pass ``hit & (cell > 0)``: a miss has no root and a ray that starts inside has the
+    constant t = t_near.  Every other ray returns ``t`` as a constant: exactly zero gradient.  Plain torch, any device and dtype."""
+    if sigma.dim() == t.dim() + 1 and sigma.shape[-1] == 1:
+        sigma = sigma.squeeze(-1)
+    if sigma.shape != t.shape or sigma_grad.shape != t.shape + (3,) or directions.shape != sigma_grad.shape:
+        raise ValueError(f"expected t [...], sigma [...] or [..., 1], sigma_grad and directions [..., 3], got {tuple(t.shape)}, "
+                         f"{tuple(sigma.shape)}, {tuple(sigma_grad.shape)}, {tuple(directions.shape)}")
+    t = t.detach().to(sigma.dtype)
+    g, d = sigma_grad.detach().to(sigma.dtype), directions.detach().to(sigma.dtype)
+    gd = (g * d).sum(-1)
+    ok = transversal(g, d, slope_floor)
+    if mask is not None:
+        ok = ok & mask
+    step = (sigma - sigma.detach()) / torch.where(ok, gd, torch.ones_like(gd))
+    return t - torch.where(ok, step, torch.zeros_like(step))

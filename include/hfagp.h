@@ -28,6 +28,8 @@
  *                              density volume of gen_samples.py --shapes (create_samples lattice), one launch (ABI 13)
  *   hfagp_planes_query_normals[_bwd] <- (no reference counterpart: autograd of sample_mixed's sigma w.r.t. the points, i.e. the
  *                              density gradient and surface normal at a point, and what a loss on them back-propagates)
+ *   hfagp_trace_rays        <- (no reference counterpart: the first hit of a ray list with the density iso-surface that marching
+ *                              cubes exports — t, point, density gradient and normal per ray)
  *   hfagp_marching_cubes_count / _emit (+ _workspace_bytes) <- the .ply mesh of gen_samples.py --shapes
  *                              (skimage.measure.marching_cubes + plyfile in EG3D's shape_utils), on the GPU (ABI 14)
  *   hfagp_raymarch_normals  <- (no reference counterpart: the per-ray surface normal map of EG3D-family geometry renders — the
@@ -316,6 +318,56 @@ int hfagp_planes_query_normals(const HfagpPlanesQueryArgs* a, float* grad /* [B]
  * box_warp.  HFAGP_EUNSUPPORTED, nothing launched: a->coords NULL (no grid mode); H * W > 2^25.                                */
 int hfagp_planes_query_normals_bwd(const HfagpPlanesQueryBwdArgs* a /* g_sigma, g_rgb, d_coords must be NULL */,
                                    const float* g_grad, const float* g_normal, void* stream);
+
+/* ------------------------------------------------------------------ surface tracing (additive to ABI 15)
+ * The first hit of every ray of a list with the iso-surface sigma = level of the raw density (the surface hfagp_marching_cubes
+ * extracts from a density lattice at the same level), one launch.  Rays as hfagp_raymarch_rays_limits_fwd takes them: origins and
+ * directions [B][R][3] in world units, directions NOT normalised (a point is o + t d), per-ray limits [B][R].  sigma(x) below is the
+ * raw density of hfagp_planes_query at the world point x, to the bit (split fp16 decoder given planes_absmax, exact fp32 without).
+ * Every operation of the ray arithmetic is rounded to fp32 on its own (no fused multiply-add), as torch evaluates the expressions:
+ *   empty ray   unless both limits are finite and t_far > t_near: a miss, nothing is evaluated for it
+ *   nodes       dt = (t_far - t_near) / fp32(steps);  t_i = t_near + fp32(i) * dt for i < steps, t_steps = t_far;  x = o + t * d
+ *   coarse      cell = the first i in 0..steps with sigma(x(t_i)) >= level (a NaN density never hits); none: a miss, cell = -1;
+ *               cell = 0: the origin is inside already, t = t_near
+ *   refine      for cell > 0: lo = t_{cell-1}, hi = t_cell with their densities s_lo, s_hi; `refine` times mid = 0.5 * (lo + hi) and
+ *               sigma(x(mid)) >= level replaces (hi, s_hi), anything else (lo, s_lo); then one secant step
+ *               t = lo + (level - s_lo) / (s_hi - s_lo) * (hi - lo) clamped into [lo, hi], or t = hi unless s_hi - s_lo > 0
+ *   at the hit  point = o + t * d;  sigma, sigma_grad = g and normal = n of hfagp_planes_query_normals at that point (its bits)
+ * Outputs, each optional (at least one), [B][R] (x 3 for point, sigma_grad, normal): hit (0 / 1), cell, t, point, sigma, sigma_grad,
+ * normal.  A miss (empty rays included) writes hit = 0, cell = -1 and exact zeros everywhere else: never NaN or inf.  One writer
+ * per ray, no atomics: two calls give the same bits, whichever outputs are asked for.  About cell + 1 + refine + 1 density
+ * evaluations per hit, steps + 1 per miss (a tile of 16 rays marches until its last ray is decided).
+ * HFAGP_EBADARG, nothing launched: a, the planes, a decoder tensor, the rays or a limit NULL; no output given; steps outside
+ * [1, 4096]; refine outside [0, 30]; bad B / H / W / R / plane_axes / box_warp.  HFAGP_EUNSUPPORTED: H * W > 2^25.              */
+typedef struct {
+    const float* planes;         /* [B][3][H][W][32] fp32 (as HfagpRaymarchArgs::planes)                                    */
+    const float* ray_origins;    /* [B][R][3]                                                                               */
+    const float* ray_directions; /* [B][R][3], taken as given                                                               */
+    const float* t_near;         /* [B][R]                                                                                  */
+    const float* t_far;          /* [B][R]                                                                                  */
+    const float* dec_w0;         /* decoder.net.0.weight [64][32]  (raw parameter)                                          */
+    const float* dec_b0;         /* decoder.net.0.bias   [64]                                                               */
+    const float* dec_w1;         /* decoder.net.2.weight [33][64]                                                           */
+    const float* dec_b1;         /* decoder.net.2.bias   [33]                                                               */
+    const float* planes_absmax;  /* optional, as HfagpPlanesQueryArgs::planes_absmax                                        */
+    uint8_t*     hit;            /* optional out [B][R]                                                                     */
+    int32_t*     cell;           /* optional out [B][R]                                                                     */
+    float*       t;              /* optional out [B][R]                                                                     */
+    float*       point;          /* optional out [B][R][3]                                                                  */
+    float*       sigma;          /* optional out [B][R]                                                                     */
+    float*       sigma_grad;     /* optional out [B][R][3]                                                                  */
+    float*       normal;         /* optional out [B][R][3]                                                                  */
+    int64_t R;                   /* rays per frame (> 0)                                                                    */
+    int32_t B, H, W;             /* frames, plane height / width (> 1)                                                      */
+    int32_t plane_axes;          /* 0: (x,y),(x,z),(z,x) [eg3d original]; 1: third = (z,y)                                  */
+    int32_t steps;               /* coarse intervals per ray, 1 .. 4096                                                     */
+    int32_t refine;              /* bisections of the bracket, 0 .. 30                                                      */
+    float level;                 /* raw density of the surface (the unit of hfagp_planes_query's sigma)                     */
+    float decoder_lr_mul;
+    double box_warp;
+} HfagpTraceRaysArgs;
+
+int hfagp_trace_rays(const HfagpTraceRaysArgs* a, void* stream);
 
 /* ------------------------------------------------------------------ marching cubes (ABI 14)
  * The iso-surface of a fp32 volume V[n0][n1][n2] (last axis fastest, each extent >= 2) as a welded triangle mesh.
