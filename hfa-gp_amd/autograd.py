@@ -324,10 +324,15 @@ class _Backward:
         self.pending = []
 
 
-def _backbone_backward(bw: _Backward, gen, backbone_tape, d_planes: torch.Tensor, b: int, dev) -> None:
+def _backbone_backward(bw: _Backward, gen, backbone_tape, d_planes: torch.Tensor, b: int, dev, views: Optional[int] = None) -> None:
     """d planes [B,3,R,R,32] → the backbone blocks, last block first, then the style gradients of the whole pass into bw.d_ws.
-    Shared by the backward of `synthesis` (after the renderer's adjoint) and of `sample_mixed(differentiable=True)`."""
-    g_img_b = ops.planes_to_nhwc(d_planes)
+    Shared by the backward of `synthesis` (after the renderer's adjoint) and of `sample_mixed(differentiable=True)`.
+    `views` = V of a multi-view `synthesis`: d_planes is per frame, [B·V,3,R,R,32], and the sum over an identity's views rides in the
+    layout change (ops.planes_sum_to_nhwc) in front of the one pass at batch B."""
+    if views is None:
+        g_img_b = ops.planes_to_nhwc(d_planes)
+    else:
+        g_img_b = ops.planes_sum_to_nhwc(d_planes.view(b, views, *d_planes.shape[1:]))
     dxs, nxt = None, None
     walk = list(reversed(backbone_tape))
     side = gen.side_stream(b, dev) if all(not r["rgb"]["small"] for r in walk) else None
@@ -378,7 +383,11 @@ class SynthesisFn(torch.autograd.Function):
     image_depth / image_mask join it as g_depth / g_wsum), the camera label's passes, then — each only if its gradient arrived,
     each adding into the renderer's d_planes and decoder gradients, and after raymarch_bwd, which overwrites plane 2 on mirrored
     planes — ops.planes_query_bwd, ops.planes_query_normals_bwd, ops.raymarch_normals_bwd; last the one backbone pass, which serves
-    every loss term and releases every parameter to the gradient sink once."""
+    every loss term and releases every parameter to the gradient sink once.
+    Multi-view (`call.views` = V; ws [B], c the flattened label [B·V,25], the per-frame outputs flat over f = b·V + v): two batch
+    sizes in the one backward.  Down to the planes it works at B·V frames — the SR blocks on the repeated ws rows, their style
+    gradients flushed early and summed over the views into d_ws; the renderer's adjoints on a transient per-frame copy of the planes,
+    into a per-frame d_planes — then the view sum rides in the layout change (ops.planes_sum_to_nhwc) and the backbone runs at B."""
 
     @staticmethod
     def forward(ctx, ws, c, u_strat, u_imp, query, call, gen, *params):
@@ -417,10 +426,14 @@ class SynthesisFn(torch.autograd.Function):
                                "(several GB at 512^2) are released by the first backward pass; sum the losses before "
                                "calling backward instead of backpropagating them one by one (retain_graph is not supported)")
         cfg = gen.cfg
-        b = tape["batch"]
+        b = tape["batch"]                            # frames: B, or B·V of a multi-view call
+        ids, views = ctx.ws_shape[0], tape["views"]
+        multi = views is not None and views > 1      # two batch sizes in this pass: B·V down to the planes, B in the backbone
         dev = tape["planes"].device
         d_ws = torch.zeros(ctx.ws_shape, device=dev, dtype=torch.float32)
-        bw = _Backward(gen, tape, d_ws, ctx.ws_c, ctx.pg)
+        # (multi-view: the SR blocks' style gradients are per frame, on the ws rows their styles were computed from)
+        bw = _Backward(gen, tape, torch.zeros_like(tape["ws_frames"]) if multi else d_ws, tape["ws_frames"] if multi else ctx.ws_c,
+                       ctx.pg)
         if g_img is None:
             g_img = torch.zeros(b, cfg.img_channels, cfg.img_resolution, cfg.img_resolution, device=dev)
         g_img = g_img.float().contiguous()
@@ -442,6 +455,14 @@ class SynthesisFn(torch.autograd.Function):
                                  g_nchw3_b=None if g_raw is None or resampled else g_raw.float().contiguous())
         c0rec0["ds"] = s[:, 0]
         bw.finish_layer(c0rec0)
+        if multi:
+            # the six SR layers' style gradients now, at B·V rows, and their sum over the views into the identities' d_ws; from here
+            # on the pass works at batch B (the backbone's styles are flushed into d_ws at its end, as in a single-view call)
+            bw.flush_styles()
+            bw.release_ready()
+            d_ws += bw.d_ws.view(ids, views, *bw.d_ws.shape[1:]).sum(1)
+            bw.d_ws, bw.ws = d_ws, ctx.ws_c
+        planes = gen._per_frame(tape["planes"], views)       # (multi-view: a transient per-frame copy, as in the forward)
         if resampled:
             # adjoint of the resample in front of the SR blocks: their gradient back at the rays' resolution, with image_raw's (taken
             # from the unresampled feature image) added in the same pass
@@ -462,11 +483,12 @@ class SynthesisFn(torch.autograd.Function):
         dec_direct = ctx.pg and os.environ.get("HFAGP_DEV_DEC_DIRECT", "0") == "1" and all(bw._direct(p) for p in dec_prm)
         need_c = ctx.needs_input_grad[1]
         rec_out = [] if need_c else None
-        rb = gen._timed("raymarch_bwd", float(b), ops.raymarch_bwd, g_feat.view(b, res * res, 32), tape["planes"],
+        rb = gen._timed("raymarch_bwd", float(b), ops.raymarch_bwd, g_feat.view(b, res * res, 32), planes,
                         u_strat=tape["u_strat"], u_imp=tape["u_imp"], decoder_grads=ctx.pg,
                         planes_absmax=tape.get("planes_absmax"), state=tape.get("ray_state"),
                         dec_out=tuple(p.grad for p in dec_prm) if dec_direct else None, rec_out=rec_out,
                         **geom, **gen._render_args(tape["c"], res))
+        d_planes, dec = rb if ctx.pg else (rb, None)      # per frame: [B·V,3,R,R,32] in a multi-view call
         d_c = None
         g_nrm = None
         if g_normal is not None:
@@ -474,46 +496,48 @@ class SynthesisFn(torch.autograd.Function):
         if need_c:      # the camera label: positional derivative of the gather along every ray, then the adjoint of the ray generation
             nrm_c = g_nrm is not None and call.normal_camera_grad       # the normal term joins the per-ray records: one reduction for the loss
             d_c2w, d_intr, ray_grad = gen._timed("raymarch_bwd_camera", float(b), ops.raymarch_bwd_camera, g_feat.view(b, res * res, 32),
-                                                 tape["planes"], rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
+                                                 planes, rec_out[0], u_strat=tape["u_strat"], u_imp=tape["u_imp"],
                                                  planes_absmax=tape.get("planes_absmax"), reduce=not nrm_c,
                                                  **gen._render_args(tape["c"], res))
             if nrm_c:
                 d_c2w, d_intr, _ = gen._timed("raymarch_normals_bwd_camera", float(b), ops.raymarch_normals_bwd_camera, g_nrm,
-                                              tape["planes"], tape["ray_state"], ray_grad=ray_grad, u_strat=tape["u_strat"],
+                                              planes, tape["ray_state"], ray_grad=ray_grad, u_strat=tape["u_strat"],
                                               u_imp=tape["u_imp"], planes_absmax=tape.get("planes_absmax"),
                                               **gen._render_args(tape["c"], res))
             d_c = torch.cat((d_c2w, d_intr), 1).to(ctx.c_dtype)
         d_coords = None
+        # the two point-query launches work on the identities' planes: they add into d_planes itself, or — multi-view, where d_planes
+        # is per frame — into one buffer at batch B of their own (made by the first of them) that joins the identity's first view
+        d_q = None if multi else d_planes
         if g_qsigma is not None or g_qrgb is not None:
             # the point query of synthesis(query=): its plane gradient joins the renderer's BEFORE the one backbone pass, its decoder
             # gradients land in the renderer's four tensors.  After raymarch_bwd has returned: that call overwrites plane 2 on
             # mirrored planes (mirror_plane_kernel), this one adds to every plane.
-            _, d_coords = gen._timed("planes_query_bwd", float(b), _query_backward, gen, tape["planes"], call.query,
-                                     tape.get("planes_absmax"), g_qsigma, g_qrgb, rb[0] if ctx.pg else rb, need_coords,
-                                     rb[1] if ctx.pg else None)
+            d_q, d_coords = gen._timed("planes_query_bwd", float(ids), _query_backward, gen, tape["planes"], call.query,
+                                       tape.get("planes_absmax"), g_qsigma, g_qrgb, d_q, need_coords, dec)
         if g_qgrad is not None or g_qnormal is not None:
             # 'query_sigma_grad' / 'query_normal' of synthesis(query_normals=True): one launch that adds into the same d_planes and
             # decoder gradients, after raymarch_bwd for the point query's reason (it adds to every plane at its true texels)
-            gen._timed("planes_query_normals_bwd", float(b), _query_normals_backward, gen, tape["planes"], call.query,
-                       tape.get("planes_absmax"), g_qgrad, g_qnormal, rb[0] if ctx.pg else rb, rb[1] if ctx.pg else None)
+            d_q = gen._timed("planes_query_normals_bwd", float(ids), _query_normals_backward, gen, tape["planes"], call.query,
+                             tape.get("planes_absmax"), g_qgrad, g_qnormal, d_q, dec)
+        if multi and d_q is not None:
+            d_planes.view(ids, views, *d_planes.shape[1:])[:, 0] += d_q
         if g_normal is not None:
             # 'image_normal' of synthesis(normal_grad=True): one launch that adds into the renderer's d_planes and decoder gradients,
             # after raymarch_bwd for the same reason as the point query (it adds to every plane at its true texels)
-            gen._timed("raymarch_normals_bwd", float(b), ops.raymarch_normals_bwd, g_nrm, tape["planes"], tape["ray_state"],
+            gen._timed("raymarch_normals_bwd", float(b), ops.raymarch_normals_bwd, g_nrm, planes, tape["ray_state"],
                        u_strat=tape["u_strat"], u_imp=tape["u_imp"], planes_absmax=tape.get("planes_absmax"),
-                       d_planes=rb[0] if ctx.pg else rb, decoder_grads=ctx.pg, dec_out=rb[1] if ctx.pg else None,
+                       d_planes=d_planes, decoder_grads=ctx.pg, dec_out=dec,
                        **gen._render_args(tape["c"], res))
+        del planes
         if ctx.pg:
-            d_planes, dec = rb
             for prm, g in zip(dec_prm, dec):
                 if dec_direct:
                     bw._mark_direct(prm)
                 else:
                     bw._acc(prm, g)
             bw.release_ready()
-        else:
-            d_planes = rb
-        _backbone_backward(bw, gen, tape["backbone"], d_planes, b, dev)
+        _backbone_backward(bw, gen, tape["backbone"], d_planes, ids, dev, views)
         ctx.tape = ctx.call = None
         if d_coords is not None:
             d_coords = d_coords.to(ctx.q_dtype)

@@ -84,6 +84,21 @@ def cam_sampler(batch: int, device, horizontal_mean=0.5, vertical_mean=0.5, hori
     return make_label(create_cam2world_matrix(-pts, pts, device=device))
 
 
+def orbit_labels(n: int, r: float = 2.7, yaw_range: float = 0.35, pitch_range: float = 0.25, pitch_offset: float = -0.05,
+                 intrinsics=FFHQ_INTRINSICS, device=None) -> torch.Tensor:
+    """The n cameras of a turntable around the head, labels [n,25] (un-flipped, as `sample_camera_positions` gives them): camera i
+    stands on the sphere of radius r at yaw h_i = π/2 + yaw_range·sin(2πi/n) and pitch v_i = π/2 + pitch_offset +
+    pitch_range·cos(2πi/n) — `sample_camera_positions`' angles: p = r·(sin v cos h, cos v, sin v sin h) — and looks at the origin.
+    `synthesis(ws, orbit_labels(V)[None].expand(B, -1, -1))` renders the V views of every latent on one backbone pass."""
+    if int(n) != n or n < 1:
+        raise ValueError(f"orbit_labels: n must be a positive integer, got {n!r}")
+    t = 2.0 * math.pi * torch.arange(int(n), dtype=torch.float, device=device) / int(n)
+    h = 0.5 * math.pi + yaw_range * torch.sin(t)
+    v = 0.5 * math.pi + pitch_offset + pitch_range * torch.cos(t)
+    pts = r * torch.stack((torch.sin(v) * torch.cos(h), torch.cos(v), torch.sin(v) * torch.sin(h)), dim=-1)
+    return make_label(create_cam2world_matrix(-normalize_vecs(pts), pts, device=device), intrinsics)
+
+
 def ray_grid(c: torch.Tensor, res: int, window=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """EG3D's RaySampler for a label, in plain torch: c [B,25] → (origins, directions), each [B, res*res, 3], pixel centres of a
     res x res image in row order, unit directions — the rays `synthesis` marches when res is the rendering resolution, and the rays

@@ -471,6 +471,29 @@ __global__ void __launch_bounds__(256) planes_to_nhwc_kernel(const float* __rest
         *reinterpret_cast<const float4*>(pm + ((((size_t)b * 3 + pl) * H + yy) * W + x) * Cp + ch);
 }
 
+// the same layout change with the sum over V views of one identity in front of it: pm [B][V][3][H][W][Cp] (the per-frame plane
+// gradients of a multi-view call, frame b*V + v) -> y [B][H][W][3*Cp], y = pm[b][0] + pm[b][1] + ... in that order (fp32, no
+// atomics: reproducible to the bit).  One thread per output float4: V independent 16-byte loads, one store; V = 1 is the copy above.
+__global__ void __launch_bounds__(256) planes_sum_to_nhwc_kernel(const float* __restrict__ pm, float* __restrict__ y,
+                                                                 int B, int V, int H, int W, int Cp) {
+    const int C4 = (3 * Cp) >> 2;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= (long long)B * H * W * C4) return;
+    const int c4 = (int)(tid % C4);
+    const long long pix = tid / C4;
+    const int x = (int)(pix % W), yy = (int)((pix / W) % H), b = (int)(pix / ((long long)W * H));
+    const int c = c4 * 4, pl = c / Cp, ch = c % Cp;
+    const size_t frame = (size_t)3 * H * W * Cp;
+    const float* src = pm + (size_t)b * V * frame + (((size_t)pl * H + yy) * W + x) * Cp + ch;
+    float4 acc = *reinterpret_cast<const float4*>(src);
+#pragma unroll 4
+    for (int v = 1; v < V; ++v) {
+        const float4 t = *reinterpret_cast<const float4*>(src + (size_t)v * frame);
+        acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w;
+    }
+    reinterpret_cast<float4*>(y)[tid] = acc;
+}
+
 // ---------------------------------------------------------------- styles -> latent
 // dstot[b][i] = gain * ( ds[b][i] - s[b][i]/gain... ) see host comment; wave per (b, i)
 __global__ void __launch_bounds__(256) style_bwd_ds_kernel(const float* __restrict__ ds, const float* __restrict__ dd,
@@ -670,6 +693,16 @@ int hfagp_planes_to_nhwc(const float* pm, float* y, int32_t B, int32_t H, int32_
     const long long total = (long long)B * H * W * (3 * Cp / 4);
     planes_to_nhwc_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(pm, y, B, H, W, Cp);
     return check_launch("planes_to_nhwc");
+}
+
+int hfagp_planes_sum_to_nhwc(const float* pm, float* y, int32_t B, int32_t V, int32_t H, int32_t W, int32_t Cp, void* stream) {
+    HFAGP_REQUIRE(pm && y, HFAGP_EBADARG, "planes_sum_to_nhwc: null pointer");
+    HFAGP_REQUIRE(B >= 1 && V >= 1 && H >= 1 && W >= 1, HFAGP_EBADARG, "planes_sum_to_nhwc: B=%d V=%d H=%d W=%d", B, V, H, W);
+    HFAGP_REQUIRE(Cp >= 4 && Cp % 4 == 0, HFAGP_EUNSUPPORTED, "planes_sum_to_nhwc: Cp=%d", Cp);
+    const long long total = (long long)B * H * W * (3 * Cp / 4);
+    HFAGP_REQUIRE((total + 255) / 256 < (1ll << 31), HFAGP_EUNSUPPORTED, "planes_sum_to_nhwc: %lld float4 outputs", total);
+    planes_sum_to_nhwc_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(pm, y, B, V, H, W, Cp);
+    return check_launch("planes_sum_to_nhwc");
 }
 
 int hfagp_style_batch_bwd(const HfagpStyleBwdItem* items, int32_t n, void* stream) {

@@ -735,8 +735,11 @@ class TriPlaneGenerator(nn.Module):
             raise RuntimeError(f"TriPlaneGenerator.synthesis: tensors live on {ws.device} but the current device is "
                                f"cuda:{torch.cuda.current_device()}; the kernels are enqueued on the CURRENT device's "
                                f"stream — wrap the call in `with torch.cuda.device(ws.device):`")
-        if ws.shape[1:] != (cfg.num_ws, cfg.w_dim) or c.shape[1] != cfg.c_dim:
-            raise ValueError(f"expected ws [B,{cfg.num_ws},{cfg.w_dim}] and c [B,{cfg.c_dim}], got "
+        if c.dim() not in (2, 3):
+            raise ValueError(f"expected c [B,{cfg.c_dim}] (one camera per latent) or [B,V,{cfg.c_dim}] (V views of every latent), got "
+                             f"{tuple(c.shape)}")
+        if ws.shape[1:] != (cfg.num_ws, cfg.w_dim) or c.shape[-1] != cfg.c_dim or (c.dim() == 3 and c.shape[0] != ws.shape[0]):
+            raise ValueError(f"expected ws [B,{cfg.num_ws},{cfg.w_dim}] and c [B,{cfg.c_dim}] or [B,V,{cfg.c_dim}], got "
                              f"{tuple(ws.shape)} and {tuple(c.shape)}")
 
     def _set_resolution(self, b: int, n: Optional[int], u_strat, u_imp) -> None:
@@ -762,10 +765,11 @@ class TriPlaneGenerator(nn.Module):
             raise NotImplementedError("TriPlaneGenerator.synthesis(normal_grad=True): the camera gradient of the normal term is opt-in "
                                       "(c.requires_grad): pass normal_camera_grad=True for it, detach the label, or use normals=True "
                                       "for a detached map")
+        frames = c.numel() // cfg.c_dim          # B, or B·V of a multi-view label
         frame_bytes = self.neural_rendering_resolution ** 2 * (cfg.depth_resolution + cfg.depth_resolution_importance) * 140
-        if ws.shape[0] * frame_bytes > RAY_STATE_CAP_BYTES:
+        if frames * frame_bytes > RAY_STATE_CAP_BYTES:
             raise RuntimeError(f"TriPlaneGenerator.synthesis(normal_grad=True): the backward of 'image_normal' reads the ray marcher's "
-                               f"per-sample state, {ws.shape[0] * frame_bytes} bytes for {ws.shape[0]} frames, above "
+                               f"per-sample state, {frames * frame_bytes} bytes for {frames} frames, above "
                                f"RAY_STATE_CAP_BYTES = {RAY_STATE_CAP_BYTES}; {RAY_STATE_CAP_BYTES // frame_bytes} frames fit")
 
     def _forward_impl(self, call, ws, c, tape):
@@ -777,7 +781,7 @@ class TriPlaneGenerator(nn.Module):
         self._in_forward = True          # (backbone_planes / superres below must not rebuild the images a second time)
         try:
             img, rgb_raw, depth, mask, normal, call.planes, call.feature_image = self._forward_body(
-                ws, c, call.u_strat, call.u_imp, tape, call.geometry, call.normals)
+                ws, c, call.u_strat, call.u_imp, tape, call.geometry, call.normals, call.views)
         finally:
             self._in_forward = False
         q = {}
@@ -789,15 +793,30 @@ class TriPlaneGenerator(nn.Module):
             q["sigma"], q["rgb"] = ops.planes_query(call.planes, call.query, planes_absmax=pam, **self._query_kwargs())
         return img, rgb_raw, depth, mask, q.get("sigma"), q.get("rgb"), q.get("grad"), q.get("normal"), normal
 
-    def _forward_body(self, ws, c, u_strat, u_imp, tape, geometry, normals):
-        """→ image, image_raw, depth, the opacity image [B,1,r,r] (`geometry`; else None), 'image_normal' (`normals`: the same
-        per-sample results feed the normal pass; else None), planes, feat_img."""
+    @staticmethod
+    def _per_frame(t: torch.Tensor, views: Optional[int]) -> torch.Tensor:
+        """A per-identity tensor [B, ...] as the per-frame one [B·V, ...] of a multi-view call, frame b·V + v reading identity b: a copy
+        (V > 1), or `t` itself (a single-view call, and V = 1)."""
+        if views is None or views == 1:
+            return t
+        # (.contiguous(): at B = 1 the reshape alone is still the stride-0 view)
+        return t[:, None].expand(-1, views, *t.shape[1:]).reshape(-1, *t.shape[1:]).contiguous()
+
+    def _forward_body(self, ws, c, u_strat, u_imp, tape, geometry, normals, views=None):
+        """→ image, image_raw, depth, the opacity image [F,1,r,r] (`geometry`; else None), 'image_normal' (`normals`: the same
+        per-sample results feed the normal pass; else None), planes, feat_img.  `views` = V of a multi-view call (c is then the
+        flattened label [B·V, 25]): the backbone runs at batch B, everything from the planes on at F = B·V frames, frame b·V + v on
+        the planes and the ws rows of identity b; every result but `planes` [B] is per frame.  None: F = B."""
         cfg = self.cfg
-        b = ws.shape[0]
+        ids = ws.shape[0]
         res, res_sr = self.neural_rendering_resolution, cfg.neural_rendering_resolution      # rays marched; the SR blocks' input
         bb_tape = [] if tape is not None else None
         sr_tape = [] if tape is not None else None
-        planes = self.backbone_planes(ws, bb_tape)
+        planes_id = self.backbone_planes(ws, bb_tape)
+        # the renderer's kernels index the planes by frame: the V frames of an identity read a transient copy of its planes (V·|planes|
+        # bytes, 25 MB per frame at 256² — a ninth of a frame's ray state); the tape keeps the identity's one set
+        planes, ws = self._per_frame(planes_id, views), self._per_frame(ws, views)
+        b = ids if views is None else ids * views
         u_strat, u_imp = self._uniforms(b, ws.device, u_strat, u_imp)
         pam = getattr(self, "_planes_absmax", None)
         # a step that will be differentiated keeps the ray marcher's per-sample results (220 MB per frame at 128^2 rays x 96
@@ -818,6 +837,7 @@ class TriPlaneGenerator(nn.Module):
             normal = normal.view(b, res, res, 3).permute(0, 3, 1, 2).contiguous()      # NCHW, 'image_normal'
             if tape is None:
                 ray_state = None                  # (not needed again: released before the super-resolution allocates)
+        del planes                                # (so is a multi-view call's per-frame copy)
         # MipRayMarcher2 clamps the expected depth to the GLOBAL min/max sample depth of the batch
         depth = ops.depth_clamp_(depth, tmm)
         feat_img = feat.view(b, res, res, 32)                             # channels-last
@@ -831,11 +851,13 @@ class TriPlaneGenerator(nn.Module):
         img = self.superres(rgb_sr, feat_sr, ws, sr_tape)
         if tape is not None:
             # (feat_img: the SR blocks' input, what their backward reads; res: the backward marches the forward's rays)
-            tape.update(backbone=bb_tape, sr=sr_tape, planes=planes, c=c, u_strat=u_strat, u_imp=u_imp,
-                        feat_img=feat_sr, res=res, batch=b, planes_absmax=pam, ray_state=ray_state)
+            # (batch: the frames; planes: the identities' — a multi-view backward expands them again for the renderer's adjoints —
+            # ws_frames: the rows the SR blocks' styles were computed from)
+            tape.update(backbone=bb_tape, sr=sr_tape, planes=planes_id, c=c, u_strat=u_strat, u_imp=u_imp,
+                        feat_img=feat_sr, res=res, batch=b, planes_absmax=pam, ray_state=ray_state, views=views, ws_frames=ws)
             if geometry:      # the clamp range of the depth, for its adjoint (autograd.SynthesisFn.backward)
                 tape["depth_range"] = ops.depth_range(tmm)
-        return img, rgb_raw, depth.view(b, 1, res, res), wsum.view(b, 1, res, res) if geometry else None, normal, planes, feat_img
+        return img, rgb_raw, depth.view(b, 1, res, res), wsum.view(b, 1, res, res) if geometry else None, normal, planes_id, feat_img
 
     def synthesis(self, ws: torch.Tensor, c: torch.Tensor, noise_mode: str = "const",
                   u_strat: Optional[torch.Tensor] = None, u_imp: Optional[torch.Tensor] = None,
@@ -887,7 +909,21 @@ class TriPlaneGenerator(nn.Module):
         bilinear, as SuperresolutionHybrid8XDC does for rgb and x), and its adjoint (ops.resize_aa_bwd) hands the blocks' gradient
         back to the N x N rays, so every mode above composes.  N = 2 r0 supersamples (four rays per SR input pixel), N = r0 / 2 is
         EG3D's cheap training regime.  N outside [r0 / 4, 4 r0], or caller-given `u_strat` / `u_imp` that are not sized for N x N
-        rays, raise ValueError before anything is launched; N = r0 launches exactly what a call without the keyword does."""
+        rays, raise ValueError before anything is launched; N = r0 launches exactly what a call without the keyword does.
+        Multi-view: `c` [B,V,25] renders V cameras of every latent row on ONE backbone pass — a turntable, a stereo pair, the images
+        of a capture rig at one time step, a multi-view consistency term.  The planes are computed once per identity; the ray
+        marcher, the normals launch, the depth clamp, the resample and the SR blocks run at batch B·V (frame f = b·V + v, the SR
+        blocks on the ws rows of identity b; memory grows with V as it does with B); the backward sums the views' plane gradients
+        (ops.planes_sum_to_nhwc) and the SR blocks' style gradients and runs the backbone once at batch B, so every parameter
+        reaches a trainer's gradient sink once.  The per-frame entries gain a view axis after the batch axis — 'image' [B,V,3,S,S],
+        'image_raw' / 'image_normal' [B,V,3,r,r], 'image_depth' / 'image_mask' [B,V,1,r,r], 'feature_image' [B,V,r,r,32] — while
+        'planes' stays [B,3,H,W,32] and the 'query_*' keys [B,M,·]: the points belong to the identity and are evaluated once.  `c.grad`
+        is [B,V,25].  Caller-given uniforms are in frame order: `u_strat` B·V·r²·Sc elements, `u_imp` [B·V·r², Sf]; the depth clamp
+        range is global over the B·V frames, as in `synthesis(ws.repeat_interleave(V, 0), c.flatten(0, 1))` — of which view v's
+        'image_raw' / 'image_mask' / 'image_normal' are also the bits `synthesis(ws, c[:, v])` gives on that view's uniforms.  Every
+        keyword above composes; RAY_STATE_CAP_BYTES counts B·V frames.  V = 0 gives empty tensors with the view axis, nothing
+        launched; a label of any other rank, or one whose first axis is not B, raises ValueError.  A 2-D `c` is the call it always
+        was: same launches, same bits."""
         return synthesis_call.synthesis(self, ws, c, noise_mode, u_strat, u_imp, return_planes, geometry, query, normals, normal_grad,
                                         normal_camera_grad, query_normals, neural_rendering_resolution)
 

@@ -30,9 +30,9 @@ _FLIP_SIGN = {}                           # (device, dtype) -> [25] tensor of +-
 
 
 def flip_label_(label: torch.Tensor) -> torch.Tensor:
-    """`label[:, [1,2,5,6,9,10]] *= -1` IN PLACE on the caller's tensor (the side effect callers of the reference
+    """`label[..., [1,2,5,6,9,10]] *= -1` IN PLACE on the caller's tensor (the side effect callers of the reference
     see), as one multiplication by a cached sign vector: no host-built index tensor, so it is also legal inside a
-    HIP-graph capture."""
+    HIP-graph capture.  It acts on the last axis: a multi-view label [B,V,25] has the columns of every view flipped."""
     key = (label.device, label.dtype, label.shape[-1])
     sign = _FLIP_SIGN.get(key)
     if sign is None:
@@ -174,7 +174,10 @@ class _LatentBasis(nn.Module):
     def get_image(self, latent: torch.Tensor, label: torch.Tensor, *, geometry: bool = False, query=None, normals: bool = False,
                   normal_grad: bool = False, normal_camera_grad: bool = False, query_normals: bool = False,
                   neural_rendering_resolution: Optional[int] = None, **renderer_uniforms):
-        """`geometry=True`: the whole synthesis dict ('image', 'image_raw', 'image_depth', 'image_mask'; depth and mask
+        """`label` [B,25], or [B,V,25]: V cameras of every latent on one backbone pass (`synthesis` with a 3-D label) — the image
+        is then [B,V,3,S,S] and every per-frame entry of the dict has the view axis after the batch axis; `forward` of the three
+        avatar classes takes it the same way, and an `out_pose` tuple is unchanged.
+        `geometry=True`: the whole synthesis dict ('image', 'image_raw', 'image_depth', 'image_mask'; depth and mask
         differentiable) instead of the image — for silhouette / depth terms of a fitting loss.
         `query=coords` [B or 1, M, 3]: the dict as well, with 'query_sigma' / 'query_rgb' at the points (`synthesis(query=)`:
         differentiable, sharing the image's backward pass) — for density regularisation and occupancy priors.

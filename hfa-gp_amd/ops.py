@@ -1809,6 +1809,18 @@ def planes_to_nhwc(pm: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def planes_sum_to_nhwc(pm: torch.Tensor) -> torch.Tensor:
+    """pm [B,V,3,H,W,Cp], the plane gradients of the V frames of every identity → [B,H,W,3Cp]: `planes_to_nhwc` of the sum over the
+    views, in one pass (hfagp_planes_sum_to_nhwc: fp32, views added in the order 0 … V−1, no atomics; V = 1 is `planes_to_nhwc`)."""
+    _chk(pm, "planes")
+    if pm.dim() != 6 or pm.shape[2] != 3:
+        raise RuntimeError(f"planes_sum_to_nhwc: pm must be [B, V, 3, H, W, Cp], got {tuple(pm.shape)}")
+    b, v, _, h, w, cp = pm.shape
+    y = torch.empty(b, h, w, 3 * cp, device=pm.device, dtype=torch.float32)
+    L.check(L.lib().hfagp_planes_sum_to_nhwc(_ptr(pm), _ptr(y), b, v, h, w, cp, _stream()), "planes_sum_to_nhwc")
+    return y
+
+
 def style_bwd(ds: torch.Tensor, dd: Optional[torch.Tensor], styles: torch.Tensor, dcoef: Optional[torch.Tensor],
               wsq: Optional[torch.Tensor], affine_w: torch.Tensor, dw: torch.Tensor, style_gain: float = 1.0,
               accumulate: bool = True) -> torch.Tensor:

@@ -36,6 +36,8 @@ def render_frames(gen, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], per
                   to_host: bool = True, neural_rendering_resolution: Optional[int] = None) -> Iterator[torch.Tensor]:
     """`gen` is a HeadNeRF_* module; `batches` yields (driver_input [B,...], label [B,25]) on gen's device.
     Yields uint8 frames [B,3,H,W].  The label flip side effect of `get_image` is preserved.
+    A label [B,V,25] renders V cameras of every driven frame on one backbone pass (a stereo pair or a light-field frame of a
+    reenacted clip; `cam_utils.orbit_labels` for a turntable) and yields [B,V,3,H,W]: the view axis after the frame axis.
     `neural_rendering_resolution=N`: march N x N rays per frame (`get_image(neural_rendering_resolution=)`; twice the configured
     value supersamples a clip: four rays per super-resolution input pixel).  The generator keeps N afterwards."""
     res_kw = {} if neural_rendering_resolution is None else {"neural_rendering_resolution": neural_rendering_resolution}

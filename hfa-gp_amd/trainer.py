@@ -683,9 +683,21 @@ class Trainer(nn.Module):
         silhouette_weight * BCE(image_mask, matte at the rendering resolution) (`silhouette_bce`) before its one backward pass — a
         masked photometric term alone leaves the generator free to put density where nothing is looked at.  The value is kept as
         a detached device scalar in `self.last_silhouette` (None when the term is off).  The returned tuple is unchanged; an empty
-        batch ignores both; with both None the step is the one it always was."""
+        batch ignores both; with both None the step is the one it always was.
+        Multi-view: `real_image` [B,V,3,s,s] with `label` [B,V,25] (and `mask` / `matte` [B,V,1,s,s]) is one step over B latents x V
+        cameras of each — a capture rig's images of one time step share one latent: the generator renders the B·V frames on one
+        backbone pass (`synthesis` with a 3-D label), every loss term is taken over the flattened frames f = b·V + v, exactly as a 4-D
+        batch of B·V frames with repeated latents would, and the returned image is [B,V,3,s,s].  `params` stays [B,·]; in rgb mode
+        the encoder sees the first view of every latent.  The SR blocks run at batch B·V: memory grows with V as with B."""
         if self.mode == "rgb" and isinstance(params, bool):          # reference call form gen_update(real, label, person_2)
             params, person_2 = None, params
+        views = label.shape[1] if label.dim() == 3 else None
+        if views is not None:
+            for name, t in (("real_image", real_image), ("mask", mask), ("matte", matte)):
+                if t is not None and (t.dim() != 5 or t.shape[:2] != label.shape[:2]):
+                    raise ValueError(f"gen_update: a label [B,V,25] = {tuple(label.shape)} needs {name} [B,V,·,s,s], got {tuple(t.shape)}")
+            first_view = real_image[:, 0] if views else None          # (V = 0: an empty step, nothing is encoded)
+            real_image, mask, matte = (None if t is None else t.flatten(0, 1) for t in (real_image, mask, matte))
         self.last_silhouette = None
         geo = {"geometry": True} if (matte is not None and silhouette_weight > 0) else {}
         self.gen.train()
@@ -704,7 +716,7 @@ class Trainer(nn.Module):
                 t1 = t2 = self._mark()
             else:
                 if self.mode == "rgb":
-                    weights = self.gen.get_weights(real_image)
+                    weights = self.gen.get_weights(real_image if views is None else first_view)
                     if isinstance(weights, tuple):
                         weights = weights[0]
                     latent = self.gen.get_latent(weights, person_2)
@@ -713,6 +725,9 @@ class Trainer(nn.Module):
                     generated = self.gen(params, label, person_2, u_strat=u_strat, u_imp=u_imp, **geo)
                 if geo:                # the synthesis dict: 'image' for the photometric terms, 'image_mask' for the silhouette
                     opacity, generated = generated["image_mask"], generated["image"]
+                if views is not None:  # the losses see B·V frames
+                    generated = generated.flatten(0, 1)
+                    opacity = opacity.flatten(0, 1) if geo else None
                 full = generated
                 # LPIPSAlex folds a 2 x 2 pool into its first conv: the L2 term then keeps the fused pool + MSE pass and no
                 # pooled image with a gradient is needed (lpips_alex.LPIPSAlex._features_of_unpooled)
@@ -743,9 +758,12 @@ class Trainer(nn.Module):
         step_skipping([self.optimizer], absent)
         t4 = self._mark()
         self._span("fwd", t0, t1), self._span("bwd", t1, t2), self._span("allreduce", t2, t3), self._span("optim", t3, t4)
+        generated = generated.detach()
+        if views is not None:
+            generated = generated.unflatten(0, tuple(label.shape[:2]))
         if self.mode == "3dmm":
-            return torch.zeros(1, device=self.device), l2.detach(), lp.detach(), generated.detach()
-        return l2.detach(), lp.detach(), generated.detach()
+            return torch.zeros(1, device=self.device), l2.detach(), lp.detach(), generated
+        return l2.detach(), lp.detach(), generated
 
     def sample(self, real_image, label, params=None, person_2=False):
         if self.mode == "rgb" and isinstance(params, bool):

@@ -42,6 +42,8 @@
  *   hfagp_resize_aa_fwd / _bwd <- SuperresolutionHybrid8XDC.forward's antialiased bilinear F.interpolate of rgb and x to its input
  *                              resolution (synthesis(neural_rendering_resolution=N), N != the configured one) and its autograd
  *   hfagp_planes_to_nhwc    <- planes.view(N, 3, 32, H, W) of TriPlaneGenerator.synthesis (layout change for the gather)
+ *   hfagp_planes_sum_to_nhwc <- (no reference counterpart: the same layout change with autograd's sum over the V frames that
+ *                              share one identity's planes in front of it — synthesis(ws [B], c [B,V,25]))
  *   hfagp_nchw_to_nhwc / hfagp_nhwc_to_nchw <- tensor layout at the module boundary (reference tensors are NCHW)
  *   hfagp_pool_mse_fwd/_bwd <- face_pool (AdaptiveAvgPool2d) + MSELoss of gen_update (code/trainer_rgb.py:63,84-85) and its backward
  *   hfagp_pool_wmse_fwd/_bwd <- the same under a per-pixel weight, normalised per frame: the unused `mask=None` slot of gen_update
@@ -764,6 +766,12 @@ int hfagp_upsample2d_bwd(const float* g, float* gin, int64_t outer, int32_t H, i
 
 /* plane-major [B][3][H][W][Cp] -> channels-last [B][H][W][3*Cp] */
 int hfagp_planes_to_nhwc(const float* pm, float* y, int32_t B, int32_t H, int32_t W, int32_t Cp, void* stream);
+
+/* the same with the sum over the V views of an identity fused in: pm [B][V][3][H][W][Cp] (frame b*V + v plane-major) ->
+ * y [B][H][W][3*Cp], y[b,h,w,pl*Cp+ch] = sum_v pm[b,v,pl,h,w,ch] in fp32, in the fixed order v = 0 .. V-1 (no atomics: the same
+ * bits on every call); V = 1 gives hfagp_planes_to_nhwc's bits.  HFAGP_EBADARG: a null pointer or B, V, H, W < 1;
+ * HFAGP_EUNSUPPORTED: Cp % 4 != 0.  (additive within ABI 15)                                                */
+int hfagp_planes_sum_to_nhwc(const float* pm, float* y, int32_t B, int32_t V, int32_t H, int32_t W, int32_t Cp, void* stream);
 
 /* styles -> latent: dstot = (ds - styles * sum_o dd_o d_o^3 wsq[o][i]) * style_gain;
  * dw[b][:] (+)= dstot[b] . affine_w / sqrt(w_dim)                                                         */

@@ -62,6 +62,7 @@ int main(void) {
     EXPECT(hfagp_upfir_bwd(NULL, NULL, 1, 8, 8, 32, NULL) < 0, "upfir_bwd(NULL)");
     EXPECT(hfagp_upsample2d_bwd(NULL, NULL, 1, 8, 8, 32, NULL) < 0, "upsample2d_bwd(NULL)");
     EXPECT(hfagp_planes_to_nhwc(NULL, NULL, 1, 8, 8, 32, NULL) < 0, "planes_to_nhwc(NULL)");
+    EXPECT(hfagp_planes_sum_to_nhwc(NULL, NULL, 1, 2, 8, 8, 32, NULL) < 0, "planes_sum_to_nhwc(NULL)");
     EXPECT(hfagp_conv_wgrad(NULL, NULL) < 0, "conv_wgrad(NULL)");
     EXPECT(hfagp_affine_grad(NULL, NULL, NULL, NULL, 2, 512, 512, 14, NULL) < 0, "affine_grad(NULL)");
     EXPECT(hfagp_pool_mse_fwd(NULL, NULL, NULL, NULL, NULL, 1, 3, 256, 2, NULL) < 0, "pool_mse_fwd(NULL)");
