@@ -56,6 +56,12 @@ class TraceRaysArgs(C.Structure):
         [("level", C.c_float), ("decoder_lr_mul", C.c_float), ("box_warp", C.c_double)]
 
 
+class TraceMeshArgs(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("tri", "ray_origins", "ray_directions", "t_near", "t_far", "cell_start", "cell_faces",
+                                          "grid_box", "hit", "face", "t", "bary", "point", "normal", "front")] + \
+        [("R", C.c_int64), ("n_pairs", C.c_int64)] + [(n, C.c_int32) for n in ("B", "F", "tri_frames", "G")]
+
+
 class MarchingCubesArgs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("volume", "workspace", "counts", "verts", "faces")] + \
         [(n, C.c_int64) for n in ("workspace_bytes", "vert_capacity", "face_capacity")] + \
@@ -221,6 +227,7 @@ SYMBOLS = {
     "hfagp_planes_query_normals": (C.c_int, [C.POINTER(PlanesQueryArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hfagp_planes_query_normals_bwd": (C.c_int, [C.POINTER(PlanesQueryBwdArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "hfagp_trace_rays": (C.c_int, [C.POINTER(TraceRaysArgs), C.c_void_p]),
+    "hfagp_trace_mesh": (C.c_int, [C.POINTER(TraceMeshArgs), C.c_void_p]),
     "hfagp_marching_cubes_workspace_bytes": (C.c_size_t, [C.c_int32] * 3),
     "hfagp_marching_cubes_count": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),
     "hfagp_marching_cubes_emit": (C.c_int, [C.POINTER(MarchingCubesArgs), C.c_void_p]),

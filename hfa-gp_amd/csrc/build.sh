@@ -45,6 +45,7 @@ units+=(ray_limits)
 units+=(raymarch_rays_normals)
 units+=(occupancy)
 units+=(surface_trace)
+units+=(mesh_trace)
 # a unit that compiles other units' sources again (#include "x.hip"): their content is part of its object's hash
 declare -A includes=([raymarch_rays_normals]="raymarch_normals raymarch_normals_bwd raymarch_normals_camera")
 for src in "${units[@]}"; do

@@ -1395,6 +1395,64 @@ def trace_rays(planes: torch.Tensor, origins: torch.Tensor, directions: torch.Te
     return out
 
 
+_MESH_OUT = ("hit", "face", "t", "bary", "point", "normal", "front")
+
+
+def trace_mesh(tri: torch.Tensor, origins: torch.Tensor, directions: torch.Tensor, t_near: torch.Tensor, t_far: torch.Tensor,
+               grid=None, want=_MESH_OUT) -> dict:
+    """The first hit of every ray with a triangle mesh (hfagp_trace_mesh), one launch → a dict with the keys of ``want`` (any
+    non-empty subset of 'hit', 'face', 't', 'bary', 'point', 'normal', 'front'), to the definition of
+    `mesh.trace_mesh_reference` in float32: 'hit' and 'front' [B,R] uint8, 'face' [B,R] int32 (−1 for a miss), 't' [B,R], 'bary',
+    'point', 'normal' [B,R,3]; a miss has exact zeros in every float output.
+    ``tri`` [B or 1, F, 9]: the vertices (a, b, c) of every face (`mesh.TriangleMesh.tri`); rays [B,R,3] with limits [B,R]
+    (directions not normalised).  ``grid`` = None: brute force, every ray against every face.  ``grid`` = (cell_start
+    [B or 1, G³+1] int32, cell_faces [P] int32, box [B or 1, 6] float32, G) as `mesh.TriangleMesh.build_grid` makes and checks them:
+    the rays walk the cells and test the faces of their lists — the same faces win, to the bit, up to the float32 phantom candidates
+    of near-degenerate or grazing faces, which only brute force is sure to report.  This launcher checks shapes and
+    dtypes only (no synchronisation); the kernel clamps what it reads from the lists, so their content cannot make it read out of
+    bounds.  No atomics: two calls return the same bits.  Nothing carries a gradient."""
+    who = "trace_mesh"
+    want = tuple(want)
+    if not want or any(k not in _MESH_OUT for k in want):
+        raise ValueError(f"{who}: want must be a non-empty subset of {_MESH_OUT}, got {want}")
+    for name, t in (("origins", origins), ("directions", directions)):
+        if _chk(t, f"{who}: {name}").dim() != 3 or t.shape[2] != 3:
+            raise RuntimeError(f"{who}: {name} must be [B, R, 3], got {tuple(t.shape)}")
+    if origins.shape != directions.shape:
+        raise RuntimeError(f"{who}: origins {tuple(origins.shape)} and directions {tuple(directions.shape)} differ")
+    b, r = origins.shape[:2]
+    dev = origins.device
+    if _chk(tri, f"{who}: tri").dim() != 3 or tri.shape[2] != 9 or (tri.shape[0] != 1 and tri.shape[0] != b) or tri.device != dev:
+        raise RuntimeError(f"{who}: tri must be [B or 1, F, 9] on {dev} for B = {b}, got {tuple(tri.shape)} on {tri.device}")
+    frames, f = tri.shape[:2]
+    for name, t in (("t_near", t_near), ("t_far", t_far)):
+        _chk_operand(who, name, t, (b, r), origins)
+    a = L.TraceMeshArgs()
+    if grid is not None and f > 0:
+        cell_start, cell_faces, box, g = grid
+        g = int(g)
+        if not 1 <= g <= 256:
+            raise ValueError(f"{who}: grid resolution must be in [1, 256], got {g}")
+        for name, t, shape in (("cell_start", cell_start, (frames, g ** 3 + 1)), ("cell_faces", cell_faces, tuple(cell_faces.shape[:1]))):
+            if tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != dev or not t.is_contiguous():
+                raise RuntimeError(f"{who}: grid {name} must be a contiguous int32 tensor {list(shape)} on {dev}, got "
+                                   f"{list(t.shape)} {t.dtype} on {t.device}")
+        _chk_operand(who, "grid box", box, (frames, 6), origins)
+        a.cell_start, a.cell_faces, a.grid_box, a.G, a.n_pairs = _ptr(cell_start), _ptr(cell_faces), _ptr(box), g, cell_faces.shape[0]
+    shape = {"hit": ((b, r), torch.uint8), "face": ((b, r), torch.int32), "t": ((b, r), torch.float32),
+             "bary": ((b, r, 3), torch.float32), "point": ((b, r, 3), torch.float32), "normal": ((b, r, 3), torch.float32),
+             "front": ((b, r), torch.uint8)}
+    out = {k: torch.empty(shape[k][0], device=dev, dtype=shape[k][1]) for k in _MESH_OUT if k in want}
+    if b == 0 or r == 0:
+        return out
+    a.tri, a.ray_origins, a.ray_directions, a.t_near, a.t_far = (_ptr(t) for t in (tri, origins, directions, t_near, t_far))
+    for k in _MESH_OUT:
+        setattr(a, k, _ptr(out.get(k)))
+    a.R, a.B, a.F, a.tri_frames = r, b, f, (b if frames == b else 1)
+    L.check(L.lib().hfagp_trace_mesh(C.byref(a), _stream()), who)
+    return out
+
+
 def marching_cubes(volume: torch.Tensor, level: float, spacing=(1.0, 1.0, 1.0), origin=(0.0, 0.0, 0.0)):
     """Iso-surface ``volume > level`` of a float32 [n0, n1, n2] volume (hfagp_marching_cubes_count / _emit) → ``(verts [V, 3]
     float32, faces [F, 3] int32)`` on the volume's device.  Vertices ``origin + spacing * p`` at the crossed lattice edges,

@@ -30,6 +30,8 @@
  *                              density gradient and surface normal at a point, and what a loss on them back-propagates)
  *   hfagp_trace_rays        <- (no reference counterpart: the first hit of a ray list with the density iso-surface that marching
  *                              cubes exports — t, point, density gradient and normal per ray)
+ *   hfagp_trace_mesh        <- (no reference counterpart: the first hit of a ray list with a triangle mesh — face, t, barycentric
+ *                              weights, point and geometric normal per ray; brute force or through a uniform grid of face lists)
  *   hfagp_marching_cubes_count / _emit (+ _workspace_bytes) <- the .ply mesh of gen_samples.py --shapes
  *                              (skimage.measure.marching_cubes + plyfile in EG3D's shape_utils), on the GPU (ABI 14)
  *   hfagp_raymarch_normals  <- (no reference counterpart: the per-ray surface normal map of EG3D-family geometry renders — the
@@ -370,6 +372,56 @@ typedef struct {
 } HfagpTraceRaysArgs;
 
 int hfagp_trace_rays(const HfagpTraceRaysArgs* a, void* stream);
+
+/* ------------------------------------------------------------------ mesh tracing (additive to ABI 15)
+ * The first hit of every ray of a list with a triangle mesh, one launch.  Rays as hfagp_trace_rays takes them (directions NOT
+ * normalised, a point is o + t d, per-ray limits [B][R]).  The mesh arrives as per-face vertex records tri [Bt][F][9] = (a, b, c)
+ * of every face, Bt = tri_frames = 1 (one mesh for all frames) or B.  Per ray and face, every operation rounded to fp32 on its own
+ * (no fused multiply-add; the division and the square root correctly rounded), as torch evaluates the expressions:
+ *   A = a - o, B = b - o, C = c - o;   cross(x, y) = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0);   dot(x, y) = (x0 y0 + x1 y1) + x2 y2
+ *   U = dot(d, cross(B, C)), V = dot(d, cross(C, A)), W = dot(d, cross(A, B)), det = (U + V) + W
+ *   N = cross(b - a, c - a), dn = dot(d, N), t = dot(A, N) / dn
+ *   candidate iff ((U >= 0 & V >= 0 & W >= 0) | (U <= 0 & V <= 0 & W <= 0)) & det != 0 & dn != 0 & t_near <= t & t <= t_far
+ *   winner = the candidate of smallest t, equal t: the smallest face index      (a NaN fails every comparison; hits are two-sided)
+ * Outputs, each optional (at least one), [B][R] (x 3 for bary, point, normal): hit (0 / 1), face (-1 for a miss), t, bary =
+ * (U, V, W) / det (the weights of a, b, c), point = o + t d, normal = N / sqrt(dot(N, N)) (the winding's, not flipped), front =
+ * (dn < 0).  A miss writes hit = 0, face = -1, front = 0 and exact zeros everywhere else.  One writer per ray, no atomics: two
+ * calls give the same bits.
+ * cell_start == NULL: brute force, every ray against every face (the faces stream through LDS in tiles of 256 records).
+ * cell_start != NULL: a uniform grid of G^3 cells per mesh frame.  grid_box [Bt][6] = the lower corner and the cell size per axis;
+ * cell (ix, iy, iz) spans [plane_k(i), plane_k(i + 1)], plane_k(i) = lo_k + fp32(i) * cell_k; cell_start [Bt][G^3 + 1] holds
+ * offsets into cell_faces [n_pairs] (the faces of cell (ix G + iy) G + iz of frame f are cell_faces[cell_start[f][c] ..
+ * cell_start[f][c + 1])).  The ray walks the cells with a 3-D DDA of at most 3 G + 3 steps, tests the faces of every list with the
+ * arithmetic above, keeps the minimum of (t, face) and stops once that t lies before the exit of the current cell.  Offsets and face
+ * indices are clamped into [0, n_pairs] and [0, F): no content of the lists can make the kernel read out of bounds.  A ray whose
+ * origin, direction or grid entry is not finite is tested against every face instead.
+ * HFAGP_EBADARG, nothing launched: a, tri, the rays or a limit NULL; no output given; B, R, F or n_pairs negative; tri_frames not 1
+ * or B; only some of cell_start / cell_faces / grid_box given; G outside [1, 256].  HFAGP_EUNSUPPORTED: B * R >= 2^31.
+ * B = 0 or R = 0 launches nothing; F = 0 writes misses.                                                                           */
+typedef struct {
+    const float*   tri;            /* [tri_frames][F][9]                                                                      */
+    const float*   ray_origins;    /* [B][R][3]                                                                               */
+    const float*   ray_directions; /* [B][R][3], taken as given                                                               */
+    const float*   t_near;         /* [B][R]                                                                                  */
+    const float*   t_far;          /* [B][R]                                                                                  */
+    const int32_t* cell_start;     /* optional [tri_frames][G^3 + 1]; NULL = brute force                                      */
+    const int32_t* cell_faces;     /* [n_pairs], with cell_start                                                              */
+    const float*   grid_box;       /* [tri_frames][6], with cell_start                                                        */
+    uint8_t*       hit;            /* optional out [B][R]                                                                     */
+    int32_t*       face;           /* optional out [B][R]                                                                     */
+    float*         t;              /* optional out [B][R]                                                                     */
+    float*         bary;           /* optional out [B][R][3]                                                                  */
+    float*         point;          /* optional out [B][R][3]                                                                  */
+    float*         normal;         /* optional out [B][R][3]                                                                  */
+    uint8_t*       front;          /* optional out [B][R]                                                                     */
+    int64_t R;                     /* rays per frame                                                                          */
+    int64_t n_pairs;               /* entries of cell_faces                                                                   */
+    int32_t B, F;                  /* ray frames, faces                                                                       */
+    int32_t tri_frames;            /* 1 or B                                                                                  */
+    int32_t G;                     /* cells per axis, 1 .. 256 (with cell_start)                                              */
+} HfagpTraceMeshArgs;
+
+int hfagp_trace_mesh(const HfagpTraceMeshArgs* a, void* stream);
 
 /* ------------------------------------------------------------------ marching cubes (ABI 14)
  * The iso-surface of a fp32 volume V[n0][n1][n2] (last axis fastest, each extent >= 2) as a welded triangle mesh.
