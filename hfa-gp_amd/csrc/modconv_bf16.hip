@@ -1543,8 +1543,9 @@ int launch_modconv_bf16(const HfagpModconvArgs* a, Plan& pl, hipStream_t s) {
                                           "(x and y fp16) or mode 1 (y fp16); got precision %d mode %d x_f16 %d y_f16 %d ksplit %d",
                       a->precision, a->mode, a->x_f16, a->y_f16, q.ksplit);
         if (a->mode == HFAGP_CONVT3X3_UP2) {
+            // (make_plan merges EVERY 16-bit up-conv, at any grid and batch: this cannot fire; Cin <= 512 is checked above)
             HFAGP_REQUIRE(pl.merged_up, HFAGP_EUNSUPPORTED, "modconv: fp16 storage of the up-conv needs the merged four-phase "
-                                                            "kernel (grids >= 32x32 at Cin <= 512)");
+                                                            "kernel (every 16-bit up-conv plan)");
             HFAGP_REQUIRE(q.up_ns <= 1 || (long long)q.up_ns * a->x_batch_stride * (a->x_f16 ? 2 : 4) < (1ll << 32), HFAGP_EUNSUPPORTED,
                           "modconv (merged up-conv): %d samples of %lld elements exceed the 32-bit patch offsets", q.up_ns,
                           (long long)a->x_batch_stride);
